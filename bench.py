@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — self-play board-steps/sec @ 800 sims/move, 8x8 Reversi (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 A step is one self-play ply of every game on the GPU (one 800-simulation MCTS search + one move
@@ -16,10 +16,20 @@ the data path. `--gpus N` without a launcher starts the N rank processes itself
 environment. Either way every rank checks that the process group's world size equals --gpus.
 
 Printed on rank 0: one JSON line with value = committed plies of all ranks / max-over-ranks wall
-time, the roofline of the dominant kernel (the NN trunk: executed and algorithmic FLOPs per
-launch / in-situ duration), the search kernels' HBM roofline, the CPU baseline (the oracle port +
-the same net on the host cores, bounded sample) and, at N = 1, the largest single-GPU config
-(C3) and the 6x6 config (C5) measured the same way.
+time, ms_per_step = that wall time / --steps, and the roofline of the dominant kernel from the
+timed launches themselves (executed and algorithmic FLOPs per launch / in-situ duration). A plain
+run does only that: set-up, the stagger, the warm-up, the --steps timed plies, the line.
+
+--full adds, after the timed plies, every measurement that takes runs of its own: the eager
+instrumented plies (the search kernels' HBM roofline), the trunk in isolation, the other --evals
+modes, the env microbench, the CPU baseline (the oracle port + the same net on the host cores,
+bounded sample) and, at N = 1, the largest single-GPU config (C3) and the 6x6 config (C5)
+measured the same way (each over at most EXTRA_STEPS plies, so the run stays bounded whatever
+--steps is).
+
+--dump-outputs DIR writes, after the timed plies, what the timed path left its caller as
+DIR/<name>.npy (dump_outputs); the games depend on the arguments alone, so two builds run with
+the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -64,6 +74,10 @@ PRESETS = {   # BASELINE.json configs
 # measured beside the headline in the default N = 1 line (the largest single-GPU config and the
 # 6x6 variant); each is a full workload of its preset over the same --steps
 SUB_CONFIGS = ("c3", "c5")
+# --full: the measurements beside the headline (the other --evals modes, the sub-configs) time at
+# most this many plies each (a whole 8x8 game, the default window), whatever --steps is
+EXTRA_STEPS = 60
+DUMP_MAX_BYTES = 64 * 1000 * 1000     # --dump-outputs writes at most this much in all
 
 
 def parse(argv=None):
@@ -75,7 +89,18 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=None,
                     help="timed plies; the default spans a whole 8x8 game (every stage, endgame "
                          "included): the steady-state mix of continuous self-play")
-    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="warm-up plies before the timed ones (the fused launch: one eager launch "
+                         "of that many plies, then one replay of the captured timed launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own, after the timed plies: the "
+                         "instrumented eager plies (search kernels' roofline), the isolated trunk, "
+                         "the other --evals modes, the env microbench, the sub-configs (C3, C5) "
+                         "and the CPU baseline; a plain run prints the headline line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed plies, write what the timed path left its caller "
+                         "(boards, status, last moves, f64 policies, ply / game counters, seeds) "
+                         "as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--games", type=int, default=None, help="games per GPU")
     ap.add_argument("--sims", type=int, default=None)
     ap.add_argument("--batch", type=int, default=64)
@@ -83,7 +108,8 @@ def parse(argv=None):
     ap.add_argument("--filters", type=int, default=None)
     ap.add_argument("--board", type=int, default=None)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--instrument-plies", type=int, default=2)
+    ap.add_argument("--instrument-plies", type=int, default=2,
+                    help="--full: eager plies with launch timing, and as many with byte counters")
     ap.add_argument("--evals", choices=("table", "lazy", "memo", "reference"), default="table",
                     help="which NN rows are evaluated (the games are bit-identical in all four, "
                          "tests/test_gpu_memo.py, tests/test_gpu_table.py): 'reference' = every "
@@ -105,7 +131,8 @@ def parse(argv=None):
                     help="no NN-output memo (with --evals lazy: the last batch is still skipped "
                          "only if --skip-last-eval)")
     ap.add_argument("--no-evals-ab", "--no-memo-ab", dest="no_evals_ab", action="store_true",
-                    help="skip the measurements of the other --evals modes beside the headline")
+                    help="--full: skip the measurements of the other --evals modes beside the "
+                         "headline")
     ap.add_argument("--torch-bookkeeping", action="store_true",
                     help="per-ply counting / autoreset as torch ops instead of rvz_env_autoreset")
     ap.add_argument("--no-compact", action="store_true",
@@ -142,8 +169,8 @@ def parse(argv=None):
                     help="no device stamps in the timed graph (roofline from the isolated "
                          "back-to-back launches)")
     ap.add_argument("--sub-configs", default=None,
-                    help="comma-separated presets measured beside the headline (default at one "
-                         "rank with --config c2: c3,c5; 'none' for none)")
+                    help="--full: comma-separated presets measured beside the headline (default "
+                         "at one rank with --config c2: c3,c5; 'none' for none)")
     ap.add_argument("--no-stagger", action="store_true",
                     help="start the timed window with every game at the same ply (all games begin "
                          "together and stay in lockstep) instead of game g at ply g mod 60 of its "
@@ -158,8 +185,9 @@ def parse(argv=None):
                     help="N > 1 ranks sharing one card (gloo rehearsals): the ranks take turns "
                          "in the timed region, each with the card to itself, so the per-rank "
                          "report compares the shards and value (sum / max) predicts N cards")
-    ap.add_argument("--cpu-seconds", type=float, default=30.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=30.0,
+                    help="--full: bound of the CPU baseline's sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL) for real multi-GPU runs; gloo to rehearse several ranks "
@@ -687,11 +715,46 @@ def stored_pmc_clock(args):
             "source": f"{os.path.relpath(args.pmc, ROOT)}[{key}] (not measured in this run)"}
 
 
-def selfplay(args, device, rank, world, full=True):
+def dump_outputs(args, runners, rank):
+    """--dump-outputs: what the timed path left its caller after its last ply, as float arrays,
+    game g of the rank in row g (the lanes' games concatenated): the boards as 0 / 1 planes
+    (float32 [G, 2, S*S]: black, white; square s = bit s), and in float64 the status words
+    [G, 4], each game's last act (move index [G], policy vector [G, S*S + 1]), the committed
+    plies and finished games per slot and the slot's current seed. All of them are functions of
+    the arguments alone (the games are deterministic per seed). More than DUMP_MAX_BYTES: a fixed
+    seeded sample of the games, their indices in game_index.npy. Rank 0 writes <name>.npy, rank
+    r > 0 <name>.rank<r>.npy."""
+    nsq = args.board * args.board
+    bits = torch.arange(nsq, dtype=torch.int64)
+
+    def planes(x):
+        return ((x.cpu().view(-1, 1) >> bits) & 1).to(torch.float32)
+
+    parts = []
+    for r in runners:
+        b, w, st = r.eng.get_state()
+        parts.append({"board": torch.stack([planes(b), planes(w)], 1),
+                      "status": st.cpu().double(), "last_move": r.eng.idx_buf.cpu().double(),
+                      "last_policy": r.eng.p_buf.cpu().double(), "plies": r._plies.cpu().double(),
+                      "games_done": r._done.cpu().double(), "seed": r.seeds.cpu().double()})
+    out = {k: torch.cat([p[k] for p in parts]).numpy() for k in parts[0]}
+    n = out["seed"].shape[0]
+    per_game = sum(a.nbytes for a in out.values()) // n + 8
+    if n * per_game > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_BYTES // per_game, replace=False))
+        out = {k: a[keep] for k, a in out.items()}
+        out["game_index"] = keep.astype(np.float64)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(args.dump_outputs, k + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
+def selfplay(args, device, rank, world, full=True, isolated=True):
     """One workload (args: a resolved preset) on this rank: warm-up, the ply graph(s) captured,
     `steps` timed replays, the dominant kernel's in-situ roofline. With `full`, also the eager
-    instrumented plies (search kernels' durations and algorithmic bytes). Returns a dict with
-    the measured pieces (rank-local except value / dt, which are whole-job)."""
+    instrumented plies (search kernels' durations and algorithmic bytes); with `isolated`, the
+    trunk launch alone, back to back (a plain run has neither). Returns a dict with the measured
+    pieces (rank-local except value / dt, which are whole-job)."""
     import rvz
     from rvz import _lib
     from rvz import dist as rdist
@@ -770,7 +833,15 @@ def selfplay(args, device, rank, world, full=True):
     cap_kw["plies"] = ppg
     warm = max(args.warmup, 0 if args.no_graph else 1)
     wdisp = Dispatches(play_kernel(args.board, args.filters), device) if args.fused else None
-    for i in range(warm):
+    fused_graph = args.fused and not args.no_graph
+    if fused_graph:
+        # --warmup plies in one eager launch, the timed launch (ppg plies) captured, and one
+        # replay of it, so that a graph's first replay is not the timed one: the warm-up costs
+        # --warmup + ppg plies, whatever --steps is
+        wdisp(f"{tag}warmup", lambda: run._body(warm))
+        run.capture(**cap_kw)
+        wdisp(f"{tag}warmup_replay", run.ply)
+    for i in range(0 if fused_graph else warm):
         if i == 0 and not args.no_graph and not args.no_stamps and not args.fused:
             run.ply()
             grid = _lib.load().rvz_resnet_h2_grid(args.board, args.filters, eng.n_games)
@@ -795,8 +866,10 @@ def selfplay(args, device, rank, world, full=True):
     torch.cuda.synchronize(device)
     if wdisp is not None:
         wdisp.flush()
-    # fused: every warm-up launch plays ppg plies; pull-style: one eager ply, then graph replays
-    warm_plies = warm * ppg if args.fused else (1 + (warm - 1) * ppg if warm else 0)
+    # fused: the eager launch and one replay (without a graph: one-ply launches); pull-style: one
+    # eager ply, then graph replays
+    warm_plies = (warm + ppg if fused_graph else
+                  warm * ppg if args.fused else (1 + (warm - 1) * ppg if warm else 0))
 
     def rows_now():
         if args.fused:
@@ -846,6 +919,8 @@ def selfplay(args, device, rank, world, full=True):
     tab_d = (eng.table_stats - tab0).tolist() if tab0 is not None else None
     for e in engines:
         e.check()
+    if args.dump_outputs and not tag:      # the headline's timed plies only
+        dump_outputs(args, [run] if args.fused or args.lanes <= 1 else run.runners, rank)
     total, dt, value = rdist.aggregate_rate(s1 - s0, t1 - t0)
     # leaf rows evaluated per NN call in the timed region (compaction on), else the full batch
     # (a last batch left to the memo, --evals lazy, is not an NN call)
@@ -872,7 +947,7 @@ def selfplay(args, device, rank, world, full=True):
     if full:
         ms, n, bytes_ = instrumented(lane0, eng, ev, args.instrument_plies)
         eng.check()
-    t_iso = ms["nn_trunk"] if ms else isolated_trunk_ms(ev, eng.leaf_x)
+    t_iso = ms["nn_trunk"] if ms else isolated_trunk_ms(ev, eng.leaf_x) if isolated else None
 
     # roofline of the dominant kernel, the NN trunk k_resnet_h2 (MFMA-bound): FLOPs per row x
     # rows per launch / launch duration. Executed = the 16-bit MFMA products the kernel issues (3
@@ -880,12 +955,12 @@ def selfplay(args, device, rank, world, full=True):
     fpr, upr = ev.mfma_flops_per_row(), ev.useful_flops_per_row()
     peak = MFMA16_PEAK_TFLOPS
     lane_games = eng.n_games
-    iso = {"avg_ms_per_launch": round(t_iso, 4), "rows_per_launch": lane_games,
-           "achieved": round(fpr * lane_games / (t_iso * 1e-3) / 1e12, 2),
-           "frac": round(fpr * lane_games / (t_iso * 1e-3) / 1e12 / peak, 4),
-           "useful_frac": round(upr * lane_games / (t_iso * 1e-3) / 1e12 / peak, 4),
-           "timing": "HIP events over 10 back-to-back launches of one full batch, no other "
-                     "lane running"}
+    iso = t_iso and {"avg_ms_per_launch": round(t_iso, 4), "rows_per_launch": lane_games,
+                     "achieved": round(fpr * lane_games / (t_iso * 1e-3) / 1e12, 2),
+                     "frac": round(fpr * lane_games / (t_iso * 1e-3) / 1e12 / peak, 4),
+                     "useful_frac": round(upr * lane_games / (t_iso * 1e-3) / 1e12 / peak, 4),
+                     "timing": "HIP events over 10 back-to-back launches of one full batch, no "
+                               "other lane running"}
     if ftimer is not None:
         durs = [ftimer.elapsed(2 * i, 2 * i + 1) for i in range(n_rep)]
         DISPATCHES.extend((play_kernel(args.board, args.filters), f"{tag}timed", d) for d in durs)
@@ -897,9 +972,13 @@ def selfplay(args, device, rank, world, full=True):
         t_tr, rows_tr = trunk_live["ms"], trunk_live["rows"]
         timing = (f"in the timed region: all {trunk_live['launches']} trunk launches of lane 0, "
                   "first workgroup start to last end (device s_memrealtime stamps)")
-    else:
+    elif iso:
         t_tr, rows_tr, timing = t_iso, lane_games, iso["timing"]
-    ach = fpr * rows_tr / (t_tr * 1e-3) / 1e12
+    else:   # a plain run without stamps: nothing but the timed region's wall time to go by
+        t_tr, rows_tr = (t1 - t0) * 1e3 / max(1, nn_calls), rows / max(1, nn_calls)
+        timing = ("the timed region's wall time per NN call (no stamps, no isolated launches in "
+                  "this run): an upper bound of the trunk launch's duration")
+    ach =fpr * rows_tr / (t_tr * 1e-3) / 1e12
     ach_u = upr * rows_tr / (t_tr * 1e-3) / 1e12
     region = fpr * rows / (t1 - t0) / 1e12      # every lane's evaluated rows / timed wall time
     traffic, traffic_src = (stored_traffic(args, "play", ppg) if args.fused else
@@ -984,6 +1063,14 @@ def selfplay(args, device, rank, world, full=True):
     return out
 
 
+def extra_steps(args):
+    """Timed plies of a measurement beside the headline (--full): --steps, at most EXTRA_STEPS
+    (--steps itself where --plies-per-graph does not divide EXTRA_STEPS)."""
+    if args.steps <= EXTRA_STEPS or (args.plies_per_graph and EXTRA_STEPS % args.plies_per_graph):
+        return args.steps
+    return EXTRA_STEPS
+
+
 def sub_config(base, name, device, rank, world):
     """A preset measured beside the headline: the same harness, its own net and engines."""
     a = copy.copy(base)
@@ -992,6 +1079,7 @@ def sub_config(base, name, device, rank, world):
     a.config = name
     a.stamps_dump = None
     a.label = name
+    a.steps = extra_steps(base)
     apply_preset(a, name)
     r = selfplay(a, device, rank, world, full=False)
     out = {"value": round(r["value"], 2), "unit": "board-steps/s",
@@ -1073,18 +1161,27 @@ def main_c4(args, rank, world, device):
     loc["train_s"] = round(sum(r["train_s"] for r in its), 4)
     ranks = rdist.rank_report(loc, keys=("value", "seconds", "selfplay_s", "train_s",
                                          "nn_rows_per_ply"))
-    # the gradient all-reduce alone: one flat fp32 bucket of every parameter (what DDP's single
-    # 25 MB bucket carries), HIP events on the current stream, 20 back-to-back collectives
-    buf = torch.randn(n_params, device=device)
-    tdist.all_reduce(buf)
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    rdist.barrier()
-    a.record()
-    for _ in range(20):
+    if args.dump_outputs:
+        # what an iteration leaves its caller: the games' final state and the trained weights
+        dump_outputs(args, [spt.runner], rank)
+        flat = torch.cat([p.detach().reshape(-1) for p in net.parameters()]).float().cpu().numpy()
+        np.save(os.path.join(args.dump_outputs,
+                             "parameters" + (f".rank{rank}" if rank else "") + ".npy"), flat)
+    ar_ms = None
+    if args.full:
+        # the gradient all-reduce alone: one flat fp32 bucket of every parameter (what DDP's
+        # single 25 MB bucket carries), HIP events on the current stream, 20 back-to-back
+        # collectives
+        buf = torch.randn(n_params, device=device)
         tdist.all_reduce(buf)
-    b.record()
-    torch.cuda.synchronize(device)
-    ar_ms = rdist.reduce_max(a.elapsed_time(b) / 20)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        rdist.barrier()
+        a.record()
+        for _ in range(20):
+            tdist.all_reduce(buf)
+        b.record()
+        torch.cuda.synchronize(device)
+        ar_ms = rdist.reduce_max(a.elapsed_time(b) / 20)
     ev, eng = spt.evaluator, spt.eng
     if args.fused:
         # the dominant kernel is the iteration's one k_play launch (self-play of every game);
@@ -1093,13 +1190,17 @@ def main_c4(args, rank, world, device):
         rows_l = rows_sp / max(1, args.steps)
         timing = ("the iteration's k_play launch: rows it evaluated (its own counter) over the "
                   "self-play phase's device-synchronised wall time")
-    else:   # the trunk in isolation: HIP events over 10 back-to-back launches
+    elif args.full:   # the trunk in isolation: HIP events over 10 back-to-back launches
         t_tr = isolated_trunk_ms(ev, eng.leaf_x)
         rows_l = eng.n_games
         timing = "HIP events over 10 back-to-back full-batch launches after the timed region"
-    ach = ev.mfma_flops_per_row() * rows_l / (t_tr * 1e-3) / 1e12
-    uach = ev.useful_flops_per_row() * rows_l / (t_tr * 1e-3) / 1e12
-    roof = {"kernel": "k_play" if args.fused else ev.trunk_kernel_name, "bound": "mfma",
+    else:
+        t_tr = None
+    ach = uach = 0.0
+    if t_tr:
+        ach = ev.mfma_flops_per_row() * rows_l / (t_tr * 1e-3) / 1e12
+        uach = ev.useful_flops_per_row() * rows_l / (t_tr * 1e-3) / 1e12
+    roof = t_tr and {"kernel": "k_play" if args.fused else ev.trunk_kernel_name, "bound": "mfma",
             "achieved": round(ach, 2), "peak": MFMA16_PEAK_TFLOPS, "unit": "TFLOP/s",
             "frac": round(ach / MFMA16_PEAK_TFLOPS, 4),
             "mfma_flops_per_row": ev.mfma_flops_per_row(),
@@ -1109,7 +1210,7 @@ def main_c4(args, rank, world, device):
             "timing": timing}
     spt.eng.check()
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, net)
     if rank == 0:
         out = {
@@ -1144,11 +1245,11 @@ def main_c4(args, rank, world, device):
                       if args.fused and args.table else None),
             "selfplay_s": round(sp_s, 3), "train_s": round(tr_s, 3), "ranks": ranks,
             "ms_per_train_step": round(tr_s / max(1, n_train) * 1e3, 3),
-            "allreduce": {"backend": tdist.get_backend(), "world": world,
-                          "bytes": n_params * 4, "ms": round(ar_ms, 4),
-                          "algbw_GBs": round(n_params * 4 / (ar_ms * 1e-3) / 1e9, 1)},
+            "allreduce": ar_ms and {"backend": tdist.get_backend(), "world": world,
+                                    "bytes": n_params * 4, "ms": round(ar_ms, 4),
+                                    "algbw_GBs": round(n_params * 4 / (ar_ms * 1e-3) / 1e9, 1)},
             "train_loss": [round(r["train/loss"], 4) for r in its],
-            "roofline": roof, "cpu_baseline": cpu,
+            "full": args.full, "roofline": roof, "cpu_baseline": cpu,
         }
         emit(out)
     tdist.destroy_process_group()
@@ -1165,10 +1266,12 @@ def main():
         return main_c4(args, rank, world, device)
     import torch.distributed as tdist
 
-    r = selfplay(args, device, rank, world, full=True)
+    # a plain run: the headline alone; --full: the instrumented plies and the isolated trunk
+    # after its timed plies, then every other measurement
+    r = selfplay(args, device, rank, world, full=args.full, isolated=args.full)
     value, dt, net = r["value"], r["dt"], r["net"]
     evals_ab = {}
-    if not args.no_evals_ab and not args.no_compact:
+    if args.full and not args.no_evals_ab and not args.no_compact:
         # the same workload with the other --evals modes: the games are identical
         # (tests/test_gpu_memo.py, test_bench_configuration_at_full_size_plays_the_plain_games), so
         # the row differences are the memo's hits and the deferred last batches
@@ -1179,9 +1282,10 @@ def main():
             set_evals(a, mode)
             a.stamps_dump = None
             a.label = f"evals_{mode}"
+            a.steps = extra_steps(args)
             o = selfplay(a, device, rank, world, full=False)
-            evals_ab[mode] = {"value": round(o["value"], 2),
-                              "ms_per_step": round(o["dt"] / args.steps * 1e3, 3),
+            evals_ab[mode] = {"value": round(o["value"], 2), "steps": a.steps,
+                              "ms_per_step": round(o["dt"] / a.steps * 1e3, 3),
                               "nn_rows_per_ply": o["nn_rows_per_ply"],
                               "speedup_of_headline": round(value / o["value"], 4)}
             del o
@@ -1190,17 +1294,16 @@ def main():
     names = (args.sub_configs.split(",") if args.sub_configs not in (None, "none") else
              (SUB_CONFIGS if args.sub_configs is None and world == 1 and args.config == "c2"
               else ()))
-    for name in names:
+    for name in names if args.full else ():
         if name and name != args.config:
             subs[name] = sub_config(args, name, device, rank, world)
-    envb = env_bench(device, args.board) if rank == 0 else None
+    envb = env_bench(device, args.board) if rank == 0 and args.full else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, net)
 
     if rank == 0:
         roof = r["roofline"]
-        nn_dom = r["nn_dominant"]
         out = {
             "metric": f"self-play board-steps/sec @ {args.sims} sims/move, "
                       f"{args.board}x{args.board} Reversi",
@@ -1233,21 +1336,30 @@ def main():
             "table": r["table"],
             "nn_calls_per_ply": r["nn_calls_per_ply"],
             "host_enqueue_ms_per_step": r["host_enqueue_ms_per_step"],
-            "evals_ab": evals_ab or None,
-            "nn_rows_frac_of_reference": (round(r["nn_rows_per_ply"] /
-                                                max(1e-9, evals_ab["reference"]["nn_rows_per_ply"]),
-                                                4) if "reference" in evals_ab else None),
-            # the dominant kernel of a ply (by time per ply) carries "roofline"
-            "roofline": roof if nn_dom else r["search_roofline"],
-            "search_roofline" if nn_dom else "nn_roofline":
-                r["search_roofline"] if nn_dom else roof,
-            "kernels": r["kernels"],
-            "path_roofline": r["path_roofline"],
-            "env_roofline": envb,
-            "configs": subs or None,
+            "full": args.full,
+            # a plain run: the timed launches' own roofline and dispatch times, nothing else
+            "roofline": roof,
             "k_play_dispatches": dispatch_summary(),
-            "cpu_baseline": cpu,
         }
+        if args.dump_outputs:
+            out["outputs"] = args.dump_outputs
+        if args.full:
+            nn_dom = r["nn_dominant"]
+            ref_rows = evals_ab.get("reference", {}).get("nn_rows_per_ply")
+            out.update({
+                "evals_ab": evals_ab or None,
+                "nn_rows_frac_of_reference": (round(r["nn_rows_per_ply"] / max(1e-9, ref_rows), 4)
+                                              if ref_rows is not None else None),
+                # the dominant kernel of a ply (by time per ply) carries "roofline"
+                "roofline": roof if nn_dom else r["search_roofline"],
+                "search_roofline" if nn_dom else "nn_roofline":
+                    r["search_roofline"] if nn_dom else roof,
+                "kernels": r["kernels"],
+                "path_roofline": r["path_roofline"],
+                "env_roofline": envb,
+                "configs": subs or None,
+                "cpu_baseline": cpu,
+            })
         emit(out)
     tdist.destroy_process_group()
 

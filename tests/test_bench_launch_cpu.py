@@ -210,3 +210,61 @@ def test_stored_pmc_quoted_only_for_the_preset_shape():
         o = bench.parse(["--config", "c3"] + extra)
         assert bench.stored_traffic(o, "play", plies=20) == (None, None), extra
         assert bench.stored_pmc_clock(o) is None, extra
+
+
+def test_full_is_off_by_default_and_bounds_the_extra_measurements():
+    """A plain run measures the headline only (--full off); under --full the measurements beside
+    the headline time --steps plies, at most bench.EXTRA_STEPS (unless --plies-per-graph does not
+    divide that)."""
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench.extra_steps(bench.parse(["--steps", "20"])) == 20
+    assert bench.extra_steps(bench.parse(["--steps", "600"])) == bench.EXTRA_STEPS
+    assert bench.extra_steps(bench.parse(["--steps", "600", "--plies-per-graph", "20"])) == \
+        bench.EXTRA_STEPS
+    assert bench.extra_steps(bench.parse(["--steps", "700", "--plies-per-graph", "7"])) == 700
+
+
+def test_dump_outputs_writes_float_arrays_within_the_size_bound(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 .npy per array, game g in row g over the lanes, the
+    bitboards as 0 / 1 planes (square s = bit s); above the size bound the same seeded sample of
+    the games every time, with its indices."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    G = 300
+
+    def lane(k):
+        eng = types.SimpleNamespace(
+            idx_buf=torch.arange(G, dtype=torch.int32) + k, p_buf=torch.rand(G, 65).double(),
+            get_state=lambda: (torch.full((G,), -1, dtype=torch.int64),
+                               torch.arange(G, dtype=torch.int64) + k * G,
+                               torch.ones(G, 4, dtype=torch.int32)))
+        return types.SimpleNamespace(eng=eng, _plies=torch.arange(G), seeds=torch.arange(G) + 42,
+                                     _done=torch.zeros(G, dtype=torch.int64))
+
+    lanes = [lane(0), lane(1)]
+
+    def dump(name, rank=0):
+        d = tmp_path / name
+        bench.dump_outputs(types.SimpleNamespace(board=8, dump_outputs=str(d)), lanes, rank)
+        return {p.name: np.load(p) for p in sorted(d.iterdir())}
+
+    out = dump("all")
+    assert sorted(out) == ["board.npy", "games_done.npy", "last_move.npy", "last_policy.npy",
+                           "plies.npy", "seed.npy", "status.npy"]
+    assert all(a.dtype in (np.float32, np.float64) and a.shape[0] == 2 * G for a in out.values())
+    assert out["board.npy"].shape == (2 * G, 2, 64) and (out["board.npy"][:, 0] == 1).all()
+    white = out["board.npy"][:, 1]                  # game g's white bitboard is g
+    assert np.array_equal((white * 2.0 ** np.arange(64)).sum(1), np.arange(2.0 * G))
+    assert np.array_equal(out["last_policy.npy"][G:], lanes[1].eng.p_buf.numpy())
+    per_game = sum(a.nbytes for a in out.values()) // (2 * G) + 8
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100 * per_game)
+    a, b = dump("sample_a", rank=1), dump("sample_b", rank=1)
+    assert "game_index.rank1.npy" in a and sum(x.nbytes for x in a.values()) <= 100 * per_game
+    idx = a["game_index.rank1.npy"].astype(int)
+    assert len(idx) == 100 and np.array_equal(a["plies.rank1.npy"], out["plies.npy"][idx])
+    assert all(np.array_equal(a[k], b[k]) for k in a)

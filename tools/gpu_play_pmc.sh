@@ -15,5 +15,5 @@ for CTRS in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES" "SQ_VALU_MFMA_BUSY_CYCLES 
       -- python bench.py $ARGS > "$OUT/play_pmc_${TAG}_$i.log" 2>&1
   rc=$?; echo "pass $i rc=$rc"; [ $rc -ne 0 ] && exit $rc
 done
-python tools/pmc_kernel_avg.py "k_play" --last ${LAST:-3} "$OUT"/play_pmc_${TAG}_* > "$OUT/play_pmc_${TAG}.txt"
+python tools/pmc_kernel_avg.py "k_play" --last ${LAST:-2} "$OUT"/play_pmc_${TAG}_* > "$OUT/play_pmc_${TAG}.txt"
 cat "$OUT/play_pmc_${TAG}.txt"

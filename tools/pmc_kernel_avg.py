@@ -3,8 +3,9 @@
     python tools/pmc_kernel_avg.py <kernel substring> [--last N] <run_dir> [<run_dir> ...]
 
 --last N: per run dir, only the last N matching dispatches (in dispatch order) are averaged —
-bench.py's k_play dispatches are the phase-stagger launch (shorter, first), the warm-up launches
-and the timed one; the last N skip the stagger launch.
+bench.py's k_play dispatches are the phase-stagger launch and the eager --warmup-ply launch (both
+shorter, first), then one warm-up replay of the timed launch and the timed one; --last 2 takes
+those two.
 """
 import collections
 import csv

@@ -17,8 +17,9 @@ import sys
 from collections import defaultdict
 
 # play: the fused self-play launch; its mean is over the last LAST_PLAY dispatches (bench.py's
-# --steps-ply launches: the warm-up replays and the timed one; the first eager ply is shorter)
-LAST_PLAY = 3
+# --steps-ply launches: the warm-up replay and the timed one; the stagger and the eager --warmup-ply
+# launch before them are shorter)
+LAST_PLAY = 2
 KERNELS = {"play": "k_play<", "step": "k_step<", "act": "k_act<", "expand_backup": "k_expand_backup<",
            "reset": "k_reset<", "nn_trunk": ("k_resnet_h2<", "k_resnet_split<"), "nn_heads": "k_heads_fc(",
            "nn_conv3x3": "igemm_fwd_gtcx35_nhwc_fp32_bx0_ex1_bt128x64x16"}
