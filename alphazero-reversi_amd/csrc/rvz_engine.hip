@@ -106,6 +106,14 @@ struct View {  // kernel argument: device pointers + sizes
     int memo;
     uint32_t* carry;  // [G]
     float* bval;      // [G][2E]
+    // Dirichlet noise on the priors of a root's children (rvz_search_root_noise; noise_eps = 0:
+    // off): P' = fl(fl(noise_om * P) + fl(noise_eps * eta)), eta from csrc/rvz_dirichlet.hip.h.
+    // seed32[g]: the seed game g's MT19937 stream was last seeded with (reset_game), the key of
+    // its noise
+    float noise_eps, noise_om, noise_alpha;
+    uint32_t noise_salt;
+    uint32_t* seed32;  // [G]
+    float* eta;        // [G][64] the current root's eta per square (written when the root is created)
 };
 
 // A link names an expanded node of the previous search's tree (the same position as the new
@@ -266,6 +274,30 @@ __device__ __forceinline__ float ucb_score(const Node& c, float sqrt_np, int tur
     return q + u;
 }
 
+#include "rvz_dirichlet.hip.h"
+
+// Root noise in two steps, both behind wave-uniform branches on v.noise_eps > 0 (nothing of it
+// runs with the noise off). root_noise_sample: when a search creates its root (select_phase,
+// first batch; few registers are live there) eta goes to the game's row of v.eta, one lane per
+// square; `root` is the root's position, its disc count the root's tag (every ply places a disc,
+// so a game never has two roots with one count), V its legal mask. root_noise_mix: wherever the
+// root is expanded later (the next launch's expand phase, the memo, a table hit) the prior of
+// square sq becomes P' = fl(fl((1 - eps) P) + fl(eps eta)), each operation rounded on its own,
+// at the cost of one load: the sampler's registers never meet the walk's or the act's.
+__device__ __forceinline__ void root_noise_sample(const View& v, int g, int lane,
+                                                  const GameS& root, uint64_t V) {
+    const float eta = dirichlet_eta(v.seed32[g], v.noise_salt,
+                                    (uint32_t)__popcll(root.black | root.white), v.noise_alpha,
+                                    V, lane, v.err);
+    v.eta[(size_t)g * WAVE + lane] = eta;
+    // the memo may expand the root later in this launch, reading other lanes' squares
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+}
+__device__ __forceinline__ float root_noise_mix(const View& v, int g, int sq, float prob) {
+    const float eta = v.eta[(size_t)g * WAVE + sq];
+    return __fadd_rn(__fmul_rn(v.noise_om, prob), __fmul_rn(v.noise_eps, eta));
+}
+
 // Inputs of the pending expand + backup, all loaded at the head of a launch (no dependent loads:
 // the leaf's meta word is kept in per-game scratch by the select that queued it).
 struct ExpIn {
@@ -342,6 +374,8 @@ __device__ __forceinline__ int expand_backup_phase(const View& v, int g, int lan
                          (lane < NSQ && !__builtin_isfinite(prob));
         if (__builtin_amdgcn_ballot_w64(bad) && lane == 0) atomicOr(v.err, ERR_NN);
     }
+    if (leaf == 0 && v.noise_eps > 0.0f)   // the root's children: Dirichlet noise on the priors
+        prob = root_noise_mix(v, g, lane, prob);
     const int base = 1 + x.e * NSQ;
     if (base + NSQ > v.M) {
         if (lane == 0) atomicOr(v.err, ERR_POOL);
@@ -423,9 +457,17 @@ __device__ __forceinline__ int memo_expand_backup(const View& v, int g, int lane
         if (lane == 0) atomicOr(v.err, ERR_POOL);
         return -1;
     }
+    float prior = lane < nch ? oc.p : 0.0f;
+    if (leaf == 0 && v.noise_eps > 0.0f) {
+        // the new root takes the carried node's clean priors (a node the memo links to is never a
+        // root: the carried node was a child of the previous root, expanded from its own NN
+        // row); the noise goes into the new root's copy. Child i sits in lane i, its square is
+        // m_sq(ocm)
+        if (lane < nch) prior = root_noise_mix(v, g, m_sq(ocm), prior);
+    }
     if (lane < nch) {
         Node c;
-        c.n = 0; c.w = 0.0f; c.p = oc.p;
+        c.n = 0; c.w = 0.0f; c.p = prior;
         const bool expd = m_nchild(ocm) > 0 && !m_term(ocm);
         c.c = __uint_as_float(expd ? link_pack(ob + lane, m_nchild(ocm), m_block(ocm))
                                    : LINK_NONE);
@@ -470,6 +512,7 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
         }
         const uint64_t rl = root.over ? 0ull : legal_wave<BS>(mine(root), theirs(root), lane);
         if (lane == 0) v.root_legal[g] = rl;
+        if (v.noise_eps > 0.0f && rl != 0ull) root_noise_sample(v, g, lane, root, rl);
         ab += 20 + 8;
     }
     ab += 32 + 8;  // game state, root meta + N
@@ -935,6 +978,7 @@ template <int BS>
 __device__ __forceinline__ void reset_game(const View& v, int g, int lane, uint32_t seed,
                                            uint32_t* k) {
     if (lane == 0) {  // mt19937_seed (init_genrand): inherently sequential
+        v.seed32[g] = seed;   // the key of the game's root noise (rvz_search_root_noise)
         uint32_t sd = seed;
         for (int pos = 0; pos < 624; ++pos) {
             k[pos] = sd;
@@ -1095,6 +1139,8 @@ struct rvz_engine {
     const void* tab_blob = nullptr;   // the weight blob the current generation's rows came from
     // rvz_play_gate: the per-XCD pass gate of the 10x128 k_play form (fraction < 0: the default)
     double gate_frac = -1.0, gate_us = 0.0, gate_late_us = 0.0;
+    // the device's g_noise_err word (rvz_dirichlet_noise's exhaustion flag), read by rvz_check
+    int32_t* noise_err = nullptr;
 };
 
 static thread_local std::string g_create_error;
@@ -1221,6 +1267,9 @@ int rvz_create(const rvz_config* cfg, rvz_engine** out) {
     }
     if (hipSetDevice(cfg->device) != hipSuccess) { g_create_error = "hipSetDevice failed"; return RVZ_EHIP; }
     rvz_engine* e = new rvz_engine();
+    if (hipGetSymbolAddress(reinterpret_cast<void**>(&e->noise_err), HIP_SYMBOL(g_noise_err)) !=
+        hipSuccess)
+        e->noise_err = nullptr;
     e->cfg = *cfg;
     e->BS = bs;
     e->NSQ = bs * bs;
@@ -1257,6 +1306,12 @@ int rvz_create(const rvz_config* cfg, rvz_engine** out) {
     v.memo = 0;
     v.carry = dalloc<uint32_t>(e, G);
     v.bval = dalloc<float>(e, (size_t)G * 2 * E);
+    v.noise_eps = 0.0f;
+    v.noise_om = 1.0f;
+    v.noise_alpha = 1.0f;
+    v.noise_salt = 0u;
+    v.seed32 = dalloc<uint32_t>(e, G);
+    v.eta = dalloc<float>(e, (size_t)G * WAVE);
     e->stats_buf = dalloc<unsigned long long>(e, 3 * (size_t)G);
     v.stats = nullptr;
     for (void* p : e->allocs)
@@ -1312,15 +1367,22 @@ int rvz_sync(rvz_engine* e) {
 
 int rvz_check(rvz_engine* e, int32_t* host_err) {
     if (!e) return RVZ_EINVAL;
-    int32_t h = 0;
+    int32_t h = 0, hn = 0;
     RVZ_HIP(hipMemcpyAsync(&h, e->v.err, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream), e);
+    if (e->noise_err)   // rvz_dirichlet_noise's flag (it has no engine): the device's word
+        RVZ_HIP(hipMemcpyAsync(&hn, e->noise_err, sizeof(int32_t), hipMemcpyDeviceToHost,
+                               e->stream), e);
     RVZ_HIP(hipStreamSynchronize(e->stream), e);
+    if (hn) RVZ_HIP(hipMemsetAsync(e->noise_err, 0, sizeof(int32_t), e->stream), e);
+    const int32_t own = h;
+    h |= hn;
     if (host_err) *host_err = h;
     if (h) {
-        RVZ_HIP(hipMemsetAsync(e->v.err, 0, sizeof(int32_t), e->stream), e);
+        if (own) RVZ_HIP(hipMemsetAsync(e->v.err, 0, sizeof(int32_t), e->stream), e);
         e->err = "device error word " + std::to_string(h) +
                  " (1: rng stream exhausted, 2: node pool, 4: path depth, 8: non-finite NN "
-                 "value or probability, 16: rvz_play queue wait timed out)";
+                 "value or probability, 16: rvz_play queue wait timed out, 32: root-noise "
+                 "Gamma sampler out of attempts)";
         return RVZ_EDEVICE;
     }
     return RVZ_OK;
@@ -1611,6 +1673,42 @@ int rvz_search_memo_reset(rvz_engine* e) {
     if (!e) return RVZ_EINVAL;
     const int r = memo_drop(e);
     return r != RVZ_OK ? r : table_bump(e);   // new weights: the table's rows are stale too
+}
+
+// alpha as the kernels take it: a positive, finite float32 (NaN fails the comparisons)
+static bool noise_alpha_ok(double alpha) { return alpha >= 1.0e-37 && alpha <= 3.0e38; }
+
+int rvz_search_root_noise(rvz_engine* e, double alpha, double epsilon, uint32_t salt) {
+    if (!e) return RVZ_EINVAL;
+    if (!noise_alpha_ok(alpha) || !(epsilon >= 0.0 && epsilon <= 1.0)) {
+        e->err = "rvz_search_root_noise: alpha a positive finite float32 (1e-37 .. 3e38), "
+                 "0 <= epsilon <= 1";
+        return RVZ_EINVAL;
+    }
+    if (e->pending || (e->searching && e->next_batch > 0)) {
+        e->err = "rvz_search_root_noise inside a search";
+        return RVZ_EINVAL;
+    }
+    // eps and 1 - eps as float32, once, here: the kernels (and a test's restatement) use these
+    const float eps = (float)epsilon;
+    e->v.noise_eps = eps;
+    e->v.noise_om = 1.0f - eps;
+    e->v.noise_alpha = (float)alpha;
+    e->v.noise_salt = salt;
+    return RVZ_OK;
+}
+
+int rvz_dirichlet_noise(int32_t bs, int32_t n, const uint64_t* legal, const uint32_t* seed32,
+                        const int32_t* tag, uint32_t salt, double alpha, float* out,
+                        uint32_t* out_bits, void* stream) {
+    if ((bs != 8 && bs != 6) || n < 0 || !noise_alpha_ok(alpha) ||
+        (n > 0 && (!legal || !seed32 || !tag || !out)) || ((uintptr_t)out_bits & 15) != 0)
+        return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    dim3 grid((n + WPB - 1) / WPB), block(WPB * WAVE);
+    if (bs == 8) hipLaunchKernelGGL(k_dirichlet<8>, grid, block, 0, (hipStream_t)stream, n, legal, seed32, tag, salt, (float)alpha, out, out_bits);
+    else hipLaunchKernelGGL(k_dirichlet<6>, grid, block, 0, (hipStream_t)stream, n, legal, seed32, tag, salt, (float)alpha, out, out_bits);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }
 
 int rvz_play_gate(rvz_engine* e, double fraction, double timeout_us, double late_us) {

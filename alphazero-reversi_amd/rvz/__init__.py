@@ -12,7 +12,7 @@ Batched core:
 """
 from ._lib import RvzError, load  # noqa: F401
 from .engine import (Engine, board_apply, board_canonical, board_legal,  # noqa: F401
-                     policy_softmax)
+                     dirichlet_noise, policy_softmax)
 from .game import Board, ReversiGame  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401

@@ -68,6 +68,9 @@ SIGNATURES = {
     "rvz_search_memo": (C.c_int, [_P, C.c_int32]),
     "rvz_search_memo_reset": (C.c_int, [_P]),
     "rvz_search_live_count": (C.c_void_p, [_P]),
+    "rvz_search_root_noise": (C.c_int, [_P, C.c_double, C.c_double, C.c_uint32]),
+    "rvz_dirichlet_noise": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_uint32, C.c_double,
+                                      _P, _P, _P]),
     "rvz_search_rows_total": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "rvz_timer_create": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p)]),
     "rvz_timer_record": (C.c_int, [_P, C.c_int32, _P]),
@@ -131,6 +134,28 @@ def load() -> C.CDLL:
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+_NO_EPSILON = object()
+
+
+def check_noise_args(alpha, epsilon=_NO_EPSILON) -> None:
+    """The argument rules of rvz_search_root_noise / rvz_dirichlet_noise, checked on the host
+    before any device call: alpha a positive finite float32 (1e-37 .. 3e38), epsilon (when
+    given) in [0, 1]."""
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError, OverflowError):
+        raise RvzError(f"root noise: alpha must be a positive finite number, not {alpha!r}")
+    if not 1.0e-37 <= a <= 3.0e38:
+        raise RvzError(f"root noise: alpha must be positive and finite (float32), not {alpha!r}")
+    if epsilon is not _NO_EPSILON:
+        try:
+            e = float(epsilon)
+        except (TypeError, ValueError):
+            raise RvzError(f"root noise: epsilon must be a number in [0, 1], not {epsilon!r}")
+        if not 0.0 <= e <= 1.0:
+            raise RvzError(f"root noise: epsilon must be in [0, 1], not {epsilon!r}")
 
 
 def check(rc: int, handle=None, what: str = "") -> int:

@@ -339,6 +339,17 @@ class Engine:
         the default 0.8 / 400 us / 200 us). Timing only: the same games with any setting."""
         self._call("rvz_play_gate", float(fraction), float(timeout_us), float(late_us))
 
+    def root_noise(self, alpha: float, epsilon: float, salt: int = 0):
+        """rvz_search_root_noise: Dirichlet(alpha) noise mixed with weight epsilon into the priors
+        of every search root's children (AlphaZero's exploration noise), in search() / act() and
+        in play() alike; epsilon = 0 turns it off (the default: the reference's games, bit for
+        bit). eta of a root is a function of the game's seed, the root's disc count, salt, alpha
+        and the legal mask only (dirichlet_noise() returns the same rows). Not inside a search;
+        set it before capturing a graph (a captured launch keeps the setting of its capture)."""
+        _lib.check_noise_args(alpha, epsilon)
+        self._call("rvz_search_root_noise", float(alpha), float(epsilon), int(salt) & 0xFFFFFFFF)
+        self.noise = (float(alpha), float(epsilon), int(salt) & 0xFFFFFFFF)
+
     # ------------------------------------------------------------------ search
     def search_begin(self):
         self._call("rvz_search_begin")
@@ -482,6 +493,35 @@ def board_canonical(black: torch.Tensor, white: torch.Tensor, status: torch.Tens
     check(lib.rvz_board_canonical(board_size, n, ptr(black), ptr(white), ptr(status), ptr(out),
                                   _lib.stream_handle(black.device)), None, "rvz_board_canonical")
     return out
+
+
+def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor, salt: int,
+                    alpha: float, board_size: int = 8, bits: bool = False):
+    """rvz_dirichlet_noise: the eta rows Engine.root_noise mixes into the roots' priors, by the
+    same device function. legal int64 [n] (the roots' legal masks, bit patterns), seed32 [n] (the
+    games' seeds, taken mod 2^32), tag [n] (the roots' disc counts). Returns eta float32
+    [n, S*S+1] (0 at illegal squares and at the pass index), and with bits=True also the
+    attempt-0 Philox4x32-10 block of every square, int32 [n, S*S, 4] (uint32 bit patterns)."""
+    _lib.check_noise_args(alpha)
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    lib = _lib.load()
+    dev = legal.device
+    lg = legal.to(torch.int64).contiguous()
+    n = lg.numel()
+    sd = seed32.to(dev).to(torch.int64).bitwise_and(0xFFFFFFFF).to(torch.int32).contiguous()
+    tg = tag.to(dev).to(torch.int32).contiguous()
+    if sd.numel() != n or tg.numel() != n:
+        raise RvzError("dirichlet_noise: legal, seed32 and tag hold one entry per root")
+    nsq = board_size * board_size
+    out = torch.empty(n, nsq + 1, dtype=torch.float32, device=dev)
+    ob = torch.empty(n, nsq, 4, dtype=torch.int32, device=dev) if bits else None
+    if n:
+        check(lib.rvz_dirichlet_noise(board_size, n, ptr(lg), ptr(sd), ptr(tg),
+                                      int(salt) & 0xFFFFFFFF, float(alpha), ptr(out),
+                                      ptr(ob) if bits else None, _lib.stream_handle(dev)),
+              None, "rvz_dirichlet_noise")
+    return (out, ob) if bits else out
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

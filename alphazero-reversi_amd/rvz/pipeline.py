@@ -37,8 +37,11 @@ class SelfPlayTrainer:
                  weight_decay: float = 1e-4, gradient_clip: float = 1.0,
                  graph: bool = True, compact_leaves: bool = True, lr_milestones=(),
                  lr_gamma: float = 0.1, memo: bool = True, fused: bool = True,
-                 table_slots: Optional[int] = None, table_discs: int = 14):
-        """table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
+                 table_slots: Optional[int] = None, table_discs: int = 14,
+                 root_noise=None):
+        """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
+        roots of the self-play games (Engine.root_noise), set before any graph is captured.
+        table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
         on 6x6): 2^20 slots = 608 MB, 2^12 = 2.4 MB."""
@@ -60,6 +63,8 @@ class SelfPlayTrainer:
         bs = int(getattr(model, "board_size", 8))
         self.eng = Engine(games, num_simulations, batch_size, c_puct, board_size=bs,
                           device=self.device, compact_leaves=compact_leaves, memo=memo)
+        if root_noise is not None:
+            self.eng.root_noise(*root_noise)
         self.max_plies = bs * bs - 4
         # fused: every game of the iteration in ONE rvz_play launch with device records, the
         # memo's deferred last batch and the cross-game table (a new generation per refresh());

@@ -16,7 +16,7 @@ from __future__ import annotations
 import os
 import time
 from datetime import datetime
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -321,6 +321,15 @@ class SelfPlay:
     args["seed"] (opt-in, the round 1-5 behaviour): game i of the j-th game played by this
     object instead draws from its own np.random.seed(seed + j) stream, and np.random is not
     touched.
+
+    args["root_noise"] = True (opt-in) turns on Dirichlet noise at the search roots
+    (Engine.root_noise) with args.get("dirichlet_alpha", 0.03) and
+    args.get("dirichlet_epsilon", 0.25), the reference's config.py:25-26 defaults, and
+    args.get("dirichlet_salt", 0). The bare presence of dirichlet_alpha / dirichlet_epsilon does
+    NOT enable it: the reference's pipeline always passes them (pipeline.py:158-159) and the
+    reference ignores them, so honouring them would silently end drop-in parity. The noise is
+    keyed by each game's seed (seed_base + game index, whichever randomness mode hands out the
+    move-sampling draws) and draws nothing from np.random.
     """
 
     def __init__(self, model, args: dict, evaluator: Optional[Callable] = None):
@@ -347,6 +356,7 @@ class SelfPlay:
         self.save_dir = args.get("save_dir", "self_play_data")
         os.makedirs(self.save_dir, exist_ok=True)
         self.seed = None if args.get("seed") is None else int(args["seed"])
+        self.root_noise = root_noise_args(args)
         self.fused = bool(args.get("fused", isinstance(self.evaluator, LeafEvaluator)))
         if self.fused and not isinstance(self.evaluator, LeafEvaluator):
             raise ValueError("SelfPlay: args['fused'] plays the h2 LeafEvaluator inside the "
@@ -354,9 +364,13 @@ class SelfPlay:
         self.games_played = 0
         self.reference_order_passes = 0
 
-    def _run(self, num_games: int, seed_base: int, draws: Optional[np.ndarray] = None):
+    def _run(self, num_games: int, seed_base: int, draws: Optional[np.ndarray] = None,
+             game_ids: Optional[Sequence[int]] = None):
         """Play num_games fresh games to their end; draws (float64 [num_games, RVZ_DRAWS]):
         each game's move-sampling values (None: game i draws from np.random.seed(seed_base + i)).
+        game_ids: game i's seed is seed_base + game_ids[i] instead of seed_base + i (a pass that
+        replays some games of a call: the root noise is keyed by the seed, so a game keeps its
+        noise in every pass).
         Returns the records (rec_black, rec_white, rec_side, rec_idx [P, G], rec_p [P, G, npol],
         final status [G, 4]) and the draws each game consumed (int32 [G], host)."""
         # compacted leaf batches: only the live leaves are evaluated (as _process_batch does);
@@ -370,6 +384,8 @@ class SelfPlay:
                      compact_leaves=bool(self.args.get("compact_leaves", True)),
                      memo=bool(self.args.get("memo", isinstance(self.evaluator, LeafEvaluator)
                                              and self.args.get("fused_softmax", True))))
+        if self.root_noise is not None:
+            eng.root_noise(*self.root_noise)
         if hasattr(self.evaluator, "bind"):
             self.evaluator.bind(eng)
         max_plies = bs * bs - 4         # every ply places a disc (passes are inside make_move)
@@ -377,6 +393,9 @@ class SelfPlay:
                              fused_softmax=self.args.get("fused_softmax", True),
                              seed_base=seed_base, record=True, max_plies=max_plies,
                              fused=self.fused)
+        if game_ids is not None:
+            run.seeds.copy_(torch.tensor([seed_base + int(i) for i in game_ids],
+                                         dtype=torch.int64))
         run.start()
         if draws is not None:
             eng.set_draws(torch.from_numpy(np.ascontiguousarray(draws, np.float64)))
@@ -397,9 +416,13 @@ class SelfPlay:
         every pass, game -> (pass, column))."""
         from ._lib import RVZ_DRAWS
         T = float(self.args.get("temperature", 1.0))
+        # the games' seeds (the key of the root noise; the move-sampling draws come from `U`):
+        # games_played + the game's index in this call, the same in every pass
         passes, where, _ = sequential_draw_passes(
             num_games, self.board_size ** 2 - 4, RVZ_DRAWS, T > 0, np.random,
-            lambda U: self._run(len(U), 0, draws=U))
+            (lambda U, todo: self._run(len(U), self.games_played, draws=U, game_ids=todo))
+            if self.root_noise is not None else (lambda U, todo: self._run(len(U), 0, draws=U)),
+            with_games=True)
         self.reference_order_passes = len(passes)
         return passes, where
 
@@ -471,8 +494,21 @@ class SelfPlay:
                 "values": t["value_targets"].cpu().numpy()}
 
 
+def root_noise_args(args: dict):
+    """SelfPlay's root-noise setting from its args: None unless args["root_noise"] is true, else
+    (alpha, epsilon, salt) from dirichlet_alpha (0.03), dirichlet_epsilon (0.25) and
+    dirichlet_salt (0), validated here, before any device call."""
+    from ._lib import check_noise_args
+    if not args.get("root_noise", False):
+        return None
+    alpha = args.get("dirichlet_alpha", 0.03)
+    eps = args.get("dirichlet_epsilon", 0.25)
+    check_noise_args(alpha, eps)
+    return float(alpha), float(eps), int(args.get("dirichlet_salt", 0)) & 0xFFFFFFFF
+
+
 def sequential_draw_passes(num_games: int, max_draws: int, piece: int, draws_on: bool, rng,
-                           play: Callable):
+                           play: Callable, with_games: bool = False):
     """Lockstep passes that give every game the piece of ONE random_sample() stream it would
     draw if the games ran one after another (SelfPlay's class docstring; self_play.py:66-101
     with mcts.py:684). rng: a NumPy RandomState or the np.random module (its state is read once
@@ -480,6 +516,7 @@ def sequential_draw_passes(num_games: int, max_draws: int, piece: int, draws_on:
     most max_draws values (one per move; none when draws_on is False, i.e. temperature 0,
     mcts.py:679-681). play(U float64 [k, piece]) plays k fresh games, game j drawing U[j, 0],
     U[j, 1], ... in order, and returns (payload, used int [k]: the values each game drew).
+    with_games: play is called as play(U, games), games being the indices of the k games.
     Returns (payloads of every pass, game -> (pass, index in that pass), draws per game)."""
     G = int(num_games)
     rs = np.random.RandomState()
@@ -494,7 +531,8 @@ def sequential_draw_passes(num_games: int, max_draws: int, piece: int, draws_on:
         todo = [g for g in range(G) if prev[g] != int(off[g])]
         if not todo:
             break
-        payload, used = play(np.stack([stream[off[g]:off[g] + piece] for g in todo]))
+        U = np.stack([stream[off[g]:off[g] + piece] for g in todo])
+        payload, used = play(U, list(todo)) if with_games else play(U)
         for j, g in enumerate(todo):
             if not 0 <= int(used[j]) <= max_draws:
                 raise RuntimeError(f"game drew {int(used[j])} values (at most {max_draws})")

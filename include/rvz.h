@@ -63,7 +63,10 @@ void rvz_destroy(rvz_engine *e);
 const char *rvz_last_error(const rvz_engine *e);          /* e may be NULL: last create error */
 int rvz_set_stream(rvz_engine *e, void *hip_stream);        /* hipStream_t; NULL = default */
 int rvz_sync(rvz_engine *e);                                /* hipStreamSynchronize */
-int rvz_check(rvz_engine *e, int32_t *host_err);            /* sync + read/clear device error */
+/* sync + read/clear the device error word: bit 1 a game's draw stream ran out, 2 node pool, 4 path
+ * depth, 8 non-finite NN value or probability, 16 an rvz_play queue wait timed out, 32 a root-noise
+ * Gamma sampler ran out of attempts (rvz_search_root_noise / rvz_dirichlet_noise) */
+int rvz_check(rvz_engine *e, int32_t *host_err);
 int rvz_version(void);
 
 /* ---- env, engine-owned (board.py / game.py over n_games boards in HBM) --------------------- */
@@ -169,6 +172,42 @@ const int32_t *rvz_search_live_count(const rvz_engine *e);
  * search. */
 int rvz_search_memo(rvz_engine *e, int32_t on);
 int rvz_search_memo_reset(rvz_engine *e);
+/* Dirichlet noise on the priors of a search root's children (AlphaZero's exploration noise; the
+ * reference carries dirichlet_alpha / dirichlet_epsilon, config.py:25-26, but no code reads
+ * them). Off by default and unless epsilon > 0; with it off every game, counter and output byte is
+ * what it is without this call. With it on, wherever a search's ROOT is expanded (from an
+ * evaluated row in rvz_search_step / rvz_act / rvz_play, from the memo, from a table hit) each
+ * child's prior becomes
+ *     P'(s) = fl32( fl32((1 - eps) * P(s)) + fl32(eps * eta(s)) ),  s over the root's legal squares,
+ * P the softmaxed prior the expansion writes otherwise, eps = (float)epsilon and 1 - eps =
+ * 1.0f - eps (float32, computed once here), the two products and the sum each rounded on their
+ * own. Non-root expansions, values, backups, UCB and rvz_act are unchanged; the memo's carried
+ * priors and the table's logits stay clean (the mix goes into the root's own copy).
+ * eta ~ Dirichlet(alpha, ..., alpha) over the k legal squares (k = 1: eta = 1) is a pure function
+ * of (seed32[g], the root's disc count, salt, (float)alpha, the root's legal mask), seed32[g] being
+ * the uint32 game g's MT19937 stream was last seeded with (rvz_env_reset, rvz_env_autoreset,
+ * rvz_play's autoreset): it does not depend on the launch geometry, the schedule, pull-style or
+ * fused play, the memo / table / compaction / gate settings, and it consumes none of the game's
+ * move-sampling draws (rvz_env_draws is unaffected). Generator: Philox4x32-10, key (seed32, salt),
+ * counter (attempt, square, disc count, 0); Marsaglia-Tsang Gamma in the log domain
+ * (csrc/rvz_dirichlet.hip.h). A Gamma rejection loop that ran out of its 64 attempts takes its
+ * proposal and sets device error bit 32 (rvz_check).
+ * RVZ_EINVAL: alpha <= 0, non-finite or not a positive normal float32 (outside 1e-37 .. 3e38);
+ * epsilon outside [0, 1]; inside a search. The setting travels in the kernel arguments: launches issued (or captured into a
+ * graph: rvz_play, rvz_search_step, rvz_act) before the call keep the setting they were issued
+ * with, so a captured graph replays with the noise setting of its capture; set it before
+ * capturing. */
+int rvz_search_root_noise(rvz_engine *e, double alpha, double epsilon, uint32_t salt);
+/* Stateless, on caller arrays: the eta rows of n roots, by the SAME device function the search
+ * uses. legal uint64 [n] (bits >= S*S ignored), seed32 uint32 [n], tag int32 [n] (the root's disc
+ * count), out float32 [n][S*S+1] (0 at illegal squares and at the pass index; a row without legal
+ * squares is all zeros), out_bits (nullable, 16-byte aligned) uint32 [n][S*S][4]: the attempt-0
+ * Philox block of every square. RVZ_EINVAL: board size, n < 0, a bad alpha (as above), a null
+ * legal / seed32 / tag / out with n > 0. The call has no engine: an exhausted rejection loop sets
+ * a word of the device that the next rvz_check of any engine on that device reports (bit 32). */
+int rvz_dirichlet_noise(int32_t board_size, int32_t n, const uint64_t *legal,
+                        const uint32_t *seed32, const int32_t *tag, uint32_t salt, double alpha,
+                        float *out, uint32_t *out_bits, void *hip_stream);
 /* Host int64: the live rows of every evaluated batch of every search completed by rvz_act since
  * compaction was first enabled (0 if never enabled; a batch left by rvz_search_skip is not
  * counted); synchronises the engine stream. */
@@ -191,7 +230,7 @@ int rvz_act(rvz_engine *e, double temperature, const double *u, int32_t apply, i
  * search of num_simulations), with the per-ply bookkeeping of rvz_env_autoreset. The games, moves,
  * p and counters are bit-identical to the pull-style loop (rvz_search_step / the
  * rvz_resnet_fwd_h2 evaluator with logits / rvz_search_submit / rvz_act / rvz_env_autoreset) on
- * the same engine state; the engine's memo setting applies; compaction is inherent (only the live
+ * the same engine state; the engine's memo and root-noise settings apply; compaction is inherent (only the live
  * leaves are evaluated). Not inside a search; graph-capturable (no allocation, no sync). */
 typedef struct rvz_play_args {
     const float *params;         /* packed fp32 net (rvz_resnet_params_size layout) */
