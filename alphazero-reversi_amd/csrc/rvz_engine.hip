@@ -114,6 +114,11 @@ struct View {  // kernel argument: device pointers + sizes
     uint32_t noise_salt;
     uint32_t* seed32;  // [G]
     float* eta;        // [G][64] the current root's eta per square (written when the root is created)
+    // Temperature schedule of the act (rvz_act_schedule; sched_from = 0: off): a game whose
+    // position before the move has at least sched_from discs acts at sched_late instead of the
+    // call's temperature
+    int sched_from;
+    double sched_late;
 };
 
 // A link names an expanded node of the previous search's tree (the same position as the new
@@ -814,46 +819,27 @@ __device__ __forceinline__ double np_power(double x, double e) {
     return rvz_pow::pow_cr(x, e);
 }
 
-// act for one game (one wave): the search's pending expand (expand 1) or visit-count backup
-// (expand 2), then get_action_probs' tail and the move; returns the sampled index (-2: the game
-// was over). s: NPOL + 7 doubles of this wave's LDS.
-template <int BS>
-__device__ __forceinline__ int act_game(const View& v, int g, int lane, double* s, int expand,
-                                        const float* __restrict__ policy, int is_logits,
-                                        const float* __restrict__ value, double temperature,
-                                        const double* __restrict__ uo, int apply,
-                                        int32_t* __restrict__ out_idx, double* __restrict__ out_p,
-                                        bool* over_after = nullptr) {
+// get_action_probs' tail (mcts.py:656-692) for one row of visit counts, one wave: n = the count of
+// square `lane` (lanes >= NSQ: ignored), npass the pass index's count (total below 2^31).
+// Normalise, p ** (1 / temperature) renormalised in numpy's pairwise order, then the first maximum
+// (temperature 0 or an all-zero row) or np.random.choice's cdf / searchsorted with one uniform
+// value. draw() is called (by every lane, wave-uniformly) only when the row needs that value, so
+// a row acting at temperature 0 reads and consumes none. s: NPOL doubles of this wave's LDS.
+// Returns idx (wave-uniform); p (lane's square) and ppass are the row of get_action_probs.
+// act_game (k_act, k_play) and k_action_probs (rvz_action_probs) both select through it.
+template <int BS, class Draw>
+__device__ __forceinline__ int select_action(int n, int npass, int lane, double* s,
+                                             double temperature, Draw&& draw, double& p,
+                                             double& ppass, int& drew) {
     constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
     constexpr int NMAIN = NPOL - NPOL % 8;
-    unsigned long long ab = 0;
-    if (expand == 1) {
-        const ExpIn x = expand_load<BS>(v, g, lane, policy, value);
-        expand_backup_phase<BS>(v, g, lane, x, is_logits, nullptr, ab);
-    } else if (expand == 2) {
-        backup_visits_only(v, g, lane, ab);
-    }
-    GameS gm = load_game(v, g);
-    double* prow = out_p + (size_t)g * NPOL;
-    if (gm.over) {
-        if (lane < NSQ) prow[lane] = 0.0;
-        if (lane == 0) {
-            prow[NSQ] = 0.0;
-            out_idx[g] = -2;
-            if (v.memo) v.carry[g] = LINK_NONE;
-            if (v.stats) v.stats[(size_t)v.G + g] += ab + 32 + 8ull * NPOL + 4;
-        }
-        if (over_after) *over_after = true;
-        return -2;
-    }
-    const int n = root_visits<BS>(v, g, lane);
-    const int total = wave_sum_i(n);
-    double p = (lane < NSQ && total > 0) ? (double)n / (double)total : 0.0;
-    double ppass = 0.0;
-    if (temperature > 0.0 && __any(p != 0.0)) {
+    const int total = wave_sum_i(lane < NSQ ? n : 0) + npass;
+    p = (lane < NSQ && total > 0) ? (double)n / (double)total : 0.0;
+    ppass = npass != 0 ? (double)npass / (double)total : 0.0;
+    if (temperature > 0.0 && (__any(p != 0.0) || ppass != 0.0)) {
         const double ex = 1.0 / temperature;
         const double t = lane < NSQ ? np_power(p, ex) : 0.0;
-        const double tp = np_power(0.0, ex);
+        const double tp = np_power(ppass, ex);
         // np.sum in numpy's pairwise order: 8 accumulators over the first NMAIN entries, then tail
         if (lane < NSQ) s[lane] = t;
         if (lane == 0) s[NSQ] = tp;
@@ -878,6 +864,7 @@ __device__ __forceinline__ int act_game(const View& v, int g, int lane, double* 
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __builtin_amdgcn_wave_barrier();
     int idx = 0;
+    drew = 0;
     if (temperature == 0.0 || all_zero) {  // np.argmax: first maximum
         if (lane == 0) {
             double best = s[0];
@@ -885,19 +872,8 @@ __device__ __forceinline__ int act_game(const View& v, int g, int lane, double* 
                 if (s[i] > best) { best = s[i]; idx = i; }
         }
     } else {  // np.random.choice(NPOL, p=p): cumsum, /= last, searchsorted(u, 'right')
-        double u;
-        if (uo) {
-            u = uo[g];
-        } else {
-            const int pos = v.rng_pos[g];
-            if (pos >= RNG_DRAWS) {
-                if (lane == 0) atomicOr(v.err, ERR_RNG);
-                u = 0.0;
-            } else {
-                u = v.rng_u[(size_t)g * RNG_DRAWS + pos];
-            }
-            if (lane == 0) v.rng_pos[g] = pos + 1;
-        }
+        const double u = draw();
+        drew = 1;
         if (lane == 0) {
             double acc = 0.0;  // cdf[-1]: the same sequential adds as p.cumsum()
             for (int i = 0; i < NPOL; ++i) acc += s[i];
@@ -909,7 +885,59 @@ __device__ __forceinline__ int act_game(const View& v, int g, int lane, double* 
             }
         }
     }
-    idx = __shfl(idx, 0);
+    return __shfl(idx, 0);
+}
+
+// act for one game (one wave): the search's pending expand (expand 1) or visit-count backup
+// (expand 2), then get_action_probs' tail and the move; returns the sampled index (-2: the game
+// was over). s: NPOL + 7 doubles of this wave's LDS.
+template <int BS>
+__device__ __forceinline__ int act_game(const View& v, int g, int lane, double* s, int expand,
+                                        const float* __restrict__ policy, int is_logits,
+                                        const float* __restrict__ value, double temperature,
+                                        const double* __restrict__ uo, int apply,
+                                        int32_t* __restrict__ out_idx, double* __restrict__ out_p,
+                                        bool* over_after = nullptr) {
+    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    unsigned long long ab = 0;
+    if (expand == 1) {
+        const ExpIn x = expand_load<BS>(v, g, lane, policy, value);
+        expand_backup_phase<BS>(v, g, lane, x, is_logits, nullptr, ab);
+    } else if (expand == 2) {
+        backup_visits_only(v, g, lane, ab);
+    }
+    GameS gm = load_game(v, g);
+    double* prow = out_p + (size_t)g * NPOL;
+    if (gm.over) {
+        if (lane < NSQ) prow[lane] = 0.0;
+        if (lane == 0) {
+            prow[NSQ] = 0.0;
+            out_idx[g] = -2;
+            if (v.memo) v.carry[g] = LINK_NONE;
+            if (v.stats) v.stats[(size_t)v.G + g] += ab + 32 + 8ull * NPOL + 4;
+        }
+        if (over_after) *over_after = true;
+        return -2;
+    }
+    // the schedule, keyed by the root's disc count: wave-uniform (one wave, one game), and
+    // nothing of it runs with the schedule off
+    if (v.sched_from > 0 && __popcll(gm.black | gm.white) >= v.sched_from)
+        temperature = v.sched_late;
+    const int n = root_visits<BS>(v, g, lane);
+    double p, ppass;
+    int drew;
+    const int idx = select_action<BS>(n, 0, lane, s, temperature, [&]() -> double {
+        if (uo) return uo[g];
+        const int pos = v.rng_pos[g];
+        double u = 0.0;
+        if (pos >= RNG_DRAWS) {
+            if (lane == 0) atomicOr(v.err, ERR_RNG);
+        } else {
+            u = v.rng_u[(size_t)g * RNG_DRAWS + pos];
+        }
+        if (lane == 0) v.rng_pos[g] = pos + 1;
+        return u;
+    }, p, ppass, drew);
     if (lane < NSQ) prow[lane] = p;
     if (lane == 0) {
         prow[NSQ] = ppass;
@@ -969,6 +997,37 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BS == 8 ? R
     }
     act_game<BS>(v, g, lane, sp[wid], expand, policy, is_logits, value, temperature, uo, apply,
                  out_idx, out_p);
+}
+
+// rvz_action_probs: select_action on caller arrays, one wave per row. A row holding a negative
+// count writes out_idx = -3 and a zero row (drew 0).
+template <int BS>
+__global__ __launch_bounds__(256) void k_action_probs(int n_rows, const int32_t* __restrict__ visits,
+                                                      const double* __restrict__ temperature,
+                                                      const double* __restrict__ u,
+                                                      int32_t* __restrict__ out_idx,
+                                                      double* __restrict__ out_p,
+                                                      int32_t* __restrict__ out_drew) {
+    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    __shared__ double sp[WPB][NPOL + 7];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int r = blockIdx.x * WPB + wid;
+    if (r >= n_rows) return;
+    const int32_t* vrow = visits + (size_t)r * NPOL;
+    double* prow = out_p + (size_t)r * NPOL;
+    const int n = lane < NSQ ? vrow[lane] : 0;
+    const int npass = vrow[NSQ];
+    double p = 0.0, ppass = 0.0;
+    int idx = -3, drew = 0;
+    if (!__any(n < 0) && npass >= 0)
+        idx = select_action<BS>(n, npass, lane, sp[wid], temperature[r],
+                                [&]() -> double { return u[r]; }, p, ppass, drew);
+    if (lane < NSQ) prow[lane] = p;
+    if (lane == 0) {
+        prow[NSQ] = ppass;
+        out_idx[r] = idx;
+        if (out_drew) out_drew[r] = drew;
+    }
 }
 
 // reset: new game (board.py:25-39) + np.random.seed(seed) random_sample() stream.
@@ -1310,6 +1369,8 @@ int rvz_create(const rvz_config* cfg, rvz_engine** out) {
     v.noise_om = 1.0f;
     v.noise_alpha = 1.0f;
     v.noise_salt = 0u;
+    v.sched_from = 0;
+    v.sched_late = 0.0;
     v.seed32 = dalloc<uint32_t>(e, G);
     v.eta = dalloc<float>(e, (size_t)G * WAVE);
     e->stats_buf = dalloc<unsigned long long>(e, 3 * (size_t)G);
@@ -1708,6 +1769,34 @@ int rvz_dirichlet_noise(int32_t bs, int32_t n, const uint64_t* legal, const uint
     dim3 grid((n + WPB - 1) / WPB), block(WPB * WAVE);
     if (bs == 8) hipLaunchKernelGGL(k_dirichlet<8>, grid, block, 0, (hipStream_t)stream, n, legal, seed32, tag, salt, (float)alpha, out, out_bits);
     else hipLaunchKernelGGL(k_dirichlet<6>, grid, block, 0, (hipStream_t)stream, n, legal, seed32, tag, salt, (float)alpha, out, out_bits);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}
+
+int rvz_act_schedule(rvz_engine* e, int32_t from_discs, double late_temperature) {
+    if (!e) return RVZ_EINVAL;
+    if (from_discs > 0 && !(late_temperature >= 0.0 && late_temperature <= 1.7976931348623157e308)) {
+        e->err = "rvz_act_schedule: late_temperature must be finite and >= 0";
+        return RVZ_EINVAL;
+    }
+    if (e->pending || (e->searching && e->next_batch > 0)) {
+        e->err = "rvz_act_schedule inside a search";
+        return RVZ_EINVAL;
+    }
+    e->v.sched_from = from_discs > 0 ? from_discs : 0;
+    e->v.sched_late = from_discs > 0 ? late_temperature : 0.0;
+    return RVZ_OK;
+}
+
+int rvz_action_probs(int32_t bs, int32_t n, const int32_t* visits, const double* temperature,
+                     const double* u, int32_t* out_idx, double* out_p, int32_t* out_drew,
+                     void* stream) {
+    if ((bs != 8 && bs != 6) || n < 0 ||
+        (n > 0 && (!visits || !temperature || !u || !out_idx || !out_p)))
+        return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    dim3 grid((n + WPB - 1) / WPB), block(WPB * WAVE);
+    if (bs == 8) hipLaunchKernelGGL(k_action_probs<8>, grid, block, 0, (hipStream_t)stream, n, visits, temperature, u, out_idx, out_p, out_drew);
+    else hipLaunchKernelGGL(k_action_probs<6>, grid, block, 0, (hipStream_t)stream, n, visits, temperature, u, out_idx, out_p, out_drew);
     return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }
 

@@ -10,6 +10,8 @@ carry the soname libamdhip64.so.7): torch streams and tensors are then valid in 
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
 import os
 
 import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
@@ -79,6 +81,8 @@ SIGNATURES = {
     "rvz_search_skip": (C.c_int, [_P]),
     "rvz_search_visits": (C.c_int, [_P, _P]),
     "rvz_act": (C.c_int, [_P, C.c_double, _P, C.c_int32, _P, _P]),
+    "rvz_act_schedule": (C.c_int, [_P, C.c_int32, C.c_double]),
+    "rvz_action_probs": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),
@@ -156,6 +160,28 @@ def check_noise_args(alpha, epsilon=_NO_EPSILON) -> None:
             raise RvzError(f"root noise: epsilon must be a number in [0, 1], not {epsilon!r}")
         if not 0.0 <= e <= 1.0:
             raise RvzError(f"root noise: epsilon must be in [0, 1], not {epsilon!r}")
+
+
+def check_schedule_args(moves, late_temperature=0.0):
+    """The argument rules of rvz_act_schedule (Engine.temperature_schedule), checked on the host
+    before any device call: moves None (the schedule is off) or an int >= 0 (the moves of a game
+    sampled at the call's temperature), late_temperature a finite number >= 0. Returns None (off)
+    or (moves, late_temperature)."""
+    if moves is None:
+        return None
+    if isinstance(moves, bool) or not isinstance(moves, numbers.Integral) or moves < 0:
+        raise RvzError(f"temperature schedule: moves must be None or an int >= 0, not {moves!r}")
+    if int(moves) > 2 ** 31 - 5:
+        raise RvzError(f"temperature schedule: moves = {moves!r} is out of range")
+    try:
+        late = float(late_temperature)
+    except (TypeError, ValueError, OverflowError):
+        raise RvzError("temperature schedule: late_temperature must be a finite number >= 0, "
+                       f"not {late_temperature!r}")
+    if isinstance(late_temperature, bool) or not (0.0 <= late < math.inf):
+        raise RvzError("temperature schedule: late_temperature must be a finite number >= 0, "
+                       f"not {late_temperature!r}")
+    return int(moves), late
 
 
 def check(rc: int, handle=None, what: str = "") -> int:

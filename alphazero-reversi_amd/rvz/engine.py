@@ -350,6 +350,21 @@ class Engine:
         self._call("rvz_search_root_noise", float(alpha), float(epsilon), int(salt) & 0xFFFFFFFF)
         self.noise = (float(alpha), float(epsilon), int(salt) & 0xFFFFFFFF)
 
+    def temperature_schedule(self, moves: Optional[int], late_temperature: float = 0.0):
+        """rvz_act_schedule: a game's first `moves` moves are chosen at the temperature of the
+        call (act() / play()), every later one at late_temperature (0: the most visited move, no
+        draw). moves=None turns it off (the default: one temperature for every ply). Keyed by the
+        disc count of the position before the move (from_discs = 4 + moves: every committed ply
+        places a disc), so games at different move numbers share a launch and pull-style and
+        fused play agree. Not inside a search; set it before capturing a graph (a captured
+        launch keeps the setting of its capture)."""
+        sched = _lib.check_schedule_args(moves, late_temperature)
+        if sched is None:
+            self._call("rvz_act_schedule", 0, 0.0)
+        else:
+            self._call("rvz_act_schedule", 4 + sched[0], sched[1])
+        self.schedule = sched
+
     # ------------------------------------------------------------------ search
     def search_begin(self):
         self._call("rvz_search_begin")
@@ -522,6 +537,38 @@ def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor
                                       ptr(ob) if bits else None, _lib.stream_handle(dev)),
               None, "rvz_dirichlet_noise")
     return (out, ob) if bits else out
+
+
+def action_probs(visits: torch.Tensor, temperature, u: Optional[torch.Tensor] = None,
+                 board_size: int = 8):
+    """rvz_action_probs: get_action_probs' tail (mcts.py:656-692) for n rows of visit counts, by
+    the device function Engine.act and Engine.play select with. visits int32 [n, S*S+1] on the
+    device (e.g. Engine.visits()), temperature a number or one per row, u float64 [n] (the values
+    np.random.random_sample() would return; None: zeros). Returns (idx int32 [n], p float64
+    [n, S*S+1], drew int32 [n]: 1 where the row consumed its u), device tensors. A row with a
+    negative count gets idx -3 and a zero p row."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    npol = board_size * board_size + 1
+    if visits.dim() != 2 or visits.shape[1] != npol:
+        raise RvzError(f"visits must be [n, {npol}]")
+    lib = _lib.load()
+    dev = visits.device
+    vis = visits.to(torch.int32).contiguous()
+    n = vis.shape[0]
+    t = torch.as_tensor(temperature, dtype=torch.float64).to(dev)
+    t = t.expand(n).contiguous() if t.dim() == 0 else t.contiguous()
+    uu = (torch.zeros(n, dtype=torch.float64, device=dev) if u is None
+          else u.to(dev, torch.float64).contiguous())
+    if t.shape != (n,) or uu.shape != (n,):
+        raise RvzError("action_probs: temperature (unless a scalar) and u hold one entry per row")
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    p = torch.empty(n, npol, dtype=torch.float64, device=dev)
+    drew = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        check(lib.rvz_action_probs(board_size, n, ptr(vis), ptr(t), ptr(uu), ptr(idx), ptr(p),
+                                   ptr(drew), _lib.stream_handle(dev)), None, "rvz_action_probs")
+    return idx, p, drew
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

@@ -38,9 +38,12 @@ class SelfPlayTrainer:
                  graph: bool = True, compact_leaves: bool = True, lr_milestones=(),
                  lr_gamma: float = 0.1, memo: bool = True, fused: bool = True,
                  table_slots: Optional[int] = None, table_discs: int = 14,
-                 root_noise=None):
+                 root_noise=None, temperature_schedule=None):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
+        temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
+        at `temperature`, the later ones at `late` (Engine.temperature_schedule), set before any
+        graph is captured.
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
@@ -65,6 +68,8 @@ class SelfPlayTrainer:
                           device=self.device, compact_leaves=compact_leaves, memo=memo)
         if root_noise is not None:
             self.eng.root_noise(*root_noise)
+        if temperature_schedule is not None:
+            self.eng.temperature_schedule(*temperature_schedule)
         self.max_plies = bs * bs - 4
         # fused: every game of the iteration in ONE rvz_play launch with device records, the
         # memo's deferred last batch and the cross-game table (a new generation per refresh());

@@ -29,8 +29,13 @@ class SelfPlayRunner:
                  fused_softmax: bool = True, autoreset: bool = False, seed_base: int = 42,
                  record: bool = False, max_plies: int = 60, seed_stride: int = None,
                  skip_last_eval: bool = False, fused_bookkeeping: bool = True,
-                 fused: bool = False):
+                 fused: bool = False, temperature_schedule=None):
         self.eng = engine
+        # temperature_schedule: None (the engine's setting stays as it is) or (moves, late): a
+        # game's first `moves` moves at `temperature`, the later ones at `late`
+        # (Engine.temperature_schedule); set here, before any capture
+        if temperature_schedule is not None:
+            engine.temperature_schedule(*temperature_schedule)
         self.skip_last_eval = bool(skip_last_eval)
         # fused: each ply() is ONE rvz_play launch (Engine.play: search + the h2 evaluator +
         # act + autoreset per workgroup) instead of the per-batch launches; same games
@@ -203,7 +208,8 @@ class LaneRunner:
     def __init__(self, make_engine: Callable[[int], Engine], make_evaluator: Callable,
                  n_games: int, lanes: int = 2, temperature: float = 1.0,
                  fused_softmax: bool = True, autoreset: bool = False, seed_base: int = 42,
-                 seed_stride: int = None, skip_last_eval: bool = False, fused: bool = False):
+                 seed_stride: int = None, skip_last_eval: bool = False, fused: bool = False,
+                 temperature_schedule=None):
         if lanes < 1 or n_games < lanes:
             raise ValueError("need 1 <= lanes <= n_games")
         sizes = [n_games // lanes + (1 if k < n_games % lanes else 0) for k in range(lanes)]
@@ -212,7 +218,7 @@ class LaneRunner:
         self.runners = [SelfPlayRunner(make_engine(gl), make_evaluator(), temperature,
                                        fused_softmax, autoreset, seed_base + o,
                                        seed_stride=stride, skip_last_eval=skip_last_eval,
-                                       fused=fused)
+                                       fused=fused, temperature_schedule=temperature_schedule)
                         for gl, o in zip(sizes, offsets)]
         dev = self.runners[0].eng.device
         self.streams = [torch.cuda.Stream(dev) for _ in range(lanes)]
@@ -330,6 +336,14 @@ class SelfPlay:
     reference ignores them, so honouring them would silently end drop-in parity. The noise is
     keyed by each game's seed (seed_base + game index, whichever randomness mode hands out the
     move-sampling draws) and draws nothing from np.random.
+
+    args["temperature_moves"] (default None: off) and args["temperature_late"] (default 0.0): a
+    game's first temperature_moves moves are chosen at args["temperature"], every later one at
+    temperature_late (Engine.temperature_schedule). A move chosen at temperature 0 draws no value,
+    here as in the reference (mcts.py:679-681), so with temperature_late = 0 a game takes one
+    value per move for its first temperature_moves moves only, and the global-stream order above
+    holds with those counts: the first pass assumes min(bs*bs - 4, temperature_moves) values per
+    earlier game, which is exact unless a game ends within its sampled moves.
     """
 
     def __init__(self, model, args: dict, evaluator: Optional[Callable] = None):
@@ -357,6 +371,7 @@ class SelfPlay:
         os.makedirs(self.save_dir, exist_ok=True)
         self.seed = None if args.get("seed") is None else int(args["seed"])
         self.root_noise = root_noise_args(args)
+        self.schedule = temperature_schedule_args(args)
         self.fused = bool(args.get("fused", isinstance(self.evaluator, LeafEvaluator)))
         if self.fused and not isinstance(self.evaluator, LeafEvaluator):
             raise ValueError("SelfPlay: args['fused'] plays the h2 LeafEvaluator inside the "
@@ -386,6 +401,8 @@ class SelfPlay:
                                              and self.args.get("fused_softmax", True))))
         if self.root_noise is not None:
             eng.root_noise(*self.root_noise)
+        if self.schedule is not None:
+            eng.temperature_schedule(*self.schedule)
         if hasattr(self.evaluator, "bind"):
             self.evaluator.bind(eng)
         max_plies = bs * bs - 4         # every ply places a disc (passes are inside make_move)
@@ -416,13 +433,15 @@ class SelfPlay:
         every pass, game -> (pass, column))."""
         from ._lib import RVZ_DRAWS
         T = float(self.args.get("temperature", 1.0))
+        max_draws = self.board_size ** 2 - 4
+        draws_on, guess = schedule_draws(T, self.schedule, max_draws)
         # the games' seeds (the key of the root noise; the move-sampling draws come from `U`):
         # games_played + the game's index in this call, the same in every pass
         passes, where, _ = sequential_draw_passes(
-            num_games, self.board_size ** 2 - 4, RVZ_DRAWS, T > 0, np.random,
+            num_games, max_draws, RVZ_DRAWS, draws_on, np.random,
             (lambda U, todo: self._run(len(U), self.games_played, draws=U, game_ids=todo))
             if self.root_noise is not None else (lambda U, todo: self._run(len(U), 0, draws=U)),
-            with_games=True)
+            with_games=True, first_guess=guess)
         self.reference_order_passes = len(passes)
         return passes, where
 
@@ -507,8 +526,35 @@ def root_noise_args(args: dict):
     return float(alpha), float(eps), int(args.get("dirichlet_salt", 0)) & 0xFFFFFFFF
 
 
+def temperature_schedule_args(args: dict):
+    """SelfPlay's temperature schedule from its args: None unless args["temperature_moves"] is
+    given, else (moves, late) from temperature_moves and temperature_late (0.0), validated here,
+    before any device call."""
+    from ._lib import check_schedule_args
+    return check_schedule_args(args.get("temperature_moves"), args.get("temperature_late", 0.0))
+
+
+def schedule_draws(temperature: float, schedule, max_draws: int):
+    """What a game draws under a temperature schedule (None: off): (whether any move can draw,
+    the first-guess draw count per game for sequential_draw_passes or None for its default). A
+    move draws one value unless it is chosen at temperature 0 (mcts.py:679-681): the first
+    `moves` moves draw when temperature != 0, the later ones when late != 0."""
+    if schedule is None:
+        return temperature > 0, None
+    moves, late = schedule
+    early, later = temperature > 0, late > 0
+    if early and later:
+        return True, None
+    if early:
+        return True, min(max_draws, moves)
+    if later:
+        return True, max(0, max_draws - moves)
+    return False, None
+
+
 def sequential_draw_passes(num_games: int, max_draws: int, piece: int, draws_on: bool, rng,
-                           play: Callable, with_games: bool = False):
+                           play: Callable, with_games: bool = False,
+                           first_guess: Optional[int] = None):
     """Lockstep passes that give every game the piece of ONE random_sample() stream it would
     draw if the games ran one after another (SelfPlay's class docstring; self_play.py:66-101
     with mcts.py:684). rng: a NumPy RandomState or the np.random module (its state is read once
@@ -517,12 +563,18 @@ def sequential_draw_passes(num_games: int, max_draws: int, piece: int, draws_on:
     mcts.py:679-681). play(U float64 [k, piece]) plays k fresh games, game j drawing U[j, 0],
     U[j, 1], ... in order, and returns (payload, used int [k]: the values each game drew).
     with_games: play is called as play(U, games), games being the indices of the k games.
+    first_guess: the draw count assumed for every game in the first pass (default: max_draws,
+    the longest game); any value in [0, max_draws] gives the same result, a good one fewer passes.
     Returns (payloads of every pass, game -> (pass, index in that pass), draws per game)."""
     G = int(num_games)
     rs = np.random.RandomState()
     rs.set_state(rng.get_state())
     stream = rs.random_sample(G * max_draws + piece)
-    n = np.full(G, max_draws if draws_on else 0, np.int64)   # first guess: the longest game
+    if first_guess is not None and not 0 <= int(first_guess) <= max_draws:
+        raise ValueError(f"first_guess must be in [0, {max_draws}]")
+    # first guess: the longest game, unless the caller knows better
+    n = np.full(G, (max_draws if first_guess is None else int(first_guess)) if draws_on else 0,
+                np.int64)
     prev: List[Optional[int]] = [None] * G
     where: List = [None] * G
     payloads = []

@@ -221,6 +221,42 @@ int rvz_search_visits(rvz_engine *e, int32_t *out);
  * the move on the engine's env (ReversiGame.make_move semantics). */
 int rvz_act(rvz_engine *e, double temperature, const double *u, int32_t apply, int32_t *out_idx,
             double *out_p);
+/* Move-number temperature schedule of the act (AlphaZero samples a game's first moves at tau = 1
+ * and plays the rest (near-)greedily; the reference has one temperature for every ply,
+ * self_play.py:84). Off by default and whenever from_discs <= 0; with it off every game, counter
+ * and output byte is what it is without this call. With it on, a game whose position before the
+ * move (the search root) holds at least from_discs discs acts with late_temperature in place of
+ * the temperature of the call (rvz_act's argument, rvz_play_args.temperature); a game with fewer
+ * discs acts with the call's. Nothing else of get_action_probs' tail changes: the power's fast
+ * paths and the correctly rounded power, the pairwise sum, the cdf and searchsorted, the first
+ * maximum at temperature 0 are the same code with the game's own temperature. A game acting at
+ * temperature 0 draws nothing: its rvz_env_draws count does not advance, and neither u[g] nor its
+ * draw buffer is read (the existing rule, per game).
+ * Every committed ply places one disc (a pass happens inside make_move), so a game from the start
+ * position holds 4 + k discs before its move k + 1: from_discs = 4 + N samples the first N moves
+ * at the call's temperature. The game's temperature is a pure function of its position: it does
+ * not depend on the launch geometry, pull-style or fused play, the memo / table / compaction /
+ * gate / root-noise settings, rvz_play's reset or ply_budget phase, or how the position came
+ * about (rvz_env_set included), so games at different move numbers share one launch.
+ * RVZ_EINVAL (rvz_last_error set): late_temperature negative or non-finite with from_discs > 0;
+ * inside a search. The setting travels in the kernel arguments: launches issued (or captured
+ * into a graph: rvz_act, rvz_play) before the call keep the setting they were issued with, so a
+ * captured graph replays with the schedule of its capture; set it before capturing. */
+int rvz_act_schedule(rvz_engine *e, int32_t from_discs, double late_temperature);
+/* Stateless, on caller arrays: get_action_probs' tail (mcts.py:656-692) for n independent rows of
+ * visit counts, one wave per row, by the SAME device function rvz_act and rvz_play select with.
+ * visits int32 [n][S*S+1] (index S*S: the pass; a row's sum must stay below 2^31), temperature
+ * float64 [n] (row r's own; 0: the first maximum), u float64 [n] (the value
+ * np.random.random_sample() would return; read only by a row that samples). out_idx int32 [n],
+ * out_p float64 [n][S*S+1], out_drew (nullable) int32 [n]: 1 if the row consumed u[r] (temperature
+ * != 0 and a nonzero row), else 0. For re-deriving move probabilities from exported visit counts
+ * (rvz_search_visits) at another temperature. Device pointers; asynchronous on hip_stream.
+ * RVZ_EINVAL: board size, n < 0, a null visits / temperature / u / out_idx / out_p with n > 0.
+ * The counts are checked in the kernel (no host synchronisation): a row holding a negative count
+ * gets out_idx = -3, a zero out_p row and out_drew 0. */
+int rvz_action_probs(int32_t board_size, int32_t n, const int32_t *visits,
+                     const double *temperature, const double *u, int32_t *out_idx, double *out_p,
+                     int32_t *out_drew, void *hip_stream);
 
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
