@@ -1,0 +1,242 @@
+// rvz_solve.hip — exact endgame solver: batched negamax over the reference's rules for gfx950
+// (MI355X), exported as rvz_solve (include/rvz.h). Its own translation unit: the code objects of
+// rvz_engine.hip (k_play, k_step, k_act) do not depend on it.
+//
+// Definition (DESIGN.md §Exact endgame solver): solve(g) = the disc difference at the end of the
+// game from g's side to move, both sides playing the maximum, the children made by make_move<BS>
+// (auto-pass included), moves in increasing square order, the first maximum kept.
+//
+// Shape: one position per LANE. A self-play iteration yields tens of thousands of small, unequal
+// trees with at most ~12 root moves each, so a wave per position would idle most lanes; here the
+// 64 lanes of a wave step one explicit-stack state machine in lockstep, each on its own position.
+// Lanes are persistent: a lane whose row is done takes the next row index from a device counter
+// in the same loop iteration, so a wave stays full until the batch drains; the grid is sized from
+// the CU count. Nothing a row computes depends on which lane, wave or launch it landed in.
+//
+// Per lane, in registers: the current node (mover's discs P, the other side's O, the moves not
+// yet tried, alpha / beta / best) and the row's bookkeeping. Per lane, in LDS: one frame per ply
+// above the current node, [depth][field][lane] in dwords, so a wave's access to one field of one
+// depth covers 64 consecutive banks. A frame is what the return needs: the moves left (2 dwords),
+// the flip mask of the move being searched (2 dwords: the undo), and {square, kept-side flag,
+// alpha, beta, best} packed in one dword: 20 bytes. No recursion and no run-time-indexed register
+// array: the kernel uses no scratch.
+//
+// Depth: every ply places a disc, and a frame is pushed only when the child has a move, i.e. at
+// least one empty square left, so a row with E empties pushes at most E - 1 frames;
+// FRAMES = RVZ_SOLVE_MAX_EMPTIES covers it with room, and the push checks it all the same.
+// LDS: 128 lanes x 14 frames x 20 B = 35,840 B per workgroup: four workgroups (8 waves, 2 per
+// SIMD) fit in a CU's 160 KiB.
+//
+// Pruning: fail-soft alpha-beta. A root's children are searched with the window (best, +inf)
+// in the root's terms: a child whose true value is above the root's best so far comes back
+// exact, any other comes back <= best and is dropped by the strict comparison, so the score and
+// the first-maximum move equal the unpruned definition (DESIGN.md has the argument). Node counts
+// depend on the row alone.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <atomic>
+
+#include "../../include/rvz.h"
+#include "rvz_rules.hip.h"
+
+using namespace rvz;
+
+namespace {
+
+constexpr int SOLVE_THREADS = 128;                 // 2 waves per workgroup
+constexpr int SOLVE_WG_PER_CU = 4;                 // 8 waves per CU by LDS
+constexpr int FRAMES = RVZ_SOLVE_MAX_EMPTIES;
+constexpr int FIELDS = 5;
+constexpr int SINF = 127;                          // |score| <= 64; fits the packed int8 fields
+constexpr int SLOTS = 32;                          // row counters: calls in flight at once
+static_assert(FRAMES * FIELDS * SOLVE_THREADS * 4 * SOLVE_WG_PER_CU <= 160 * 1024,
+              "2 waves per SIMD must fit in the CU's LDS");
+
+// the next row index of each call in flight; zeroed on the call's stream by k_solve_zero
+__device__ unsigned int g_next_row[SLOTS];
+
+__global__ void k_solve_zero(int slot) { g_next_row[slot] = 0u; }
+
+template <int BS>
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
+    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
+    const int32_t* __restrict__ status, int max_empties, long long node_limit,
+    int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
+    long long* __restrict__ out_nodes, int slot) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    constexpr uint64_t FULL = Geo<BS>::FULL;
+    __shared__ uint32_t stk[FRAMES * FIELDS * SOLVE_THREADS];
+    uint32_t* const my = stk + threadIdx.x;        // field f of depth d: my[(d * FIELDS + f) * T]
+
+    bool active = false, exhausted = false;
+    int row = 0, depth = 0, alpha = 0, beta = 0, best = 0, bestsq = 0, rootpass = 0;
+    uint64_t P = 0, O = 0, rem = 0;
+    long long nodes = 0;
+
+    auto emit = [&](int score, int move, long long cnt) {
+        out_score[row] = score;
+        out_move[row] = move;
+        if (out_nodes) out_nodes[row] = cnt;
+        active = false;
+    };
+
+    for (;;) {
+        // ---- an idle lane takes the next row and settles everything that needs no search
+        if (!active && !exhausted) {
+            const unsigned r = atomicAdd(&g_next_row[slot], 1u);
+            if (r >= (unsigned)n) {
+                exhausted = true;
+            } else {
+                row = (int)r;
+                const uint64_t b = black[row], w = white[row];
+                const int side = status[4 * row], over = status[4 * row + 1];
+                const int passed = status[4 * row + 3];
+                P = side == 1 ? b : w;
+                O = side == 1 ? w : b;
+                const int diff = __popcll(P) - __popcll(O);
+                if ((b & w) || ((b | w) & ~FULL) || (side != 1 && side != 2)) {
+                    emit(0, -5, 0);
+                } else if (over) {
+                    emit(diff, -2, 1);
+                } else if (__popcll(~(b | w) & FULL) > max_empties) {
+                    emit(0, -3, 0);
+                } else {
+                    uint64_t M = legal<BS>(P, O);
+                    rootpass = 0;
+                    nodes = 1;
+                    if (!M) {
+                        // the root's only move is the pass (make_move<BS>(g, -1)): the side
+                        // flips, passed + 1; two passes in a row end the game
+                        const uint64_t M2 = legal<BS>(O, P);
+                        if (node_limit < 2) {
+                            emit(0, -4, 1);
+                        } else if (passed + 1 >= 2) {
+                            emit(diff, NSQ, 2);
+                        } else if (!M2) {          // the child passes too: the grandchild is over
+                            if (node_limit < 3) emit(0, -4, 2);
+                            else emit(diff, NSQ, 3);
+                        } else {                   // search the child; the root's score is -its
+                            const uint64_t t = P; P = O; O = t;
+                            M = M2;
+                            rootpass = 1;
+                            nodes = 2;
+                        }
+                    }
+                    if (M) {
+                        active = true;
+                        rem = M;
+                        depth = 0;
+                        alpha = -SINF; beta = SINF; best = -SINF;
+                        bestsq = 0;
+                    }
+                }
+            }
+        }
+        if (__all(exhausted)) break;               // exhausted lanes are never active
+
+        // ---- a finished node returns to its parent (one level per iteration)
+        if (active && (rem == 0 || best >= beta)) {
+            if (depth == 0) {
+                emit(rootpass ? -best : best, rootpass ? NSQ : bestsq, nodes);
+            } else {
+                --depth;
+                const uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
+                rem = (uint64_t)fr[0] | ((uint64_t)fr[SOLVE_THREADS] << 32);
+                const uint64_t f = (uint64_t)fr[2 * SOLVE_THREADS] |
+                                   ((uint64_t)fr[3 * SOLVE_THREADS] << 32);
+                const uint32_t pk = fr[4 * SOLVE_THREADS];
+                const int sq = pk & 63, keep = (pk >> 6) & 1;
+                const int v = keep ? best : -best;
+                if (!keep) { const uint64_t t = P; P = O; O = t; }
+                P ^= (1ull << sq) | f;             // undo the move
+                O ^= f;
+                alpha = (int)(int8_t)(pk >> 8);
+                beta = (int)(int8_t)(pk >> 16);
+                best = (int)(int8_t)(pk >> 24);
+                if (v > best) {
+                    best = v;
+                    if (depth == 0) bestsq = sq;
+                }
+                if (best > alpha) alpha = best;
+            }
+        }
+
+        // ---- an open node tries its next move
+        if (active && rem != 0 && best < beta) {
+            const int sq = __builtin_ctzll(rem);
+            rem &= rem - 1;
+            if (nodes >= node_limit) {
+                emit(0, -4, nodes);
+            } else {
+                ++nodes;
+                const uint64_t f = flips<BS>(sq, P, O);
+                const uint64_t nP = P ^ ((1ull << sq) | f), nO = O ^ f;
+                const uint64_t Mo = legal<BS>(nO, nP);
+                uint64_t Mm = 0;
+                if (!Mo) Mm = legal<BS>(nP, nO);   // auto-pass: the mover keeps the side
+                if (!(Mo | Mm)) {                  // neither side can move: the game is over
+                    const int v = __popcll(nP) - __popcll(nO);
+                    if (v > best) {
+                        best = v;
+                        if (depth == 0) bestsq = sq;
+                    }
+                    if (best > alpha) alpha = best;
+                } else if (depth >= FRAMES) {      // unreachable (see the head of the file)
+                    emit(0, -4, nodes);
+                } else {
+                    const int keep = Mo ? 0 : 1;
+                    uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
+                    fr[0] = (uint32_t)rem;
+                    fr[SOLVE_THREADS] = (uint32_t)(rem >> 32);
+                    fr[2 * SOLVE_THREADS] = (uint32_t)f;
+                    fr[3 * SOLVE_THREADS] = (uint32_t)(f >> 32);
+                    fr[4 * SOLVE_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
+                                            ((uint32_t)(alpha & 0xFF) << 8) |
+                                            ((uint32_t)(beta & 0xFF) << 16) |
+                                            ((uint32_t)(best & 0xFF) << 24);
+                    ++depth;
+                    if (keep) {
+                        P = nP; O = nO; rem = Mm;
+                    } else {
+                        P = nO; O = nP; rem = Mo;
+                        const int a = alpha;
+                        alpha = -beta; beta = -a;
+                    }
+                    best = -SINF;
+                }
+            }
+        }
+    }
+}
+
+std::atomic<unsigned> g_slot{0};
+
+}  // namespace
+
+extern "C" int rvz_solve(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
+                         const int32_t* status, int32_t max_empties, int64_t node_limit,
+                         int32_t* out_score, int32_t* out_move, int64_t* out_nodes, void* stream) {
+    if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
+        node_limit <= 0 || (n > 0 && (!black || !white || !status || !out_score || !out_move)))
+        return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        return RVZ_EHIP;
+    const int slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
+    const int need = (n + SOLVE_THREADS - 1) / SOLVE_THREADS;
+    const int wgs = cus * SOLVE_WG_PER_CU;
+    dim3 grid(need < wgs ? need : wgs), block(SOLVE_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, slot);
+    if (bs == 8)
+        hipLaunchKernelGGL(k_solve<8>, grid, block, 0, s, n, black, white, status, max_empties,
+                           (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
+    else
+        hipLaunchKernelGGL(k_solve<6>, grid, block, 0, s, n, black, white, status, max_empties,
+                           (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}

@@ -9,10 +9,11 @@ Batched core:
     SelfPlayRunner          one ply per call, HIP-graph capturable
     LaneRunner              independent lanes of SelfPlayRunners, one stream each, one graph
     AlphaZeroNetwork, LeafEvaluator   the policy/value net at the evaluation boundary
+    solve                   exact endgame values of a batch of positions (rvz_solve)
 """
 from ._lib import RvzError, load  # noqa: F401
 from .engine import (Engine, action_probs, board_apply, board_canonical,  # noqa: F401
-                     board_legal, dirichlet_noise, policy_softmax)
+                     board_legal, dirichlet_noise, policy_softmax, solve)
 from .game import Board, ReversiGame  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401

@@ -22,6 +22,7 @@ LIB_PATH = os.environ.get("RVZ_LIB", os.path.join(_HERE, "librvz.so"))   # RVZ_L
 RVZ_OK, RVZ_DONE = 0, 1
 RVZ_LEAF_F32, RVZ_LEAF_BF16 = 0, 1
 RVZ_DRAWS = 64          # move-sampling draws held per game (rvz_env_set_draws)
+RVZ_SOLVE_MAX_EMPTIES = 14   # rvz_solve: the deepest root its per-lane stack holds
 
 
 class RvzError(RuntimeError):
@@ -83,6 +84,8 @@ SIGNATURES = {
     "rvz_act": (C.c_int, [_P, C.c_double, _P, C.c_int32, _P, _P]),
     "rvz_act_schedule": (C.c_int, [_P, C.c_int32, C.c_double]),
     "rvz_action_probs": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "rvz_solve": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P,
+                            _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),

@@ -22,6 +22,7 @@ from . import _lib
 from ._lib import RVZ_DONE, RVZ_LEAF_BF16, RVZ_LEAF_F32, RvzError, check, ptr
 
 U64 = 0xFFFFFFFFFFFFFFFF
+SOLVE_MAX_EMPTIES = _lib.RVZ_SOLVE_MAX_EMPTIES
 
 
 def to_signed64(x: int) -> int:
@@ -213,6 +214,17 @@ class Engine:
         st = status.to(self.device, torch.int32).contiguous()
         self._call("rvz_env_set", ptr(b), ptr(w), ptr(st))
         torch.cuda.current_stream(self.device).synchronize()  # b, w, st are temporaries
+
+    def solve(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24):
+        """rvz.solve on the engine's current env state (rvz_env_get into fresh tensors, then
+        rvz_solve): (score, move, nodes) per game. Reads only: the env, a running search and the
+        buffers get_state() returns are left as they are."""
+        self._stream()
+        b = torch.empty(self.n_games, dtype=torch.int64, device=self.device)
+        w = torch.empty_like(b)
+        st = torch.empty(self.n_games, 4, dtype=torch.int32, device=self.device)
+        self._call("rvz_env_get", ptr(b), ptr(w), ptr(st))
+        return solve(b, w, st, self.board_size, max_empties, node_limit)
 
     def legal(self) -> torch.Tensor:
         self._stream()
@@ -569,6 +581,35 @@ def action_probs(visits: torch.Tensor, temperature, u: Optional[torch.Tensor] = 
         check(lib.rvz_action_probs(board_size, n, ptr(vis), ptr(t), ptr(uu), ptr(idx), ptr(p),
                                    ptr(drew), _lib.stream_handle(dev)), None, "rvz_action_probs")
     return idx, p, drew
+
+
+def solve(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int = 8,
+          max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24):
+    """rvz_solve: the exact value of n positions under the engine's rules (exhaustive negamax
+    with alpha-beta pruning, one position per lane). black / white int64 [n] (bit patterns),
+    status int32 [n, 4] (side, over, winner, passed), device tensors. Returns (score int32 [n],
+    move int32 [n], nodes int64 [n]) on the inputs' device: score is the final disc difference
+    from the side to move; move is the lowest-index best square, S*S for a forced pass, -2 for a
+    root that is over (score valid), -3 above max_empties, -4 abandoned at node_limit visited
+    positions, -5 for a malformed row (score 0 for -3 / -4 / -5); nodes counts the positions
+    visited."""
+    lib = _lib.load()
+    n = black.numel()
+    if status.shape != (n, 4) or white.numel() != n:
+        raise RvzError("solve: black and white hold one entry per row, status is [n, 4]")
+    dev = black.device
+    b = black.to(torch.int64).contiguous()
+    w = white.to(dev, torch.int64).contiguous()
+    st = status.to(dev, torch.int32).contiguous()
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    move = torch.empty(n, dtype=torch.int32, device=dev)
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    check(lib.rvz_solve(int(board_size), n, ptr(b) if n else None, ptr(w) if n else None,
+                        ptr(st) if n else None, int(max_empties), int(node_limit),
+                        ptr(score) if n else None, ptr(move) if n else None,
+                        ptr(nodes) if n else None, _lib.stream_handle(dev) if n else None),
+          None, "rvz_solve")
+    return score, move, nodes
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

@@ -38,12 +38,17 @@ class SelfPlayTrainer:
                  graph: bool = True, compact_leaves: bool = True, lr_milestones=(),
                  lr_gamma: float = 0.1, memo: bool = True, fused: bool = True,
                  table_slots: Optional[int] = None, table_discs: int = 14,
-                 root_noise=None, temperature_schedule=None):
+                 root_noise=None, temperature_schedule=None, exact_endgame: int = 0,
+                 exact_node_limit: int = 2 ** 24):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
         at `temperature`, the later ones at `late` (Engine.temperature_schedule), set before any
         graph is captured.
+        exact_endgame: 0 (off) or N: the value targets of the records with at most N empty squares
+        come from the exact endgame solver (records_to_training; rvz_solve abandoning a row after
+        exact_node_limit positions), not from the outcome of the game as played. Self-play itself
+        is unchanged.
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
@@ -54,6 +59,7 @@ class SelfPlayTrainer:
         self.rank, self.world = ((dist.get_rank(), dist.get_world_size()) if self.distributed
                                  else (0, 1))
         self.games, self.seed = int(games), int(seed)
+        self.exact_endgame, self.exact_node_limit = int(exact_endgame), int(exact_node_limit)
         self.train_steps = train_steps
         self.trainer = DDPTrainer(model, lr=lr, weight_decay=weight_decay,
                                   gradient_clip=gradient_clip, batch_size=train_batch,
@@ -108,7 +114,9 @@ class SelfPlayTrainer:
         if not bool(run.post_status[:, 1].all()):
             raise RuntimeError(f"a game is not over after {self.max_plies} plies")
         return records_to_training(run.rec_black, run.rec_white, run.rec_side, run.rec_idx,
-                                   run.rec_p, run.post_status, self.eng.board_size)
+                                   run.rec_p, run.post_status, self.eng.board_size,
+                                   exact_endgame=self.exact_endgame,
+                                   exact_node_limit=self.exact_node_limit)
 
     def train(self, data: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """_train_epoch over this iteration's data (each rank walks its own games; DDP averages
@@ -136,5 +144,7 @@ class SelfPlayTrainer:
         t2 = time.perf_counter()
         self.iteration += 1
         out.update({"selfplay_s": t1 - t0, "train_s": t2 - t1, "board_steps": plies,
-                    "samples": int(data["states"].shape[0])})
+                    "samples": int(data["states"].shape[0]),
+                    "exact_rows": int(data.get("exact_rows", 0)),
+                    "exact_unsolved": int(data.get("exact_unsolved", 0))})
         return out

@@ -22,12 +22,13 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .engine import board_canonical
+from .engine import board_canonical, solve
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
                         rec_idx: torch.Tensor, rec_p: torch.Tensor, final_status: torch.Tensor,
-                        board_size: int = 8, canonical=None) -> Dict[str, torch.Tensor]:
+                        board_size: int = 8, canonical=None, exact_endgame: int = 0,
+                        solver=None, exact_node_limit: int = 2 ** 24) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -36,6 +37,14 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     (pipeline.py:179-246). Only plies that committed a move (rec_idx >= 0) are kept.
     canonical(black, white, status, board_size) -> planes: default the rvz_board_canonical HIP
     kernel (tests on a host without a GPU pass the oracle's restatement).
+    exact_endgame = N > 0: every kept record whose position has at most N empty squares gets the
+    exact value target sign(score) of the endgame solver (+1 / 0 / -1 relative to the player to
+    move) in place of the played game's outcome; states and policy targets are untouched. A row
+    the solver abandons at its node limit (move -4) keeps its outcome target. Two more keys then,
+    0-d int64 tensors (no host synchronisation): "exact_rows", the rows replaced, and
+    "exact_unsolved", the rows abandoned. N = 0 (the default) is off: the outputs of before.
+    solver(black, white, status, board_size, max_empties) -> (score, move, ...): default rvz.solve
+    (the rvz_solve HIP kernel) with node_limit = exact_node_limit.
     """
     if canonical is None:
         canonical = board_canonical
@@ -53,7 +62,18 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     v = torch.where(winner == side.to(torch.int32), 1.0, -1.0)
     v = torch.where(winner == 0, torch.zeros_like(v), v)
     v = torch.where(over != 0, v, -torch.ones_like(v))      # winner None -> -1 (self_play.py:121-126)
-    return {"states": states, "policy_targets": policy, "value_targets": v.reshape(-1, 1).float()}
+    out = {"states": states, "policy_targets": policy, "value_targets": v.reshape(-1, 1).float()}
+    if exact_endgame:
+        if solver is None:
+            def solver(b, w, s, bs, me):
+                return solve(b, w, s, bs, me, exact_node_limit)
+        score, move = solver(black, white, st, board_size, int(exact_endgame))[:2]
+        solved = move >= 0                                   # -3: above N; -4: abandoned
+        exact = torch.sign(score).to(torch.float32).reshape(-1, 1)
+        out["value_targets"] = torch.where(solved.reshape(-1, 1), exact, out["value_targets"])
+        out["exact_rows"] = solved.sum()
+        out["exact_unsolved"] = (move == -4).sum()
+    return out
 
 
 class DDPTrainer:

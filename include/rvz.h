@@ -258,6 +258,43 @@ int rvz_action_probs(int32_t board_size, int32_t n, const int32_t *visits,
                      const double *temperature, const double *u, int32_t *out_idx, double *out_p,
                      int32_t *out_drew, void *hip_stream);
 
+/* ---- exact endgame solver ----------------------------------------------------------------
+ * Stateless, on caller arrays: the game-theoretic value of n independent positions under the
+ * rules the engine plays by (Board.get_valid_moves board.py:70-133 without file masks, the flip
+ * walk board.py:196-219, ReversiGame.make_move game.py:36-70 -> board.py:135-251 with its
+ * auto-pass and game end, the winner counting discs only, board.py:363-373), by exhaustive
+ * negamax with alpha-beta pruning, one position per lane (csrc/rvz_solve.hip):
+ *   solve(g) = discs(g.side) - discs(other side) if g is over, else the maximum over g's moves
+ *   (the squares of its legal mask in increasing index, or the pass alone when it has none) of
+ *   the child made by make_move: solve(child) if the child kept the side (auto-pass), else
+ *   -solve(child).
+ * black / white uint64 [n], status int32 [n][4] (side, over, winner, passed: rvz_env_get's
+ * layout; `passed` counts, a root with passed = 1 and no move ends the game by passing; `winner`
+ * is not read). out_score int32 [n]: solve(row), the final disc difference from the row's side to
+ * move (no bonus for empty squares). out_move int32 [n]: the lowest square index among the root
+ * moves that reach out_score; S*S when the root's only move is the pass; or, with out_score 0
+ * unless noted:
+ *   -2  the root is already over (out_score is its disc difference);
+ *   -3  more than max_empties empty squares: not searched;
+ *   -4  abandoned: the search would have visited more than node_limit positions;
+ *   -5  malformed row (black & white overlap, bits at or above S*S, side not 1 | 2), checked in
+ *       the kernel (no host synchronisation): not searched.
+ * out_nodes (nullable) int64 [n]: the positions visited for the row, the root included (0 for -3
+ * and -5, node_limit for -4). Score and move equal the unpruned definition exactly; a row's node
+ * count depends on that row and the build alone, not on n, the row's index or its neighbours.
+ * max_empties in [0, RVZ_SOLVE_MAX_EMPTIES] (the depth the per-lane LDS stack holds);
+ * node_limit > 0 bounds every row's work (there is no unbounded form). Device pointers;
+ * asynchronous on hip_stream; graph-capturable (no allocation, no synchronisation). At most 32
+ * calls may be executing at once on one device (each takes one of 32 row counters in turn; a
+ * captured call keeps the one of its capture).
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, max_empties out of range,
+ * node_limit <= 0, a null black / white / status / out_score / out_move with n > 0. n = 0
+ * returns RVZ_OK without a launch. */
+#define RVZ_SOLVE_MAX_EMPTIES 14
+int rvz_solve(int32_t board_size, int32_t n, const uint64_t *black, const uint64_t *white,
+              const int32_t *status, int32_t max_empties, int64_t node_limit, int32_t *out_score,
+              int32_t *out_move, int64_t *out_nodes, void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
