@@ -210,6 +210,197 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
     }
 }
 
+// rvz_solve_window's kernel: k_solve's state machine (the same frames, node counting, row codes
+// and row counters) with the caller's window at the root and, at nodes with at least `order_min`
+// empty squares, the untried move whose child leaves the side to move there the fewest legal
+// squares tried first. A kernel of its own rather than a template over k_solve, so that k_solve's
+// code object stays byte for byte what it was.
+//
+// Ordering re-scans the untried set at every pick and keeps nothing per frame: the frame stays
+// 20 B and the LDS is k_solve's. The scan is a state of the lane's machine, not an inner loop:
+// a scanning lane evaluates ONE candidate per iteration of the wave's loop (flips + the
+// opponent's legal mask, exactly what a plain lane needs to make its next move), keeps the best
+// so far in registers (square, flip mask, reply mask, reply count) and commits it in the
+// iteration that evaluates the last candidate, or at once when a candidate leaves no reply
+// (nothing later in index order can beat it). So ordering and plain lanes of one wave run the same
+// instructions in every iteration and a scan never holds the other lanes up for more than it
+// costs itself. A node with one untried move is not scanned. Scans visit no position: `nodes`
+// counts committed moves only.
+template <int BS>
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
+    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
+    const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
+    int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
+    long long* __restrict__ out_nodes, int slot) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    constexpr uint64_t FULL = Geo<BS>::FULL;
+    __shared__ uint32_t stk[FRAMES * FIELDS * SOLVE_THREADS];
+    uint32_t* const my = stk + threadIdx.x;        // field f of depth d: my[(d * FIELDS + f) * T]
+
+    bool active = false, exhausted = false;
+    int row = 0, depth = 0, alpha = 0, beta = 0, best = 0, bestsq = 0, rootpass = 0;
+    uint64_t P = 0, O = 0, rem = 0;
+    long long nodes = 0;
+    // the scan in progress: candidates not yet evaluated (0: no scan) and the best so far
+    uint64_t scan = 0, cf = 0, cMo = 0;
+    int csq = 0, ckey = 0;
+
+    auto emit = [&](int score, int move, long long cnt) {
+        out_score[row] = score;
+        out_move[row] = move;
+        if (out_nodes) out_nodes[row] = cnt;
+        active = false;
+    };
+
+    for (;;) {
+        // ---- an idle lane takes the next row and settles everything that needs no search
+        if (!active && !exhausted) {
+            const unsigned r = atomicAdd(&g_next_row[slot], 1u);
+            if (r >= (unsigned)n) {
+                exhausted = true;
+            } else {
+                row = (int)r;
+                const uint64_t b = black[row], w = white[row];
+                const int side = status[4 * row], over = status[4 * row + 1];
+                const int passed = status[4 * row + 3];
+                P = side == 1 ? b : w;
+                O = side == 1 ? w : b;
+                const int diff = __popcll(P) - __popcll(O);
+                if ((b & w) || ((b | w) & ~FULL) || (side != 1 && side != 2)) {
+                    emit(0, -5, 0);
+                } else if (over) {
+                    emit(diff, -2, 1);
+                } else if (__popcll(~(b | w) & FULL) > max_empties) {
+                    emit(0, -3, 0);
+                } else {
+                    uint64_t M = legal<BS>(P, O);
+                    rootpass = 0;
+                    nodes = 1;
+                    if (!M) {                      // the pass root, as in k_solve
+                        const uint64_t M2 = legal<BS>(O, P);
+                        if (node_limit < 2) {
+                            emit(0, -4, 1);
+                        } else if (passed + 1 >= 2) {
+                            emit(diff, NSQ, 2);
+                        } else if (!M2) {
+                            if (node_limit < 3) emit(0, -4, 2);
+                            else emit(diff, NSQ, 3);
+                        } else {                   // search the child with the negated window
+                            const uint64_t t = P; P = O; O = t;
+                            M = M2;
+                            rootpass = 1;
+                            nodes = 2;
+                        }
+                    }
+                    if (M) {
+                        active = true;
+                        rem = M;
+                        depth = 0;
+                        alpha = rootpass ? -wbeta : walpha;
+                        beta = rootpass ? -walpha : wbeta;
+                        best = -SINF;
+                        bestsq = 0;
+                        scan = 0;
+                    }
+                }
+            }
+        }
+        if (__all(exhausted)) break;               // exhausted lanes are never active
+
+        // ---- a finished node returns to its parent (one level per iteration); a scanning node
+        // has rem != 0 and best < beta, so it is never here
+        if (active && (rem == 0 || best >= beta)) {
+            if (depth == 0) {
+                // fail low (-6) is judged on the root's own score, r = best <= alpha
+                if (rootpass) emit(-best, NSQ, nodes);
+                else emit(best, best <= walpha ? -6 : bestsq, nodes);
+            } else {
+                --depth;
+                const uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
+                rem = (uint64_t)fr[0] | ((uint64_t)fr[SOLVE_THREADS] << 32);
+                const uint64_t f = (uint64_t)fr[2 * SOLVE_THREADS] |
+                                   ((uint64_t)fr[3 * SOLVE_THREADS] << 32);
+                const uint32_t pk = fr[4 * SOLVE_THREADS];
+                const int sq = pk & 63, keep = (pk >> 6) & 1;
+                const int v = keep ? best : -best;
+                if (!keep) { const uint64_t t = P; P = O; O = t; }
+                P ^= (1ull << sq) | f;             // undo the move
+                O ^= f;
+                alpha = (int)(int8_t)(pk >> 8);
+                beta = (int)(int8_t)(pk >> 16);
+                best = (int)(int8_t)(pk >> 24);
+                if (v > best) {
+                    best = v;
+                    if (depth == 0) bestsq = sq;
+                }
+                if (best > alpha) alpha = best;
+            }
+        }
+
+        // ---- an open node evaluates one square: its next move, or one candidate of its scan
+        if (active && rem != 0 && best < beta) {
+            if (nodes >= node_limit) {             // a move will be committed: one node too many
+                emit(0, -4, nodes);
+            } else {
+                const bool ordered = order_min > 0 && (rem & (rem - 1)) != 0 &&
+                                     __popcll(~(P | O) & FULL) >= order_min;
+                int sq = __builtin_ctzll(rem);
+                if (ordered) {
+                    if (!scan) { scan = rem; ckey = 65; }
+                    sq = __builtin_ctzll(scan);
+                    scan &= scan - 1;
+                }
+                uint64_t f = flips<BS>(sq, P, O);
+                uint64_t Mo = legal<BS>(O ^ f, P ^ ((1ull << sq) | f));
+                bool commit = true;
+                if (ordered) {
+                    const int key = __popcll(Mo);  // 0: the child ends the game or auto-passes
+                    if (key < ckey) { ckey = key; csq = sq; cf = f; cMo = Mo; }
+                    commit = scan == 0 || ckey == 0;
+                    if (commit) { sq = csq; f = cf; Mo = cMo; scan = 0; }
+                }
+                if (commit) {
+                    rem &= ~(1ull << sq);
+                    ++nodes;
+                    const uint64_t nP = P ^ ((1ull << sq) | f), nO = O ^ f;
+                    uint64_t Mm = 0;
+                    if (!Mo) Mm = legal<BS>(nP, nO);   // auto-pass: the mover keeps the side
+                    if (!(Mo | Mm)) {              // neither side can move: the game is over
+                        const int v = __popcll(nP) - __popcll(nO);
+                        if (v > best) {
+                            best = v;
+                            if (depth == 0) bestsq = sq;
+                        }
+                        if (best > alpha) alpha = best;
+                    } else if (depth >= FRAMES) {  // unreachable (see the head of the file)
+                        emit(0, -4, nodes);
+                    } else {
+                        const int keep = Mo ? 0 : 1;
+                        uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
+                        fr[0] = (uint32_t)rem;
+                        fr[SOLVE_THREADS] = (uint32_t)(rem >> 32);
+                        fr[2 * SOLVE_THREADS] = (uint32_t)f;
+                        fr[3 * SOLVE_THREADS] = (uint32_t)(f >> 32);
+                        fr[4 * SOLVE_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
+                                                ((uint32_t)(alpha & 0xFF) << 8) |
+                                                ((uint32_t)(beta & 0xFF) << 16) |
+                                                ((uint32_t)(best & 0xFF) << 24);
+                        ++depth;
+                        if (keep) {
+                            P = nP; O = nO; rem = Mm;
+                        } else {
+                            P = nO; O = nP; rem = Mo;
+                            const int a = alpha;
+                            alpha = -beta; beta = -a;
+                        }
+                        best = -SINF;
+                    }
+                }
+            }
+        }
+    }
+}
+
 std::atomic<unsigned> g_slot{0};
 
 }  // namespace
@@ -238,5 +429,37 @@ extern "C" int rvz_solve(int32_t bs, int32_t n, const uint64_t* black, const uin
     else
         hipLaunchKernelGGL(k_solve<6>, grid, block, 0, s, n, black, white, status, max_empties,
                            (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}
+
+extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
+                                const uint64_t* white, const int32_t* status, int32_t max_empties,
+                                int64_t node_limit, int32_t alpha, int32_t beta,
+                                int32_t order_min_empties, int32_t* out_score, int32_t* out_move,
+                                int64_t* out_nodes, void* stream) {
+    if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
+        node_limit <= 0 || alpha < -64 || alpha >= beta || beta > 64 || order_min_empties < 0 ||
+        (n > 0 && (!black || !white || !status || !out_score || !out_move)))
+        return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        return RVZ_EHIP;
+    const int slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
+    const int need = (n + SOLVE_THREADS - 1) / SOLVE_THREADS;
+    const int wgs = cus * SOLVE_WG_PER_CU;
+    dim3 grid(need < wgs ? need : wgs), block(SOLVE_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, slot);
+    if (bs == 8)
+        hipLaunchKernelGGL(k_solve_window<8>, grid, block, 0, s, n, black, white, status,
+                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
+                           out_score, out_move, (long long*)out_nodes, slot);
+    else
+        hipLaunchKernelGGL(k_solve_window<6>, grid, block, 0, s, n, black, white, status,
+                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
+                           out_score, out_move, (long long*)out_nodes, slot);
     return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }

@@ -10,10 +10,13 @@ Batched core:
     LaneRunner              independent lanes of SelfPlayRunners, one stream each, one graph
     AlphaZeroNetwork, LeafEvaluator   the policy/value net at the evaluation boundary
     solve                   exact endgame values of a batch of positions (rvz_solve)
+    solve_window, solve_wld the same within a caller's (alpha, beta) / as win, draw or loss, with
+                            optional move ordering (rvz_solve_window)
 """
 from ._lib import RvzError, load  # noqa: F401
 from .engine import (Engine, action_probs, board_apply, board_canonical,  # noqa: F401
-                     board_legal, dirichlet_noise, policy_softmax, solve)
+                     board_legal, dirichlet_noise, policy_softmax, solve, solve_window,
+                     solve_wld)
 from .game import Board, ReversiGame  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401

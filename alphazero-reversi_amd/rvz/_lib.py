@@ -86,6 +86,8 @@ SIGNATURES = {
     "rvz_action_probs": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "rvz_solve": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64, _P, _P, _P,
                             _P]),
+    "rvz_solve_window": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64,
+                                   C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),

@@ -226,6 +226,19 @@ class Engine:
         self._call("rvz_env_get", ptr(b), ptr(w), ptr(st))
         return solve(b, w, st, self.board_size, max_empties, node_limit)
 
+    def solve_wld(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24,
+                  order_min_empties: Optional[int] = None):
+        """rvz.solve_wld on the engine's current env state, as solve(): (outcome, move, nodes) per
+        game. order_min_empties None: solve_wld's default."""
+        self._stream()
+        b = torch.empty(self.n_games, dtype=torch.int64, device=self.device)
+        w = torch.empty_like(b)
+        st = torch.empty(self.n_games, 4, dtype=torch.int32, device=self.device)
+        self._call("rvz_env_get", ptr(b), ptr(w), ptr(st))
+        if order_min_empties is None:
+            order_min_empties = WLD_ORDER_MIN_EMPTIES
+        return solve_wld(b, w, st, self.board_size, max_empties, node_limit, order_min_empties)
+
     def legal(self) -> torch.Tensor:
         self._stream()
         out = torch.empty(self.n_games, dtype=torch.int64, device=self.device)
@@ -610,6 +623,59 @@ def solve(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_
                         ptr(nodes) if n else None, _lib.stream_handle(dev) if n else None),
           None, "rvz_solve")
     return score, move, nodes
+
+
+def solve_window(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
+                 board_size: int = 8, max_empties: int = SOLVE_MAX_EMPTIES,
+                 node_limit: int = 2 ** 24, alpha: int = -64, beta: int = 64,
+                 order_min_empties: int = 0):
+    """rvz_solve_window: solve() within the window (alpha, beta), -64 <= alpha < beta <= 64.
+    Inputs and outputs as solve(). With v the exact score: score == v when alpha < v < beta,
+    v <= score <= alpha when v <= alpha, beta <= score <= v when v >= beta (fail-soft); a root
+    that is over reports its exact difference. move as solve(), but -6 when score <= alpha (fail
+    low: no move reported), and when score >= beta a square whose own value is >= beta (the
+    lowest-index one with order_min_empties = 0).
+    order_min_empties = K > 0: nodes with at least K empty squares try the move that leaves the
+    opponent the fewest replies first (ties to the lowest index); 0: increasing index everywhere,
+    and then a row's nodes are at most solve()'s."""
+    lib = _lib.load()
+    n = black.numel()
+    if status.shape != (n, 4) or white.numel() != n:
+        raise RvzError("solve_window: black and white hold one entry per row, status is [n, 4]")
+    dev = black.device
+    b = black.to(torch.int64).contiguous()
+    w = white.to(dev, torch.int64).contiguous()
+    st = status.to(dev, torch.int32).contiguous()
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    move = torch.empty(n, dtype=torch.int32, device=dev)
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    check(lib.rvz_solve_window(int(board_size), n, ptr(b) if n else None, ptr(w) if n else None,
+                               ptr(st) if n else None, int(max_empties), int(node_limit),
+                               int(alpha), int(beta), int(order_min_empties),
+                               ptr(score) if n else None, ptr(move) if n else None,
+                               ptr(nodes) if n else None, _lib.stream_handle(dev) if n else None),
+          None, "rvz_solve_window")
+    return score, move, nodes
+
+
+# solve_wld's default order_min_empties: the setting that measured fastest on the MI355X
+# (profiles/solve02_wld_e10.json, solve02_wld_e12.json; solve_wld's docstring has the figures)
+WLD_ORDER_MIN_EMPTIES = 4
+
+
+def solve_wld(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int = 8,
+              max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24,
+              order_min_empties: int = WLD_ORDER_MIN_EMPTIES):
+    """Win / draw / loss of n positions: solve_window with the window (-1, +1). Returns (outcome
+    int32 [n] in {-1, 0, +1} for the side to move: the sign of the exact score; move; nodes).
+    outcome is 0 wherever move is -3 / -4 / -5 (not solved); move is -6 for a loss.
+    order_min_empties: see solve_window. The default, 4, is the fastest of 0 / 4 / 5 / 6 / 7 on
+    32,768 8x8 rows (profiles/solve02_wld_e10.json, solve02_wld_e12.json): 0.63 s at 10 empties
+    and 4.8 s at 12 against 2.2 s and 43 s with ordering off, far outside the 5 repeats' spread;
+    5 ties with it within that spread (0.63 s, 4.6 s)."""
+    score, move, nodes = solve_window(black, white, status, board_size, max_empties, node_limit,
+                                      -1, 1, order_min_empties)
+    return torch.sign(score), move, nodes
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

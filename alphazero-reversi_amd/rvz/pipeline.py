@@ -24,10 +24,10 @@ from typing import Dict, Optional
 import torch
 import torch.distributed as dist
 
-from .engine import Engine
+from .engine import SOLVE_MAX_EMPTIES, Engine
 from .network import LeafEvaluator, leaf_evaluator
 from .selfplay import SelfPlayRunner
-from .trainer import DDPTrainer, records_to_training
+from .trainer import DDPTrainer, adjudicate, records_to_training
 
 
 class SelfPlayTrainer:
@@ -39,7 +39,8 @@ class SelfPlayTrainer:
                  lr_gamma: float = 0.1, memo: bool = True, fused: bool = True,
                  table_slots: Optional[int] = None, table_discs: int = 14,
                  root_noise=None, temperature_schedule=None, exact_endgame: int = 0,
-                 exact_node_limit: int = 2 ** 24):
+                 exact_node_limit: int = 2 ** 24, exact_wld: bool = False,
+                 adjudicate_empties: int = 0, adjudicate_node_limit: int = 2 ** 24):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -48,7 +49,15 @@ class SelfPlayTrainer:
         exact_endgame: 0 (off) or N: the value targets of the records with at most N empty squares
         come from the exact endgame solver (records_to_training; rvz_solve abandoning a row after
         exact_node_limit positions), not from the outcome of the game as played. Self-play itself
-        is unchanged.
+        is unchanged. exact_wld: those targets by the win / draw / loss solve (rvz.solve_wld), the
+        same values from a smaller search.
+        adjudicate_empties: 0 (off) or N in [1, 14], N < S*S - 4: endgame adjudication. Self-play
+        stops after S*S - 4 - N plies, where every unfinished game holds exactly N empty squares
+        (every committed ply places one disc), and each such game's outcome is the win / draw /
+        loss solve of that position (rvz.trainer.adjudicate; a game abandoned after
+        adjudicate_node_limit positions is dropped from the iteration's data). The last N plies
+        are not searched and yield no training rows; every row's value target is the perfect-play
+        outcome from the stopping position.
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
@@ -60,6 +69,9 @@ class SelfPlayTrainer:
                                  else (0, 1))
         self.games, self.seed = int(games), int(seed)
         self.exact_endgame, self.exact_node_limit = int(exact_endgame), int(exact_node_limit)
+        self.exact_wld = bool(exact_wld)
+        self.adjudicate_empties = int(adjudicate_empties)
+        self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
         self.trainer = DDPTrainer(model, lr=lr, weight_decay=weight_decay,
                                   gradient_clip=gradient_clip, batch_size=train_batch,
@@ -77,6 +89,10 @@ class SelfPlayTrainer:
         if temperature_schedule is not None:
             self.eng.temperature_schedule(*temperature_schedule)
         self.max_plies = bs * bs - 4
+        if self.adjudicate_empties and not (1 <= self.adjudicate_empties <= SOLVE_MAX_EMPTIES and
+                                            self.adjudicate_empties < self.max_plies):
+            raise ValueError(f"adjudicate_empties must be 0 or in [1, {SOLVE_MAX_EMPTIES}] and "
+                             f"below {self.max_plies}")
         # fused: every game of the iteration in ONE rvz_play launch with device records, the
         # memo's deferred last batch and the cross-game table (a new generation per refresh());
         # else the pull-style ply graph (per-batch launches, records copied per ply)
@@ -103,20 +119,46 @@ class SelfPlayTrainer:
         run = self.runner
         self._seeds()
         run.start()
+        plies = self.max_plies - self.adjudicate_empties
         if self.fused:
-            run.play_record(self.max_plies)     # one launch: whole games, records on the device
+            run.play_record(plies)              # one launch: whole games, records on the device
         else:
-            for k in range(self.max_plies):
+            for k in range(plies):
                 if self.graph and run.graph is None and k == 1:
                     run.capture()               # after one eager ply (kernel warm-up)
                 run.ply()
         run.check()
+        if self.adjudicate_empties:
+            return self._adjudicated(plies)
         if not bool(run.post_status[:, 1].all()):
             raise RuntimeError(f"a game is not over after {self.max_plies} plies")
         return records_to_training(run.rec_black, run.rec_white, run.rec_side, run.rec_idx,
                                    run.rec_p, run.post_status, self.eng.board_size,
                                    exact_endgame=self.exact_endgame,
-                                   exact_node_limit=self.exact_node_limit)
+                                   exact_node_limit=self.exact_node_limit,
+                                   exact_wld=self.exact_wld)
+
+    def _adjudicated(self, plies: int) -> Dict[str, torch.Tensor]:
+        """generate()'s tail with adjudication on: the games stand after `plies` plies."""
+        run, eng, N = self.runner, self.eng, self.adjudicate_empties
+        black, white, status = eng.get_state()
+        bits = torch.arange(64, dtype=torch.int64, device=self.device)
+        discs = (((black | white).unsqueeze(1) >> bits) & 1).sum(1)
+        live = status[:, 1] == 0
+        if bool((live & (discs != eng.board_size ** 2 - N)).any()):
+            raise RuntimeError(f"a live game does not hold {N} empty squares after {plies} plies")
+        final, keep, stats = adjudicate(black, white, status, eng.board_size,
+                                        node_limit=self.adjudicate_node_limit, check_depth=False)
+        # a dropped game's plies leave the data: on a copy, the runner's records stay as played
+        rec_idx = torch.where(keep.unsqueeze(0), run.rec_idx[:plies],
+                              torch.full_like(run.rec_idx[:plies], -2))
+        out = records_to_training(run.rec_black[:plies], run.rec_white[:plies],
+                                  run.rec_side[:plies], rec_idx, run.rec_p[:plies], final,
+                                  eng.board_size, exact_endgame=self.exact_endgame,
+                                  exact_node_limit=self.exact_node_limit,
+                                  exact_wld=self.exact_wld)
+        out.update(stats)
+        return out
 
     def train(self, data: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """_train_epoch over this iteration's data (each rank walks its own games; DDP averages
@@ -146,5 +188,8 @@ class SelfPlayTrainer:
         out.update({"selfplay_s": t1 - t0, "train_s": t2 - t1, "board_steps": plies,
                     "samples": int(data["states"].shape[0]),
                     "exact_rows": int(data.get("exact_rows", 0)),
-                    "exact_unsolved": int(data.get("exact_unsolved", 0))})
+                    "exact_unsolved": int(data.get("exact_unsolved", 0)),
+                    "adjudicated": int(data.get("adjudicated", 0)),
+                    "adjudicate_unsolved": int(data.get("adjudicate_unsolved", 0)),
+                    "already_over": int(data.get("already_over", 0))})
         return out

@@ -22,13 +22,14 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .engine import board_canonical, solve
+from .engine import SOLVE_MAX_EMPTIES, board_canonical, solve, solve_wld
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
                         rec_idx: torch.Tensor, rec_p: torch.Tensor, final_status: torch.Tensor,
                         board_size: int = 8, canonical=None, exact_endgame: int = 0,
-                        solver=None, exact_node_limit: int = 2 ** 24) -> Dict[str, torch.Tensor]:
+                        solver=None, exact_node_limit: int = 2 ** 24,
+                        exact_wld: bool = False) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -45,6 +46,9 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     "exact_unsolved", the rows abandoned. N = 0 (the default) is off: the outputs of before.
     solver(black, white, status, board_size, max_empties) -> (score, move, ...): default rvz.solve
     (the rvz_solve HIP kernel) with node_limit = exact_node_limit.
+    exact_wld = True: the default solver is rvz.solve_wld (rvz_solve_window with the window
+    (-1, +1)) instead: the same targets, since only the sign is kept, from a smaller search;
+    exact_rows / exact_unsolved can differ only through the node limit.
     """
     if canonical is None:
         canonical = board_canonical
@@ -66,7 +70,7 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     if exact_endgame:
         if solver is None:
             def solver(b, w, s, bs, me):
-                return solve(b, w, s, bs, me, exact_node_limit)
+                return (solve_wld if exact_wld else solve)(b, w, s, bs, me, exact_node_limit)
         score, move = solver(black, white, st, board_size, int(exact_endgame))[:2]
         solved = move >= 0                                   # -3: above N; -4: abandoned
         exact = torch.sign(score).to(torch.float32).reshape(-1, 1)
@@ -74,6 +78,48 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
         out["exact_rows"] = solved.sum()
         out["exact_unsolved"] = (move == -4).sum()
     return out
+
+
+def adjudicate(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int,
+               solver=None, node_limit: int = 2 ** 24, check_depth: bool = True):
+    """Endgame adjudication: the final status of games stopped short of their end, each live
+    game's winner taken from a win / draw / loss solve of its position.
+
+    black / white int64 [G], status int32 [G, 4] (side, over, winner, passed): the games after the
+    shortened self-play. Returns (final_status int32 [G, 4], keep bool [G], stats). A game that is
+    over keeps its status and is kept. Any other game is solved: over = 1 and winner = the side to
+    move for +1, the other side for -1, 0 for a draw; a game the solver abandons at its node limit
+    (move -4) keeps its status and gets keep = False (its records are to be dropped). stats: 0-d
+    int64 tensors "adjudicated" (live games solved), "adjudicate_unsolved" (abandoned) and
+    "already_over".
+    A live game with more than 14 empty squares (SOLVE_MAX_EMPTIES; the solver's code -3) cannot
+    be adjudicated: with check_depth (the default) that raises ValueError, at the cost of the
+    function's only host read; a caller that has established the depth of its games itself
+    (SelfPlayTrainer has: every live game holds exactly N empties) passes check_depth=False, and
+    then nothing here synchronises with the host (such a game would get keep = False).
+    solver(black, white, status, board_size, max_empties) -> (outcome or score, move, ...):
+    default rvz.solve_wld with max_empties = 14 and node_limit; only the sign of its first output
+    is read, so records_to_training's solvers fit."""
+    if solver is None:
+        def solver(b, w, s, bs, me):
+            return solve_wld(b, w, s, bs, me, node_limit)
+    st = status.to(torch.int32)
+    over = st[:, 1] != 0
+    score, move = solver(black, white, st, board_size, SOLVE_MAX_EMPTIES)[:2]
+    score, move = score.to(st.device), move.to(st.device)
+    if check_depth and bool((~over & (move == -3)).any()):
+        raise ValueError(f"adjudicate: a live game has more than {SOLVE_MAX_EMPTIES} empty squares")
+    solved = ~over & ((move >= 0) | (move == -6))
+    side = st[:, 0]
+    sg = torch.sign(score).to(torch.int32)
+    winner = torch.where(sg > 0, side, torch.where(sg < 0, 3 - side, torch.zeros_like(side)))
+    final = st.clone()
+    final[:, 1] = torch.where(solved, torch.ones_like(side), st[:, 1])
+    final[:, 2] = torch.where(solved, winner, st[:, 2])
+    unsolved = ~over & (move == -4)
+    stats = {"adjudicated": solved.sum(), "adjudicate_unsolved": unsolved.sum(),
+             "already_over": over.sum()}
+    return final, over | solved, stats
 
 
 class DDPTrainer:

@@ -294,6 +294,35 @@ int rvz_action_probs(int32_t board_size, int32_t n, const int32_t *visits,
 int rvz_solve(int32_t board_size, int32_t n, const uint64_t *black, const uint64_t *white,
               const int32_t *status, int32_t max_empties, int64_t node_limit, int32_t *out_score,
               int32_t *out_move, int64_t *out_nodes, void *hip_stream);
+/* rvz_solve with a caller's window and optional move ordering (kernel k_solve_window). Everything
+ * not stated here is rvz_solve's: the rules, the row layout, the codes -2 / -3 / -4 / -5 and the
+ * in-kernel validation, out_nodes, the launch shape, asynchronous and graph-capturable, and the
+ * 32 row counters, which the two calls share (at most 32 calls of either kind executing at once).
+ * Let v = rvz_solve's score of the row. out_score = r, fail-soft:
+ *   alpha < v < beta: r == v;   v <= alpha: v <= r <= alpha;   v >= beta: beta <= r <= v.
+ * So (-1, +1) gives sign(r) == sign(v), the win / draw / loss question, and (-64, 64) gives
+ * r == v. A root that is already over reports its exact disc difference and move -2 whatever the
+ * window; so do the pass roots that end the game (move S*S).
+ * out_move: S*S when the root's only move is the pass; -6 ("fail low: no move reported") when
+ * r <= alpha; otherwise a root square whose own exact value m satisfies m == v when r < beta and
+ * m >= beta when r >= beta. With order_min_empties == 0 it is the lowest-index such square (for
+ * alpha < v < beta that is rvz_solve's move); with ordering on, which qualifying square is
+ * reported is unspecified, but a pure function of the row and the build.
+ * The root's children are searched with (max(best so far, alpha), beta), a pass root's child
+ * with the negated window.
+ * order_min_empties = K > 0: at every node with at least K empty squares the next move tried is
+ * the untried move whose child leaves the side to move there the fewest legal squares (a child
+ * that ends the game or auto-passes counts as 0; ties to the lowest index); below K empties, and
+ * everywhere when K == 0, moves are tried in increasing index. Ordering changes which positions
+ * are visited, never r's contract above.
+ * out_nodes: with order_min_empties == 0, at most rvz_solve's count for the row, for every window
+ * (same move order, nested windows: DESIGN.md); with ordering on there is no per-row bound. A
+ * row's outputs depend on the row, the arguments and the build alone.
+ * RVZ_EINVAL as rvz_solve, and unless -64 <= alpha < beta <= 64 and order_min_empties >= 0. */
+int rvz_solve_window(int32_t board_size, int32_t n, const uint64_t *black, const uint64_t *white,
+                     const int32_t *status, int32_t max_empties, int64_t node_limit,
+                     int32_t alpha, int32_t beta, int32_t order_min_empties,
+                     int32_t *out_score, int32_t *out_move, int64_t *out_nodes, void *hip_stream);
 
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
