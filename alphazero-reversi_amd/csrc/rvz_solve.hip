@@ -1,6 +1,6 @@
 // rvz_solve.hip — exact endgame solver: batched negamax over the reference's rules for gfx950
-// (MI355X), exported as rvz_solve (include/rvz.h). Its own translation unit: the code objects of
-// rvz_engine.hip (k_play, k_step, k_act) do not depend on it.
+// (MI355X), exported as rvz_solve and rvz_solve_window (include/rvz.h). Its own translation unit:
+// the code objects of rvz_engine.hip (k_play, k_step, k_act) do not depend on it.
 //
 // Definition (DESIGN.md §Exact endgame solver): solve(g) = the disc difference at the end of the
 // game from g's side to move, both sides playing the maximum, the children made by make_move<BS>
@@ -19,7 +19,7 @@
 // depth covers 64 consecutive banks. A frame is what the return needs: the moves left (2 dwords),
 // the flip mask of the move being searched (2 dwords: the undo), and {square, kept-side flag,
 // alpha, beta, best} packed in one dword: 20 bytes. No recursion and no run-time-indexed register
-// array: the kernel uses no scratch.
+// array: the kernels use no scratch.
 //
 // Depth: every ply places a disc, and a frame is pushed only when the child has a move, i.e. at
 // least one empty square left, so a row with E empties pushes at most E - 1 frames;
@@ -32,6 +32,23 @@
 // exact, any other comes back <= best and is dropped by the strict comparison, so the score and
 // the first-maximum move equal the unpruned definition (DESIGN.md has the argument). Node counts
 // depend on the row alone.
+//
+// One machine, two kernels: solve_rows<BS, WIN> is the loop; k_solve is WIN = false and
+// k_solve_window is WIN = true. WIN switches three things: the root window (the caller's
+// (walpha, wbeta), negated under a pass root, instead of (-SINF, SINF)), the fail-low move code
+// -6 at the root, and move ordering (below). With WIN = false those are compiled out.
+//
+// Ordering (WIN only): at nodes with at least `order_min` empty squares, the untried move whose
+// child leaves the side to move there the fewest legal squares is tried first. It re-scans the
+// untried set at every pick and keeps nothing per frame: the frame stays 20 B. The scan is a
+// state of the lane's machine, not an inner loop: a scanning lane evaluates ONE candidate per
+// iteration of the wave's loop (flips + the opponent's legal mask, exactly what a plain lane
+// needs to make its next move), keeps the best so far in registers (square, flip mask, reply
+// mask, reply count) and commits it in the iteration that evaluates the last candidate, or at
+// once when a candidate leaves no reply (nothing later in index order can beat it). So ordering
+// and plain lanes of one wave run the same instructions in every iteration and a scan never holds
+// the other lanes up for more than it costs itself. A node with one untried move is not scanned.
+// Scans visit no position: `nodes` counts committed moves only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,11 +75,13 @@ __device__ unsigned int g_next_row[SLOTS];
 
 __global__ void k_solve_zero(int slot) { g_next_row[slot] = 0u; }
 
-template <int BS>
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
+// The state machine of both kernels (the head of the file has what WIN switches); walpha, wbeta
+// and order_min are read only when WIN.
+template <int BS, bool WIN>
+__device__ __forceinline__ void solve_rows(
     int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
-    const int32_t* __restrict__ status, int max_empties, long long node_limit,
-    int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
+    const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
+    int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
     long long* __restrict__ out_nodes, int slot) {
     constexpr int NSQ = Geo<BS>::NSQ;
     constexpr uint64_t FULL = Geo<BS>::FULL;
@@ -73,6 +92,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
     int row = 0, depth = 0, alpha = 0, beta = 0, best = 0, bestsq = 0, rootpass = 0;
     uint64_t P = 0, O = 0, rem = 0;
     long long nodes = 0;
+    // WIN: the scan in progress: candidates not yet evaluated (0: no scan) and the best so far
+    uint64_t scan = 0, cf = 0, cMo = 0;
+    int csq = 0, ckey = 0;
 
     auto emit = [&](int score, int move, long long cnt) {
         out_score[row] = score;
@@ -116,8 +138,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
                         } else if (!M2) {          // the child passes too: the grandchild is over
                             if (node_limit < 3) emit(0, -4, 2);
                             else emit(diff, NSQ, 3);
-                        } else {                   // search the child; the root's score is -its
-                            const uint64_t t = P; P = O; O = t;
+                        } else {                   // search the child with the negated window;
+                            const uint64_t t = P; P = O; O = t;     // the root's score is -its
                             M = M2;
                             rootpass = 1;
                             nodes = 2;
@@ -127,180 +149,15 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
                         active = true;
                         rem = M;
                         depth = 0;
-                        alpha = -SINF; beta = SINF; best = -SINF;
-                        bestsq = 0;
-                    }
-                }
-            }
-        }
-        if (__all(exhausted)) break;               // exhausted lanes are never active
-
-        // ---- a finished node returns to its parent (one level per iteration)
-        if (active && (rem == 0 || best >= beta)) {
-            if (depth == 0) {
-                emit(rootpass ? -best : best, rootpass ? NSQ : bestsq, nodes);
-            } else {
-                --depth;
-                const uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
-                rem = (uint64_t)fr[0] | ((uint64_t)fr[SOLVE_THREADS] << 32);
-                const uint64_t f = (uint64_t)fr[2 * SOLVE_THREADS] |
-                                   ((uint64_t)fr[3 * SOLVE_THREADS] << 32);
-                const uint32_t pk = fr[4 * SOLVE_THREADS];
-                const int sq = pk & 63, keep = (pk >> 6) & 1;
-                const int v = keep ? best : -best;
-                if (!keep) { const uint64_t t = P; P = O; O = t; }
-                P ^= (1ull << sq) | f;             // undo the move
-                O ^= f;
-                alpha = (int)(int8_t)(pk >> 8);
-                beta = (int)(int8_t)(pk >> 16);
-                best = (int)(int8_t)(pk >> 24);
-                if (v > best) {
-                    best = v;
-                    if (depth == 0) bestsq = sq;
-                }
-                if (best > alpha) alpha = best;
-            }
-        }
-
-        // ---- an open node tries its next move
-        if (active && rem != 0 && best < beta) {
-            const int sq = __builtin_ctzll(rem);
-            rem &= rem - 1;
-            if (nodes >= node_limit) {
-                emit(0, -4, nodes);
-            } else {
-                ++nodes;
-                const uint64_t f = flips<BS>(sq, P, O);
-                const uint64_t nP = P ^ ((1ull << sq) | f), nO = O ^ f;
-                const uint64_t Mo = legal<BS>(nO, nP);
-                uint64_t Mm = 0;
-                if (!Mo) Mm = legal<BS>(nP, nO);   // auto-pass: the mover keeps the side
-                if (!(Mo | Mm)) {                  // neither side can move: the game is over
-                    const int v = __popcll(nP) - __popcll(nO);
-                    if (v > best) {
-                        best = v;
-                        if (depth == 0) bestsq = sq;
-                    }
-                    if (best > alpha) alpha = best;
-                } else if (depth >= FRAMES) {      // unreachable (see the head of the file)
-                    emit(0, -4, nodes);
-                } else {
-                    const int keep = Mo ? 0 : 1;
-                    uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
-                    fr[0] = (uint32_t)rem;
-                    fr[SOLVE_THREADS] = (uint32_t)(rem >> 32);
-                    fr[2 * SOLVE_THREADS] = (uint32_t)f;
-                    fr[3 * SOLVE_THREADS] = (uint32_t)(f >> 32);
-                    fr[4 * SOLVE_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
-                                            ((uint32_t)(alpha & 0xFF) << 8) |
-                                            ((uint32_t)(beta & 0xFF) << 16) |
-                                            ((uint32_t)(best & 0xFF) << 24);
-                    ++depth;
-                    if (keep) {
-                        P = nP; O = nO; rem = Mm;
-                    } else {
-                        P = nO; O = nP; rem = Mo;
-                        const int a = alpha;
-                        alpha = -beta; beta = -a;
-                    }
-                    best = -SINF;
-                }
-            }
-        }
-    }
-}
-
-// rvz_solve_window's kernel: k_solve's state machine (the same frames, node counting, row codes
-// and row counters) with the caller's window at the root and, at nodes with at least `order_min`
-// empty squares, the untried move whose child leaves the side to move there the fewest legal
-// squares tried first. A kernel of its own rather than a template over k_solve, so that k_solve's
-// code object stays byte for byte what it was.
-//
-// Ordering re-scans the untried set at every pick and keeps nothing per frame: the frame stays
-// 20 B and the LDS is k_solve's. The scan is a state of the lane's machine, not an inner loop:
-// a scanning lane evaluates ONE candidate per iteration of the wave's loop (flips + the
-// opponent's legal mask, exactly what a plain lane needs to make its next move), keeps the best
-// so far in registers (square, flip mask, reply mask, reply count) and commits it in the
-// iteration that evaluates the last candidate, or at once when a candidate leaves no reply
-// (nothing later in index order can beat it). So ordering and plain lanes of one wave run the same
-// instructions in every iteration and a scan never holds the other lanes up for more than it
-// costs itself. A node with one untried move is not scanned. Scans visit no position: `nodes`
-// counts committed moves only.
-template <int BS>
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
-    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
-    const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
-    int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
-    long long* __restrict__ out_nodes, int slot) {
-    constexpr int NSQ = Geo<BS>::NSQ;
-    constexpr uint64_t FULL = Geo<BS>::FULL;
-    __shared__ uint32_t stk[FRAMES * FIELDS * SOLVE_THREADS];
-    uint32_t* const my = stk + threadIdx.x;        // field f of depth d: my[(d * FIELDS + f) * T]
-
-    bool active = false, exhausted = false;
-    int row = 0, depth = 0, alpha = 0, beta = 0, best = 0, bestsq = 0, rootpass = 0;
-    uint64_t P = 0, O = 0, rem = 0;
-    long long nodes = 0;
-    // the scan in progress: candidates not yet evaluated (0: no scan) and the best so far
-    uint64_t scan = 0, cf = 0, cMo = 0;
-    int csq = 0, ckey = 0;
-
-    auto emit = [&](int score, int move, long long cnt) {
-        out_score[row] = score;
-        out_move[row] = move;
-        if (out_nodes) out_nodes[row] = cnt;
-        active = false;
-    };
-
-    for (;;) {
-        // ---- an idle lane takes the next row and settles everything that needs no search
-        if (!active && !exhausted) {
-            const unsigned r = atomicAdd(&g_next_row[slot], 1u);
-            if (r >= (unsigned)n) {
-                exhausted = true;
-            } else {
-                row = (int)r;
-                const uint64_t b = black[row], w = white[row];
-                const int side = status[4 * row], over = status[4 * row + 1];
-                const int passed = status[4 * row + 3];
-                P = side == 1 ? b : w;
-                O = side == 1 ? w : b;
-                const int diff = __popcll(P) - __popcll(O);
-                if ((b & w) || ((b | w) & ~FULL) || (side != 1 && side != 2)) {
-                    emit(0, -5, 0);
-                } else if (over) {
-                    emit(diff, -2, 1);
-                } else if (__popcll(~(b | w) & FULL) > max_empties) {
-                    emit(0, -3, 0);
-                } else {
-                    uint64_t M = legal<BS>(P, O);
-                    rootpass = 0;
-                    nodes = 1;
-                    if (!M) {                      // the pass root, as in k_solve
-                        const uint64_t M2 = legal<BS>(O, P);
-                        if (node_limit < 2) {
-                            emit(0, -4, 1);
-                        } else if (passed + 1 >= 2) {
-                            emit(diff, NSQ, 2);
-                        } else if (!M2) {
-                            if (node_limit < 3) emit(0, -4, 2);
-                            else emit(diff, NSQ, 3);
-                        } else {                   // search the child with the negated window
-                            const uint64_t t = P; P = O; O = t;
-                            M = M2;
-                            rootpass = 1;
-                            nodes = 2;
+                        if constexpr (WIN) {
+                            alpha = rootpass ? -wbeta : walpha;
+                            beta = rootpass ? -walpha : wbeta;
+                            scan = 0;
+                        } else {
+                            alpha = -SINF; beta = SINF;
                         }
-                    }
-                    if (M) {
-                        active = true;
-                        rem = M;
-                        depth = 0;
-                        alpha = rootpass ? -wbeta : walpha;
-                        beta = rootpass ? -walpha : wbeta;
                         best = -SINF;
                         bestsq = 0;
-                        scan = 0;
                     }
                 }
             }
@@ -311,9 +168,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
         // has rem != 0 and best < beta, so it is never here
         if (active && (rem == 0 || best >= beta)) {
             if (depth == 0) {
-                // fail low (-6) is judged on the root's own score, r = best <= alpha
+                // WIN: fail low (-6) is judged on the root's own score, r = best <= alpha
                 if (rootpass) emit(-best, NSQ, nodes);
-                else emit(best, best <= walpha ? -6 : bestsq, nodes);
+                else emit(best, WIN && best <= walpha ? -6 : bestsq, nodes);
             } else {
                 --depth;
                 const uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
@@ -342,7 +199,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
             if (nodes >= node_limit) {             // a move will be committed: one node too many
                 emit(0, -4, nodes);
             } else {
-                const bool ordered = order_min > 0 && (rem & (rem - 1)) != 0 &&
+                const bool ordered = WIN && order_min > 0 && (rem & (rem - 1)) != 0 &&
                                      __popcll(~(P | O) & FULL) >= order_min;
                 int sq = __builtin_ctzll(rem);
                 if (ordered) {
@@ -401,33 +258,66 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
     }
 }
 
+template <int BS>
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
+    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
+    const int32_t* __restrict__ status, int max_empties, long long node_limit,
+    int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
+    long long* __restrict__ out_nodes, int slot) {
+    solve_rows<BS, false>(n, black, white, status, max_empties, node_limit, 0, 0, 0, out_score,
+                          out_move, out_nodes, slot);
+}
+
+template <int BS>
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
+    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
+    const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
+    int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
+    long long* __restrict__ out_nodes, int slot) {
+    solve_rows<BS, true>(n, black, white, status, max_empties, node_limit, walpha, wbeta,
+                         order_min, out_score, out_move, out_nodes, slot);
+}
+
 std::atomic<unsigned> g_slot{0};
+
+// What both entry points do before their own launch: the common argument checks (RVZ_EINVAL
+// before any HIP call), then for n > 0 the row-counter slot, the grid and the zeroing launch.
+// Returns the grid size, 0 when n == 0 (nothing to launch), or a negative RVZ_E* code.
+int solve_prepare(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
+                  const int32_t* status, int32_t max_empties, int64_t node_limit,
+                  const int32_t* out_score, const int32_t* out_move, hipStream_t s, int* slot) {
+    if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
+        node_limit <= 0 || (n > 0 && (!black || !white || !status || !out_score || !out_move)))
+        return RVZ_EINVAL;
+    if (n == 0) return 0;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus <= 0)
+        return RVZ_EHIP;
+    *slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
+    hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, *slot);
+    const int need = (n + SOLVE_THREADS - 1) / SOLVE_THREADS;
+    const int wgs = cus * SOLVE_WG_PER_CU;
+    return need < wgs ? need : wgs;
+}
 
 }  // namespace
 
 extern "C" int rvz_solve(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
                          const int32_t* status, int32_t max_empties, int64_t node_limit,
                          int32_t* out_score, int32_t* out_move, int64_t* out_nodes, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
-        node_limit <= 0 || (n > 0 && (!black || !white || !status || !out_score || !out_move)))
-        return RVZ_EINVAL;
-    if (n == 0) return RVZ_OK;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        return RVZ_EHIP;
-    const int slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
-    const int need = (n + SOLVE_THREADS - 1) / SOLVE_THREADS;
-    const int wgs = cus * SOLVE_WG_PER_CU;
-    dim3 grid(need < wgs ? need : wgs), block(SOLVE_THREADS);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, slot);
+    int slot = 0;
+    const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_score,
+                                  out_move, s, &slot);
+    if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
+    dim3 g(wgs), block(SOLVE_THREADS);
     if (bs == 8)
-        hipLaunchKernelGGL(k_solve<8>, grid, block, 0, s, n, black, white, status, max_empties,
+        hipLaunchKernelGGL(k_solve<8>, g, block, 0, s, n, black, white, status, max_empties,
                            (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
     else
-        hipLaunchKernelGGL(k_solve<6>, grid, block, 0, s, n, black, white, status, max_empties,
+        hipLaunchKernelGGL(k_solve<6>, g, block, 0, s, n, black, white, status, max_empties,
                            (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
     return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }
@@ -437,28 +327,19 @@ extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
                                 int64_t node_limit, int32_t alpha, int32_t beta,
                                 int32_t order_min_empties, int32_t* out_score, int32_t* out_move,
                                 int64_t* out_nodes, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
-        node_limit <= 0 || alpha < -64 || alpha >= beta || beta > 64 || order_min_empties < 0 ||
-        (n > 0 && (!black || !white || !status || !out_score || !out_move)))
-        return RVZ_EINVAL;
-    if (n == 0) return RVZ_OK;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        return RVZ_EHIP;
-    const int slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
-    const int need = (n + SOLVE_THREADS - 1) / SOLVE_THREADS;
-    const int wgs = cus * SOLVE_WG_PER_CU;
-    dim3 grid(need < wgs ? need : wgs), block(SOLVE_THREADS);
+    if (alpha < -64 || alpha >= beta || beta > 64 || order_min_empties < 0) return RVZ_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, slot);
+    int slot = 0;
+    const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_score,
+                                  out_move, s, &slot);
+    if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
+    dim3 g(wgs), block(SOLVE_THREADS);
     if (bs == 8)
-        hipLaunchKernelGGL(k_solve_window<8>, grid, block, 0, s, n, black, white, status,
+        hipLaunchKernelGGL(k_solve_window<8>, g, block, 0, s, n, black, white, status,
                            max_empties, (long long)node_limit, alpha, beta, order_min_empties,
                            out_score, out_move, (long long*)out_nodes, slot);
     else
-        hipLaunchKernelGGL(k_solve_window<6>, grid, block, 0, s, n, black, white, status,
+        hipLaunchKernelGGL(k_solve_window<6>, g, block, 0, s, n, black, white, status,
                            max_empties, (long long)node_limit, alpha, beta, order_min_empties,
                            out_score, out_move, (long long*)out_nodes, slot);
     return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;

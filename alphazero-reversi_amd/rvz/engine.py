@@ -215,26 +215,27 @@ class Engine:
         self._call("rvz_env_set", ptr(b), ptr(w), ptr(st))
         torch.cuda.current_stream(self.device).synchronize()  # b, w, st are temporaries
 
-    def solve(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24):
-        """rvz.solve on the engine's current env state (rvz_env_get into fresh tensors, then
-        rvz_solve): (score, move, nodes) per game. Reads only: the env, a running search and the
-        buffers get_state() returns are left as they are."""
+    def _env_snapshot(self):
+        """rvz_env_get into fresh tensors (black, white, status): get_state()'s buffers stay."""
         self._stream()
         b = torch.empty(self.n_games, dtype=torch.int64, device=self.device)
         w = torch.empty_like(b)
         st = torch.empty(self.n_games, 4, dtype=torch.int32, device=self.device)
         self._call("rvz_env_get", ptr(b), ptr(w), ptr(st))
+        return b, w, st
+
+    def solve(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24):
+        """rvz.solve on the engine's current env state (rvz_env_get into fresh tensors, then
+        rvz_solve): (score, move, nodes) per game. Reads only: the env, a running search and the
+        buffers get_state() returns are left as they are."""
+        b, w, st = self._env_snapshot()
         return solve(b, w, st, self.board_size, max_empties, node_limit)
 
     def solve_wld(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24,
                   order_min_empties: Optional[int] = None):
         """rvz.solve_wld on the engine's current env state, as solve(): (outcome, move, nodes) per
         game. order_min_empties None: solve_wld's default."""
-        self._stream()
-        b = torch.empty(self.n_games, dtype=torch.int64, device=self.device)
-        w = torch.empty_like(b)
-        st = torch.empty(self.n_games, 4, dtype=torch.int32, device=self.device)
-        self._call("rvz_env_get", ptr(b), ptr(w), ptr(st))
+        b, w, st = self._env_snapshot()
         if order_min_empties is None:
             order_min_empties = WLD_ORDER_MIN_EMPTIES
         return solve_wld(b, w, st, self.board_size, max_empties, node_limit, order_min_empties)
@@ -596,6 +597,29 @@ def action_probs(visits: torch.Tensor, temperature, u: Optional[torch.Tensor] = 
     return idx, p, drew
 
 
+def _solve_call(name, black, white, status, board_size, max_empties, node_limit, *extra):
+    """solve / solve_window: lib.rvz_<name> on the rows, `extra` the integer arguments the entry
+    point takes between node_limit and the outputs. Every pointer is null when n == 0."""
+    lib = _lib.load()
+    n = black.numel()
+    if status.shape != (n, 4) or white.numel() != n:
+        raise RvzError(f"{name}: black and white hold one entry per row, status is [n, 4]")
+    dev = black.device
+    b = black.to(torch.int64).contiguous()
+    w = white.to(dev, torch.int64).contiguous()
+    st = status.to(dev, torch.int32).contiguous()
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    move = torch.empty(n, dtype=torch.int32, device=dev)
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    pb, pw, pst, pscore, pmove, pnodes, stream = (
+        [ptr(t) for t in (b, w, st, score, move, nodes)] + [_lib.stream_handle(dev)]
+        if n else [None] * 7)
+    check(getattr(lib, "rvz_" + name)(int(board_size), n, pb, pw, pst, int(max_empties),
+                                      int(node_limit), *map(int, extra), pscore, pmove, pnodes,
+                                      stream), None, "rvz_" + name)
+    return score, move, nodes
+
+
 def solve(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int = 8,
           max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24):
     """rvz_solve: the exact value of n positions under the engine's rules (exhaustive negamax
@@ -606,23 +630,7 @@ def solve(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_
     root that is over (score valid), -3 above max_empties, -4 abandoned at node_limit visited
     positions, -5 for a malformed row (score 0 for -3 / -4 / -5); nodes counts the positions
     visited."""
-    lib = _lib.load()
-    n = black.numel()
-    if status.shape != (n, 4) or white.numel() != n:
-        raise RvzError("solve: black and white hold one entry per row, status is [n, 4]")
-    dev = black.device
-    b = black.to(torch.int64).contiguous()
-    w = white.to(dev, torch.int64).contiguous()
-    st = status.to(dev, torch.int32).contiguous()
-    score = torch.empty(n, dtype=torch.int32, device=dev)
-    move = torch.empty(n, dtype=torch.int32, device=dev)
-    nodes = torch.empty(n, dtype=torch.int64, device=dev)
-    check(lib.rvz_solve(int(board_size), n, ptr(b) if n else None, ptr(w) if n else None,
-                        ptr(st) if n else None, int(max_empties), int(node_limit),
-                        ptr(score) if n else None, ptr(move) if n else None,
-                        ptr(nodes) if n else None, _lib.stream_handle(dev) if n else None),
-          None, "rvz_solve")
-    return score, move, nodes
+    return _solve_call("solve", black, white, status, board_size, max_empties, node_limit)
 
 
 def solve_window(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
@@ -638,24 +646,8 @@ def solve_window(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
     order_min_empties = K > 0: nodes with at least K empty squares try the move that leaves the
     opponent the fewest replies first (ties to the lowest index); 0: increasing index everywhere,
     and then a row's nodes are at most solve()'s."""
-    lib = _lib.load()
-    n = black.numel()
-    if status.shape != (n, 4) or white.numel() != n:
-        raise RvzError("solve_window: black and white hold one entry per row, status is [n, 4]")
-    dev = black.device
-    b = black.to(torch.int64).contiguous()
-    w = white.to(dev, torch.int64).contiguous()
-    st = status.to(dev, torch.int32).contiguous()
-    score = torch.empty(n, dtype=torch.int32, device=dev)
-    move = torch.empty(n, dtype=torch.int32, device=dev)
-    nodes = torch.empty(n, dtype=torch.int64, device=dev)
-    check(lib.rvz_solve_window(int(board_size), n, ptr(b) if n else None, ptr(w) if n else None,
-                               ptr(st) if n else None, int(max_empties), int(node_limit),
-                               int(alpha), int(beta), int(order_min_empties),
-                               ptr(score) if n else None, ptr(move) if n else None,
-                               ptr(nodes) if n else None, _lib.stream_handle(dev) if n else None),
-          None, "rvz_solve_window")
-    return score, move, nodes
+    return _solve_call("solve_window", black, white, status, board_size, max_empties, node_limit,
+                       alpha, beta, order_min_empties)
 
 
 # solve_wld's default order_min_empties: the setting that measured fastest on the MI355X

@@ -168,6 +168,105 @@ def to_arrays(games):
     return b, w, st
 
 
+def to_device(games):
+    """to_arrays(games) as tensors on the current GPU."""
+    import torch
+    return tuple(torch.from_numpy(a).cuda() for a in to_arrays(games))
+
+
+def pass_roots(bs, seeds):
+    """Roots whose mover has no move: the position after an auto-pass with the side flipped."""
+    out = []
+    for s in seeds:
+        g = last_auto_pass(s, 0, bs)
+        assert g is not None and not g.over
+        g.side = 3 - g.side
+        assert mover_mask(g, bs) == 0
+        out.append(g)
+    return out
+
+
+class RootCases:
+    """The root-case batch of the solver tests (run at max_empties = 6): 8 plain rows at 6 empties
+    with the rows that need no search, or only the pass, mixed in.
+
+    plain    the 8 ordinary rows; mixed[i] for i in keep, in order
+    mixed    the batch: a special row after each of the first plain rows, the rest appended
+    where    {index in mixed: index in special / expect}
+    expect   per special row (score, move, ends): what rvz_solve reports. ends is False for a
+             pass root whose pass does not end the game (its score is searched, so only exact
+             inside a window) and True for every other row (score holds under any window)
+    zero     the batch for max_empties = 0: a full board, the finished game, plain[0] and the pass
+             roots; zero_full is the full board
+    """
+
+    def __init__(self, bs, seeds):
+        nsq = bs * bs
+        self.plain = plain = [position(s, 6, bs)[0] for s in range(8)]
+        self.special, self.expect = special, expect = [], []
+        # a finished game: play a generated position out
+        self.over = over = position(3, 0, bs)[0]
+        assert over.over
+        special.append(over)
+        expect.append((discs_diff(over), -2, True))
+        # the mover has no move: passed = 0 (the other side plays on, unless it has no move
+        # either) and passed = 1 (the game ends)
+        for g in pass_roots(bs, seeds):
+            for passed in (0, 1):
+                c = g.copy()
+                c.passed = passed
+                hs, hm, _ = negamax(c, bs)
+                assert hm == -1
+                child = c.copy()
+                assert O.make_move(child, -1, bs)
+                ends = bool(child.over) or mover_mask(child, bs) == 0
+                if passed:
+                    assert ends and hs == discs_diff(c)
+                special.append(c)
+                expect.append((hs, nsq, ends))
+        # above max_empties
+        special.append(position(0, 7, bs)[0])
+        expect.append((0, -3, True))
+        # malformed rows: overlap, bits at or above S*S (6x6 only has such bits), side not 1 | 2
+        g = plain[0].copy()
+        g.white |= g.black & -g.black
+        special.append(g)
+        expect.append((0, -5, True))
+        if bs == 6:
+            for bit, col in ((36, "black"), (63, "white")):
+                g = plain[1].copy()
+                setattr(g, col, getattr(g, col) | 1 << bit)
+                special.append(g)
+                expect.append((0, -5, True))
+        for side in (0, 3, -1):
+            g = plain[2].copy()
+            g.side = side
+            special.append(g)
+            expect.append((0, -5, True))
+        # mixed into ordinary rows, whose answers must not change
+        self.mixed, self.where = mixed, where = [], {}
+        for i, g in enumerate(plain):
+            mixed.append(g)
+            if i < len(special):
+                where[len(mixed)] = i
+                mixed.append(special[i])
+        for j in range(len(plain), len(special)):
+            where[len(mixed)] = j
+            mixed.append(special[j])
+        self.keep = [i for i in range(len(mixed)) if i not in where]
+        # max_empties = 0: only full or finished boards are solved
+        full = (1 << nsq) - 1
+        self.zero_full = O.Game(full & 0x5555555555555555, full & 0xAAAAAAAAAAAAAAAA, 1, 0, -1, 0)
+        self.zero = [self.zero_full, over, plain[0]] + pass_roots(bs, seeds)
+
+    def check_zero(self, bs, s0, m0):
+        """The answers of the `zero` batch at max_empties = 0."""
+        hs, hm, _ = negamax(self.zero_full, bs)
+        assert hm == -1 and (s0[0], m0[0]) == (hs, bs * bs)
+        assert (s0[1], m0[1]) == (discs_diff(self.over), -2)
+        assert list(m0[2:]) == [-3] * (len(self.zero) - 2) and not s0[2:].any()
+
+
 @functools.lru_cache(maxsize=None)
 def solved(seed: int, max_empties: int, bs: int = 8):
     """(score, move in rvz_solve's encoding, nodes) of position(seed, max_empties, bs) by the

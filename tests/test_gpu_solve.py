@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import solve_ref as R
+import solve_window_ref as W
 
 pytestmark = pytest.mark.gpu
 
@@ -15,7 +16,7 @@ BIG = 2 ** 40        # a node limit no row of these tests reaches
 def gpu_solve(games, bs, max_empties=None, node_limit=BIG):
     import rvz
     from rvz._lib import RVZ_SOLVE_MAX_EMPTIES
-    b, w, st = (torch.from_numpy(a).cuda() for a in R.to_arrays(games))
+    b, w, st = R.to_device(games)
     s, m, k = rvz.solve(b, w, st, bs, RVZ_SOLVE_MAX_EMPTIES if max_empties is None else
                         max_empties, node_limit)
     assert s.dtype == torch.int32 and m.dtype == torch.int32 and k.dtype == torch.int64
@@ -30,6 +31,9 @@ def check_exact(bs, seeds, empties):
         hs, hm, hk = R.solved(s, empties, bs)
         assert (score[i], move[i]) == (hs, hm), (bs, empties, s, score[i], move[i], hs, hm)
         assert 1 <= nodes[i] <= hk, (bs, empties, s, nodes[i], hk)
+        # node for node the host's fail-soft search in index order with the open window
+        want = W.window_ab_seed(s, empties, bs, -W.INF, W.INF)[2]
+        assert nodes[i] == want, (bs, empties, s, nodes[i], want)
 
 
 def quirk_roots(bs, seeds, empties):
@@ -75,91 +79,25 @@ def test_batch_shape_independence():
     side.synchronize()
 
 
-def pass_roots(bs, seeds):
-    """Roots whose mover has no move: the position after an auto-pass with the side flipped."""
-    out = []
-    for s in seeds:
-        g = R.last_auto_pass(s, 0, bs)
-        assert g is not None and not g.over
-        g.side = 3 - g.side
-        assert R.mover_mask(g, bs) == 0
-        out.append(g)
-    return out
-
-
 @pytest.mark.parametrize("bs,seeds", [(8, (12, 25)), (6, (9, 15))])
 def test_root_cases(bs, seeds):
-    O = R.O
-    nsq = bs * bs
-    plain = [R.position(s, 6, bs)[0] for s in range(8)]
-    want = gpu_solve(plain, bs)
-    full = (1 << nsq) - 1
-    special, expect = [], []            # expect: (score, move) or move alone (score 0)
-    # a finished game: play a generated position out
-    over = R.position(3, 0, bs)[0]
-    assert over.over
-    special.append(over)
-    expect.append((R.discs_diff(over), -2))
-    # the mover has no move: passed = 0 (the other side plays on) and passed = 1 (the game ends)
-    for g in pass_roots(bs, seeds):
-        for passed in (0, 1):
-            c = g.copy()
-            c.passed = passed
-            hs, hm, _ = R.negamax(c, bs)
-            assert hm == -1
-            if passed:
-                assert hs == R.discs_diff(c)
-            special.append(c)
-            expect.append((hs, nsq))
-    # above max_empties (the batch runs at max_empties = 6)
-    special.append(R.position(0, 7, bs)[0])
-    expect.append((0, -3))
-    # malformed rows: overlap, bits at or above S*S (6x6 only has such bits), side not 1 | 2
-    g = plain[0].copy()
-    g.white |= g.black & -g.black
-    special.append(g)
-    expect.append((0, -5))
-    if bs == 6:
-        g = plain[1].copy()
-        g.black |= 1 << 36
-        special.append(g)
-        expect.append((0, -5))
-        g = plain[1].copy()
-        g.white |= 1 << 63
-        special.append(g)
-        expect.append((0, -5))
-    for side in (0, 3, -1):
-        g = plain[2].copy()
-        g.side = side
-        special.append(g)
-        expect.append((0, -5))
-    # mixed into ordinary rows, whose answers must not change
-    mixed, where = [], {}
-    for i, g in enumerate(plain):
-        mixed.append(g)
-        if i < len(special):
-            where[len(mixed)] = i
-            mixed.append(special[i])
-    for j in range(len(plain), len(special)):
-        where[len(mixed)] = j
-        mixed.append(special[j])
-    score, move, nodes = gpu_solve(mixed, bs, max_empties=6)
-    keep = [i for i in range(len(mixed)) if i not in where]
+    c = R.RootCases(bs, seeds)
+    want = gpu_solve(c.plain, bs)
+    score, move, nodes = gpu_solve(c.mixed, bs, max_empties=6)
     for got, w in zip((score, move, nodes), want):
-        assert np.array_equal(got[keep], w)
-    for i, j in where.items():
-        assert (score[i], move[i]) == expect[j], (j, score[i], move[i], expect[j])
+        assert np.array_equal(got[c.keep], w)
+    for i in c.keep:
+        assert nodes[i] == W.window_ab(c.mixed[i], bs, -W.INF, W.INF)[2], i
+    for i, j in c.where.items():
+        assert (score[i], move[i]) == c.expect[j][:2], (j, score[i], move[i], c.expect[j])
         if move[i] in (-3, -5):
             assert nodes[i] == 0
+        elif move[i] == bs * bs:            # a pass root
+            assert nodes[i] == W.window_ab(c.mixed[i], bs, -W.INF, W.INF)[2], j
         else:
             assert nodes[i] >= 1
-    # max_empties = 0: only full or finished boards are solved
-    g_full = O.Game(full & 0x5555555555555555, full & 0xAAAAAAAAAAAAAAAA, 1, 0, -1, 0)
-    s0, m0, _ = gpu_solve([g_full, over, plain[0]] + pass_roots(bs, seeds), bs, max_empties=0)
-    hs, hm, _ = R.negamax(g_full, bs)
-    assert hm == -1 and (s0[0], m0[0]) == (hs, nsq)
-    assert (s0[1], m0[1]) == (R.discs_diff(over), -2)
-    assert list(m0[2:]) == [-3] * (1 + len(seeds)) and not s0[2:].any()
+    s0, m0, _ = gpu_solve(c.zero, bs, max_empties=0)
+    c.check_zero(bs, s0, m0)
 
 
 def test_node_limit():
@@ -198,7 +136,7 @@ def test_api_errors():
     lib = rvz.load()
     EINVAL = -22
     games = [R.position(s, 6, 8)[0] for s in range(4)]
-    b, w, st = (torch.from_numpy(a).cuda() for a in R.to_arrays(games))
+    b, w, st = R.to_device(games)
     sc = torch.full((4,), 77, dtype=torch.int32, device="cuda")
     mv = torch.full((4,), 77, dtype=torch.int32, device="cuda")
     nd = torch.full((4,), 77, dtype=torch.int64, device="cuda")
@@ -234,7 +172,7 @@ def test_api_errors():
 def test_engine_solve():
     import rvz
     games = [R.position(s, 6, 8)[0] for s in range(16)]
-    b, w, st = (torch.from_numpy(a).cuda() for a in R.to_arrays(games))
+    b, w, st = R.to_device(games)
     eng = rvz.Engine(16, num_simulations=16, batch_size=16, device="cuda:0")
     eng.set_state(b, w, st)
     before = [t.clone() for t in eng.get_state()]

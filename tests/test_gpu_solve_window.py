@@ -58,14 +58,10 @@ def set_windows(name):
     return out
 
 
-def to_gpu(games):
-    return tuple(torch.from_numpy(a).cuda() for a in R.to_arrays(games))
-
-
 def gpu_window(games, bs, alpha, beta, order=0, max_empties=None, node_limit=BIG):
     import rvz
     from rvz._lib import RVZ_SOLVE_MAX_EMPTIES
-    b, w, st = to_gpu(games)
+    b, w, st = R.to_device(games)
     s, m, k = rvz.solve_window(b, w, st, bs, RVZ_SOLVE_MAX_EMPTIES if max_empties is None else
                                max_empties, node_limit, alpha, beta, order)
     assert s.dtype == torch.int32 and m.dtype == torch.int32 and k.dtype == torch.int64
@@ -75,7 +71,7 @@ def gpu_window(games, bs, alpha, beta, order=0, max_empties=None, node_limit=BIG
 
 def gpu_solve(games, bs):
     import rvz
-    b, w, st = to_gpu(games)
+    b, w, st = R.to_device(games)
     return tuple(t.cpu().numpy() for t in rvz.solve(b, w, st, bs, 14, BIG))
 
 
@@ -124,7 +120,7 @@ def test_solve_wld(order):
     import rvz
     for name in SETS:
         bs, games, host = set_rows(name)
-        b, w, st = to_gpu(games)
+        b, w, st = R.to_device(games)
         kw = {} if order is None else {"order_min_empties": order}
         out, move, nodes = rvz.solve_wld(b, w, st, bs, 14, BIG, **kw)
         assert out.dtype == torch.int32 and move.dtype == torch.int32
@@ -133,98 +129,34 @@ def test_solve_wld(order):
         assert all((m[i] == -6) == (host[i][0] < 0) for i in range(len(host)))   # a loss
     # unsolved rows report 0
     deep = [R.position(0, 7, 8)[0], R.position(1, 6, 8)[0]]
-    b, w, st = to_gpu(deep)
+    b, w, st = R.to_device(deep)
     out, move, _ = rvz.solve_wld(b, w, st, 8, 6, BIG, **kw)
     assert int(move[0]) == -3 and int(out[0]) == 0
     out, move, _ = rvz.solve_wld(b, w, st, 8, 7, 1, **kw)
     assert [int(x) for x in move.cpu()] == [-4, -4] and not bool(out.any())
 
 
-def pass_roots(bs, seeds):
-    """Roots whose mover has no move: the position after an auto-pass with the side flipped."""
-    out = []
-    for s in seeds:
-        g = R.last_auto_pass(s, 0, bs)
-        assert g is not None and not g.over
-        g.side = 3 - g.side
-        assert R.mover_mask(g, bs) == 0
-        out.append(g)
-    return out
-
-
 @pytest.mark.parametrize("order", [0, 1])
 @pytest.mark.parametrize("bs,seeds", [(8, (12, 25)), (6, (9, 15))])
 def test_root_cases(bs, seeds, order):
     """test_gpu_solve.py's root cases under the window (-1, 1)."""
-    nsq = bs * bs
-    plain = [R.position(s, 6, bs)[0] for s in range(8)]
-    want = gpu_window(plain, bs, -1, 1, order)
-    special, expect = [], []            # expect: (score, move), score None: only its sign
-    over = R.position(3, 0, bs)[0]
-    assert over.over
-    special.append(over)
-    expect.append((R.discs_diff(over), -2))
-    for g in pass_roots(bs, seeds):
-        for passed in (0, 1):
-            c = g.copy()
-            c.passed = passed
-            hs, hm, _ = R.negamax(c, bs)
-            assert hm == -1
-            special.append(c)
-            # a pass that ends the game reports the exact difference; else fail-soft in (-1, 1)
-            child = c.copy()
-            assert R.O.make_move(child, -1, bs)
-            ends = child.over or R.mover_mask(child, bs) == 0
-            expect.append((hs if ends else None, nsq))
-    special.append(R.position(0, 7, bs)[0])
-    expect.append((0, -3))
-    g = plain[0].copy()
-    g.white |= g.black & -g.black
-    special.append(g)
-    expect.append((0, -5))
-    if bs == 6:
-        for bit, col in ((36, "black"), (63, "white")):
-            g = plain[1].copy()
-            setattr(g, col, getattr(g, col) | 1 << bit)
-            special.append(g)
-            expect.append((0, -5))
-    for side in (0, 3, -1):
-        g = plain[2].copy()
-        g.side = side
-        special.append(g)
-        expect.append((0, -5))
-    mixed, where = [], {}
-    for i, g in enumerate(plain):
-        mixed.append(g)
-        if i < len(special):
-            where[len(mixed)] = i
-            mixed.append(special[i])
-    for j in range(len(plain), len(special)):
-        where[len(mixed)] = j
-        mixed.append(special[j])
-    score, move, nodes = gpu_window(mixed, bs, -1, 1, order, max_empties=6)
-    keep = [i for i in range(len(mixed)) if i not in where]
+    c = R.RootCases(bs, seeds)
+    want = gpu_window(c.plain, bs, -1, 1, order)
+    score, move, nodes = gpu_window(c.mixed, bs, -1, 1, order, max_empties=6)
     for got, w in zip((score, move, nodes), want):
-        assert np.array_equal(got[keep], w)
-    for i, j in where.items():
-        es, em = expect[j]
+        assert np.array_equal(got[c.keep], w)
+    for i, j in c.where.items():
+        es, em, ends = c.expect[j]
         assert move[i] == em, (j, move[i], em)
-        if es is None:
-            v = R.negamax(mixed[i], bs)[0]
-            W.check_result(mixed[i], bs, -1, 1, v, score[i], move[i])
-            if order == 0:
-                assert (score[i], move[i], nodes[i]) == W.window_ab(mixed[i], bs, -1, 1)
-        else:
+        if ends:
             assert score[i] == es, (j, score[i], es)
+        else:       # a pass that does not end the game: fail-soft in (-1, 1)
+            W.check_result(c.mixed[i], bs, -1, 1, es, score[i], move[i])
+            if order == 0:
+                assert (score[i], move[i], nodes[i]) == W.window_ab(c.mixed[i], bs, -1, 1)
         assert (nodes[i] == 0) if move[i] in (-3, -5) else (nodes[i] >= 1)
-    full = (1 << nsq) - 1
-    g_full = R.O.Game(full & 0x5555555555555555, full & 0xAAAAAAAAAAAAAAAA, 1, 0, -1, 0)
-    s0, m0, _ = gpu_window([g_full, over, plain[0]] + pass_roots(bs, seeds), bs, -1, 1, order,
-                           max_empties=0)
-    hs, hm, _ = R.negamax(g_full, bs)
-    assert hm == -1 and (s0[0], m0[0]) == (hs, nsq)
-    assert (s0[1], m0[1]) == (R.discs_diff(over), -2)
-    assert list(m0[2:]) == [-3] * (1 + len(seeds)) and not s0[2:].any()
+    s0, m0, _ = gpu_window(c.zero, bs, -1, 1, order, max_empties=0)
+    c.check_zero(bs, s0, m0)
 
 
 def test_batch_shape_independence():
@@ -271,7 +203,7 @@ def test_api_errors():
     lib = rvz.load()
     EINVAL = -22
     games = [R.position(s, 6, 8)[0] for s in range(4)]
-    b, w, st = to_gpu(games)
+    b, w, st = R.to_device(games)
     sc = torch.full((4,), 77, dtype=torch.int32, device="cuda")
     mv = torch.full((4,), 77, dtype=torch.int32, device="cuda")
     nd = torch.full((4,), 77, dtype=torch.int64, device="cuda")
@@ -314,7 +246,7 @@ def test_api_errors():
 def test_engine_solve_wld():
     import rvz
     games = [R.position(s, 6, 8)[0] for s in range(16)]
-    b, w, st = to_gpu(games)
+    b, w, st = R.to_device(games)
     eng = rvz.Engine(16, num_simulations=16, batch_size=16, device="cuda:0")
     eng.set_state(b, w, st)
     before = [t.clone() for t in eng.get_state()]
