@@ -1,5 +1,6 @@
 // rvz_solve.hip — exact endgame solver: batched negamax over the reference's rules for gfx950
-// (MI355X), exported as rvz_solve and rvz_solve_window (include/rvz.h). Its own translation unit:
+// (MI355X), exported as rvz_solve, rvz_solve_window and rvz_solve_moves (include/rvz.h). Its own
+// translation unit:
 // the code objects of rvz_engine.hip (k_play, k_step, k_act) do not depend on it.
 //
 // Definition (DESIGN.md §Exact endgame solver): solve(g) = the disc difference at the end of the
@@ -33,10 +34,27 @@
 // the first-maximum move equal the unpruned definition (DESIGN.md has the argument). Node counts
 // depend on the row alone.
 //
-// One machine, two kernels: solve_rows<BS, WIN> is the loop; k_solve is WIN = false and
-// k_solve_window is WIN = true. WIN switches three things: the root window (the caller's
-// (walpha, wbeta), negated under a pass root, instead of (-SINF, SINF)), the fail-low move code
-// -6 at the root, and move ordering (below). With WIN = false those are compiled out.
+// One machine, three kernels: solve_rows<BS, MODE> is the loop; k_solve is MODE_FULL,
+// k_solve_window MODE_WINDOW and k_solve_moves MODE_MOVES. WIN (both MODE_WINDOW and MODE_MOVES)
+// switches three things: the root window (the caller's (walpha, wbeta), negated under a pass
+// root, instead of (-SINF, SINF)), the fail-low move code -6 at the root, and move ordering
+// (below). With MODE_FULL those are compiled out.
+//
+// MODE_MOVES (rvz_solve_moves: the value of every root move) changes the intake and nothing
+// below it. The unit a lane takes from the counter is a task (row, j), j < max(1, max_empties)
+// >= the row's legal squares: task r is row r % rows, j = r / rows, so every row's first move
+// comes before any row's second: neighbouring lanes read neighbouring rows, the tasks that have
+// a move are taken first, and the ones that have none (high j) fall where the launch drains.
+// Task j of a root with k legal squares makes the move to the j-th set bit of its legal mask
+// (j < k) exactly as an open node commits a move, and the child, after its auto-pass never a pass
+// root, becomes the lane's depth-0 node: the window negated and the negate flag set when the side
+// changed, the caller's window when the child kept the side; a child that ends the game is scored
+// in place. The depth-0 return writes that one entry, out_score[row][square], and nothing else.
+// A task with j >= k has no move: its lane reads the row, finds that out and asks for the next
+// task in the wave's next iteration. Task 0 of every row, which always exists, also writes the
+// row's out_count and NOT_A_MOVE / 0 into every entry no task of the row owns (the squares
+// outside the legal mask, and the pass entry unless the root is a pass root, which task 0 then
+// solves as k_solve_window does and writes itself). So every element has exactly one writer.
 //
 // Ordering (WIN only): at nodes with at least `order_min` empty squares, the untried move whose
 // child leaves the side to move there the fewest legal squares is tried first. It re-scans the
@@ -75,20 +93,26 @@ __device__ unsigned int g_next_row[SLOTS];
 
 __global__ void k_solve_zero(int slot) { g_next_row[slot] = 0u; }
 
-// The state machine of both kernels (the head of the file has what WIN switches); walpha, wbeta
-// and order_min are read only when WIN.
-template <int BS, bool WIN>
+enum { MODE_FULL = 0, MODE_WINDOW = 1, MODE_MOVES = 2 };
+
+// The state machine of the three kernels (the head of the file has what the modes switch);
+// walpha, wbeta and order_min are read only when WIN. MODE_MOVES: n counts tasks over `rows`
+// rows; out_score and out_nodes are [rows][NSQ + 1] and out_move is out_count.
+template <int BS, int MODE>
 __device__ __forceinline__ void solve_rows(
-    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
+    int n, int rows, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
     const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
     int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
     long long* __restrict__ out_nodes, int slot) {
+    constexpr bool WIN = MODE != MODE_FULL, MOVES = MODE == MODE_MOVES;
     constexpr int NSQ = Geo<BS>::NSQ;
     constexpr uint64_t FULL = Geo<BS>::FULL;
     __shared__ uint32_t stk[FRAMES * FIELDS * SOLVE_THREADS];
     uint32_t* const my = stk + threadIdx.x;        // field f of depth d: my[(d * FIELDS + f) * T]
 
     bool active = false, exhausted = false;
+    // row: where emit writes (MOVES: the entry's index in out_score / out_nodes); rootpass: the
+    // depth-0 node is the other side's, its score is negated (MOVES: also a child that moved on)
     int row = 0, depth = 0, alpha = 0, beta = 0, best = 0, bestsq = 0, rootpass = 0;
     uint64_t P = 0, O = 0, rem = 0;
     long long nodes = 0;
@@ -97,8 +121,12 @@ __device__ __forceinline__ void solve_rows(
     int csq = 0, ckey = 0;
 
     auto emit = [&](int score, int move, long long cnt) {
-        out_score[row] = score;
-        out_move[row] = move;
+        if constexpr (MOVES) {
+            out_score[row] = move == -4 ? RVZ_SOLVE_ABANDONED : score;
+        } else {
+            out_score[row] = score;
+            out_move[row] = move;
+        }
         if (out_nodes) out_nodes[row] = cnt;
         active = false;
     };
@@ -110,7 +138,13 @@ __device__ __forceinline__ void solve_rows(
             if (r >= (unsigned)n) {
                 exhausted = true;
             } else {
-                row = (int)r;
+                // MOVES: task r is (row src, j); code is the row's out_count, own the legal
+                // mask of a root with moves: the entries the row's other tasks write
+                const int j = MOVES ? (int)(r / (unsigned)rows) : 0;
+                const int src = MOVES ? (int)(r - (unsigned)j * (unsigned)rows) : (int)r;
+                int code = 0;
+                uint64_t own = 0;
+                row = src;
                 const uint64_t b = black[row], w = white[row];
                 const int side = status[4 * row], over = status[4 * row + 1];
                 const int passed = status[4 * row + 3];
@@ -118,16 +152,49 @@ __device__ __forceinline__ void solve_rows(
                 O = side == 1 ? w : b;
                 const int diff = __popcll(P) - __popcll(O);
                 if ((b & w) || ((b | w) & ~FULL) || (side != 1 && side != 2)) {
-                    emit(0, -5, 0);
+                    if constexpr (MOVES) code = -5;
+                    else emit(0, -5, 0);
                 } else if (over) {
-                    emit(diff, -2, 1);
+                    if constexpr (MOVES) code = -2;
+                    else emit(diff, -2, 1);
                 } else if (__popcll(~(b | w) & FULL) > max_empties) {
-                    emit(0, -3, 0);
+                    if constexpr (MOVES) code = -3;
+                    else emit(0, -3, 0);
                 } else {
                     uint64_t M = legal<BS>(P, O);
                     rootpass = 0;
                     nodes = 1;
-                    if (!M) {
+                    bool mine = true;              // MOVES: the task has an entry to settle
+                    if constexpr (MOVES) {
+                        own = M;
+                        code = M ? __popcll(M) : 1;
+                        mine = j < code;
+                        row = src * (NSQ + 1) + NSQ;        // a pass root's entry
+                        if (M && mine) {
+                            // the move to the j-th legal square, as an open node commits one;
+                            // its child is this lane's depth-0 node
+                            uint64_t m = M;
+                            for (int i = 0; i < j; ++i) m &= m - 1;
+                            const int sq = __builtin_ctzll(m);
+                            row = src * (NSQ + 1) + sq;
+                            const uint64_t f = flips<BS>(sq, P, O);
+                            const uint64_t nP = P ^ ((1ull << sq) | f), nO = O ^ f;
+                            M = legal<BS>(nO, nP);
+                            if (M) {               // the other side moves: negated, like a pass
+                                P = nO; O = nP;
+                                rootpass = 1;
+                            } else {               // auto-pass: the root's side keeps the move
+                                P = nP; O = nO;
+                                M = legal<BS>(nP, nO);
+                                if (!M) {          // the move ends the game
+                                    emit(__popcll(nP) - __popcll(nO), 0, 1);
+                                    mine = false;
+                                }
+                            }
+                        }
+                        if (!mine) M = 0;
+                    }
+                    if (!M && mine) {
                         // the root's only move is the pass (make_move<BS>(g, -1)): the side
                         // flips, passed + 1; two passes in a row end the game
                         const uint64_t M2 = legal<BS>(O, P);
@@ -158,6 +225,22 @@ __device__ __forceinline__ void solve_rows(
                         }
                         best = -SINF;
                         bestsq = 0;
+                    }
+                }
+                if constexpr (MOVES) {
+                    if (j == 0) {
+                        int32_t* const os = out_score + (size_t)src * (NSQ + 1);
+                        long long* const on = out_nodes ? out_nodes + (size_t)src * (NSQ + 1) : 0;
+                        out_move[src] = code;
+                        for (int s = 0; s < NSQ; ++s)
+                            if (!((own >> s) & 1)) {
+                                os[s] = RVZ_SOLVE_NOT_A_MOVE;
+                                if (on) on[s] = 0;
+                            }
+                        if (code < 0 || own) {
+                            os[NSQ] = RVZ_SOLVE_NOT_A_MOVE;
+                            if (on) on[NSQ] = 0;
+                        }
                     }
                 }
             }
@@ -264,8 +347,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
     const int32_t* __restrict__ status, int max_empties, long long node_limit,
     int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
     long long* __restrict__ out_nodes, int slot) {
-    solve_rows<BS, false>(n, black, white, status, max_empties, node_limit, 0, 0, 0, out_score,
-                          out_move, out_nodes, slot);
+    solve_rows<BS, MODE_FULL>(n, 0, black, white, status, max_empties, node_limit, 0, 0, 0,
+                              out_score, out_move, out_nodes, slot);
 }
 
 template <int BS>
@@ -274,18 +357,31 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
     const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
     int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
     long long* __restrict__ out_nodes, int slot) {
-    solve_rows<BS, true>(n, black, white, status, max_empties, node_limit, walpha, wbeta,
-                         order_min, out_score, out_move, out_nodes, slot);
+    solve_rows<BS, MODE_WINDOW>(n, 0, black, white, status, max_empties, node_limit, walpha, wbeta,
+                                order_min, out_score, out_move, out_nodes, slot);
+}
+
+// tasks = rows * max(1, max_empties) (rvz_solve_moves checks that it fits)
+template <int BS>
+__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_moves(
+    int tasks, int rows, const uint64_t* __restrict__ black,
+    const uint64_t* __restrict__ white, const int32_t* __restrict__ status, int max_empties,
+    long long node_limit, int walpha, int wbeta, int order_min, int32_t* __restrict__ out_scores,
+    int32_t* __restrict__ out_count, long long* __restrict__ out_nodes, int slot) {
+    solve_rows<BS, MODE_MOVES>(tasks, rows, black, white, status, max_empties, node_limit,
+                               walpha, wbeta, order_min, out_scores, out_count, out_nodes, slot);
 }
 
 std::atomic<unsigned> g_slot{0};
 
-// What both entry points do before their own launch: the common argument checks (RVZ_EINVAL
+// What the entry points do before their own launch: the common argument checks (RVZ_EINVAL
 // before any HIP call), then for n > 0 the row-counter slot, the grid and the zeroing launch.
+// per_row: the units of work a row makes (1; rvz_solve_moves: its tasks per row).
 // Returns the grid size, 0 when n == 0 (nothing to launch), or a negative RVZ_E* code.
 int solve_prepare(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
                   const int32_t* status, int32_t max_empties, int64_t node_limit,
-                  const int32_t* out_score, const int32_t* out_move, hipStream_t s, int* slot) {
+                  const int32_t* out_score, const int32_t* out_move, hipStream_t s, int* slot,
+                  int per_row = 1) {
     if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
         node_limit <= 0 || (n > 0 && (!black || !white || !status || !out_score || !out_move)))
         return RVZ_EINVAL;
@@ -297,9 +393,9 @@ int solve_prepare(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* 
         return RVZ_EHIP;
     *slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
     hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, *slot);
-    const int need = (n + SOLVE_THREADS - 1) / SOLVE_THREADS;
+    const int64_t need = ((int64_t)n * per_row + SOLVE_THREADS - 1) / SOLVE_THREADS;
     const int wgs = cus * SOLVE_WG_PER_CU;
-    return need < wgs ? need : wgs;
+    return need < wgs ? (int)need : wgs;
 }
 
 }  // namespace
@@ -342,5 +438,31 @@ extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
         hipLaunchKernelGGL(k_solve_window<6>, g, block, 0, s, n, black, white, status,
                            max_empties, (long long)node_limit, alpha, beta, order_min_empties,
                            out_score, out_move, (long long*)out_nodes, slot);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}
+
+extern "C" int rvz_solve_moves(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
+                               const int32_t* status, int32_t max_empties, int64_t node_limit,
+                               int32_t alpha, int32_t beta, int32_t order_min_empties,
+                               int32_t* out_scores, int32_t* out_count, int64_t* out_nodes,
+                               void* stream) {
+    if (alpha < -64 || alpha >= beta || beta > 64 || order_min_empties < 0) return RVZ_EINVAL;
+    if ((bs == 8 || bs == 6) && n > 0 && (int64_t)n * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int per_row = max_empties > 1 ? max_empties : 1;
+    int slot = 0;
+    const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_scores,
+                                  out_count, s, &slot, per_row);
+    if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
+    dim3 g(wgs), block(SOLVE_THREADS);
+    const int tasks = n * per_row;                 // per_row <= 14 < S*S + 1: fits
+    if (bs == 8)
+        hipLaunchKernelGGL(k_solve_moves<8>, g, block, 0, s, tasks, n, black, white, status,
+                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
+                           out_scores, out_count, (long long*)out_nodes, slot);
+    else
+        hipLaunchKernelGGL(k_solve_moves<6>, g, block, 0, s, tasks, n, black, white, status,
+                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
+                           out_scores, out_count, (long long*)out_nodes, slot);
     return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }

@@ -12,11 +12,13 @@ Batched core:
     solve                   exact endgame values of a batch of positions (rvz_solve)
     solve_window, solve_wld the same within a caller's (alpha, beta) / as win, draw or loss, with
                             optional move ordering (rvz_solve_window)
+    solve_moves, solve_moves_wld   the value of every root move (rvz_solve_moves); best_moves
+                            reduces them to the proven-optimal moves of each row
 """
 from ._lib import RvzError, load  # noqa: F401
-from .engine import (Engine, action_probs, board_apply, board_canonical,  # noqa: F401
-                     board_legal, dirichlet_noise, policy_softmax, solve, solve_window,
-                     solve_wld)
+from .engine import (SOLVE_ABANDONED, SOLVE_NOT_A_MOVE, Engine, action_probs,  # noqa: F401
+                     best_moves, board_apply, board_canonical, board_legal, dirichlet_noise,
+                     policy_softmax, solve, solve_moves, solve_moves_wld, solve_window, solve_wld)
 from .game import Board, ReversiGame  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401

@@ -23,6 +23,7 @@ RVZ_OK, RVZ_DONE = 0, 1
 RVZ_LEAF_F32, RVZ_LEAF_BF16 = 0, 1
 RVZ_DRAWS = 64          # move-sampling draws held per game (rvz_env_set_draws)
 RVZ_SOLVE_MAX_EMPTIES = 14   # rvz_solve: the deepest root its per-lane stack holds
+RVZ_SOLVE_NOT_A_MOVE, RVZ_SOLVE_ABANDONED = -128, -127     # rvz_solve_moves: entries without a score
 
 
 class RvzError(RuntimeError):
@@ -88,6 +89,8 @@ SIGNATURES = {
                             _P]),
     "rvz_solve_window": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64,
                                    C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "rvz_solve_moves": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64,
+                                  C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),

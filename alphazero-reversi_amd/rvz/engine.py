@@ -23,6 +23,8 @@ from ._lib import RVZ_DONE, RVZ_LEAF_BF16, RVZ_LEAF_F32, RvzError, check, ptr
 
 U64 = 0xFFFFFFFFFFFFFFFF
 SOLVE_MAX_EMPTIES = _lib.RVZ_SOLVE_MAX_EMPTIES
+SOLVE_NOT_A_MOVE = _lib.RVZ_SOLVE_NOT_A_MOVE      # solve_moves: not a legal move of the row
+SOLVE_ABANDONED = _lib.RVZ_SOLVE_ABANDONED        # solve_moves: the move's search hit node_limit
 
 
 def to_signed64(x: int) -> int:
@@ -239,6 +241,23 @@ class Engine:
         if order_min_empties is None:
             order_min_empties = WLD_ORDER_MIN_EMPTIES
         return solve_wld(b, w, st, self.board_size, max_empties, node_limit, order_min_empties)
+
+    def solve_moves(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24,
+                    alpha: int = -64, beta: int = 64, order_min_empties: int = 0):
+        """rvz.solve_moves on the engine's current env state, as solve(): (scores, count, nodes)
+        per game, one entry per move."""
+        b, w, st = self._env_snapshot()
+        return solve_moves(b, w, st, self.board_size, max_empties, node_limit, alpha, beta,
+                           order_min_empties)
+
+    def solve_moves_wld(self, max_empties: int = SOLVE_MAX_EMPTIES, node_limit: int = 2 ** 24,
+                        order_min_empties: Optional[int] = None):
+        """rvz.solve_moves_wld on the engine's current env state, as solve_wld()."""
+        b, w, st = self._env_snapshot()
+        if order_min_empties is None:
+            order_min_empties = WLD_ORDER_MIN_EMPTIES
+        return solve_moves_wld(b, w, st, self.board_size, max_empties, node_limit,
+                               order_min_empties)
 
     def legal(self) -> torch.Tensor:
         self._stream()
@@ -597,9 +616,11 @@ def action_probs(visits: torch.Tensor, temperature, u: Optional[torch.Tensor] = 
     return idx, p, drew
 
 
-def _solve_call(name, black, white, status, board_size, max_empties, node_limit, *extra):
-    """solve / solve_window: lib.rvz_<name> on the rows, `extra` the integer arguments the entry
-    point takes between node_limit and the outputs. Every pointer is null when n == 0."""
+def _solve_call(name, black, white, status, board_size, max_empties, node_limit, *extra,
+                per_move=False):
+    """solve / solve_window / solve_moves: lib.rvz_<name> on the rows, `extra` the integer
+    arguments the entry point takes between node_limit and the outputs. per_move: the first and
+    third outputs hold S*S + 1 entries per row. Every pointer is null when n == 0."""
     lib = _lib.load()
     n = black.numel()
     if status.shape != (n, 4) or white.numel() != n:
@@ -608,9 +629,10 @@ def _solve_call(name, black, white, status, board_size, max_empties, node_limit,
     b = black.to(torch.int64).contiguous()
     w = white.to(dev, torch.int64).contiguous()
     st = status.to(dev, torch.int32).contiguous()
-    score = torch.empty(n, dtype=torch.int32, device=dev)
+    shape = (n, int(board_size) ** 2 + 1) if per_move else (n,)
+    score = torch.empty(shape, dtype=torch.int32, device=dev)
     move = torch.empty(n, dtype=torch.int32, device=dev)
-    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    nodes = torch.empty(shape, dtype=torch.int64, device=dev)
     pb, pw, pst, pscore, pmove, pnodes, stream = (
         [ptr(t) for t in (b, w, st, score, move, nodes)] + [_lib.stream_handle(dev)]
         if n else [None] * 7)
@@ -668,6 +690,59 @@ def solve_wld(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, bo
     score, move, nodes = solve_window(black, white, status, board_size, max_empties, node_limit,
                                       -1, 1, order_min_empties)
     return torch.sign(score), move, nodes
+
+
+def solve_moves(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
+                board_size: int = 8, max_empties: int = SOLVE_MAX_EMPTIES,
+                node_limit: int = 2 ** 24, alpha: int = -64, beta: int = 64,
+                order_min_empties: int = 0):
+    """rvz_solve_moves: the value of every root move of n positions, each move on a lane of its
+    own. Inputs, window and ordering as solve_window(). Returns (scores int32 [n, S*S+1], count
+    int32 [n], nodes int64 [n, S*S+1]) on the inputs' device; index S*S is the pass.
+    count >= 1: the number of legal squares (1 for a root that can only pass); the entry of a
+    legal square s is solve_window()'s score of the child make_move(root, s), seen from the
+    root's side (window and sign mapped when the side changes; a move that ends the game scores
+    its final difference), so with m the move's exact value, min(max(entry, alpha), beta) ==
+    min(max(m, alpha), beta); nodes is that child's count. SOLVE_ABANDONED marks a move whose own
+    search reached node_limit, SOLVE_NOT_A_MOVE (nodes 0) every entry that is no move of the row.
+    A pass root's one entry, at S*S, is solve_window()'s answer for the root itself.
+    count -2 (root over), -3 (above max_empties), -5 (malformed): the whole row is
+    SOLVE_NOT_A_MOVE. Moves share no bounds: each is searched with the whole window."""
+    return _solve_call("solve_moves", black, white, status, board_size, max_empties, node_limit,
+                       alpha, beta, order_min_empties, per_move=True)
+
+
+def solve_moves_wld(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
+                    board_size: int = 8, max_empties: int = SOLVE_MAX_EMPTIES,
+                    node_limit: int = 2 ** 24, order_min_empties: int = WLD_ORDER_MIN_EMPTIES):
+    """Win / draw / loss of every root move: solve_moves with the window (-1, +1), the scores
+    reduced to their sign in {-1, 0, +1} for the side to move; SOLVE_NOT_A_MOVE and
+    SOLVE_ABANDONED entries are kept. Returns (outcomes, count, nodes) as solve_moves()."""
+    scores, count, nodes = solve_moves(black, white, status, board_size, max_empties, node_limit,
+                                       -1, 1, order_min_empties)
+    return torch.where(scores <= SOLVE_ABANDONED, scores, torch.sign(scores)), count, nodes
+
+
+def best_moves(scores: torch.Tensor, count: torch.Tensor, alpha: int = -64, beta: int = 64):
+    """The proven-optimal moves of solve_moves()' rows (pure torch, CPU or GPU tensors).
+    Returns (best int32 [n], mask bool [n, S*S+1], complete bool [n]). With clamp(x) =
+    min(max(x, alpha), beta): best is the maximum of clamp over the row's solved entries, mask
+    marks the entries whose clamp equals it, complete means count >= 1 and no entry is
+    SOLVE_ABANDONED. An entry's clamp equals its move's exact value's clamp (fail-soft), so for a
+    complete row mask is exactly the set of moves optimal at the window's resolution: every best
+    move at (-64, 64), every move of the best win / draw / loss class at (-1, 1). Rows that are
+    not complete get best 0 and an all-false mask. alpha, beta: the window of the solve_moves()
+    call (solve_moves_wld: -1, 1)."""
+    if not -64 <= alpha < beta <= 64:
+        raise RvzError("best_moves: the window must satisfy -64 <= alpha < beta <= 64")
+    scores = scores.to(torch.int32)
+    solved = scores > SOLVE_ABANDONED
+    complete = (count >= 1) & ~(scores == SOLVE_ABANDONED).any(dim=1)
+    clamped = torch.where(solved, scores.clamp(alpha, beta), torch.full_like(scores, -65))
+    best = clamped.max(dim=1).values
+    mask = solved & (clamped == best.unsqueeze(1)) & complete.unsqueeze(1)
+    best = torch.where(complete, best, torch.zeros_like(best))
+    return best, mask, complete
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

@@ -40,7 +40,8 @@ class SelfPlayTrainer:
                  table_slots: Optional[int] = None, table_discs: int = 14,
                  root_noise=None, temperature_schedule=None, exact_endgame: int = 0,
                  exact_node_limit: int = 2 ** 24, exact_wld: bool = False,
-                 adjudicate_empties: int = 0, adjudicate_node_limit: int = 2 ** 24):
+                 adjudicate_empties: int = 0, adjudicate_node_limit: int = 2 ** 24,
+                 exact_policy: int = 0):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -51,6 +52,11 @@ class SelfPlayTrainer:
         exact_node_limit positions), not from the outcome of the game as played. Self-play itself
         is unchanged. exact_wld: those targets by the win / draw / loss solve (rvz.solve_wld), the
         same values from a smaller search.
+        exact_policy: 0 (off) or N in [1, 14]: the policy targets of the records with at most N
+        empty squares become uniform over the moves the per-move endgame solver proves optimal
+        (records_to_training; rvz_solve_moves with exact_node_limit per move, at the window
+        (-1, 1) with exact_wld), not the MCTS visit distribution. Independent of exact_endgame;
+        with adjudication on, the rows are those of the shortened games.
         adjudicate_empties: 0 (off) or N in [1, 14], N < S*S - 4: endgame adjudication. Self-play
         stops after S*S - 4 - N plies, where every unfinished game holds exactly N empty squares
         (every committed ply places one disc), and each such game's outcome is the win / draw /
@@ -70,6 +76,9 @@ class SelfPlayTrainer:
         self.games, self.seed = int(games), int(seed)
         self.exact_endgame, self.exact_node_limit = int(exact_endgame), int(exact_node_limit)
         self.exact_wld = bool(exact_wld)
+        self.exact_policy = int(exact_policy)
+        if not 0 <= self.exact_policy <= SOLVE_MAX_EMPTIES:
+            raise ValueError(f"exact_policy must be in [0, {SOLVE_MAX_EMPTIES}]")
         self.adjudicate_empties = int(adjudicate_empties)
         self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
@@ -136,7 +145,7 @@ class SelfPlayTrainer:
                                    run.rec_p, run.post_status, self.eng.board_size,
                                    exact_endgame=self.exact_endgame,
                                    exact_node_limit=self.exact_node_limit,
-                                   exact_wld=self.exact_wld)
+                                   exact_wld=self.exact_wld, exact_policy=self.exact_policy)
 
     def _adjudicated(self, plies: int) -> Dict[str, torch.Tensor]:
         """generate()'s tail with adjudication on: the games stand after `plies` plies."""
@@ -156,7 +165,7 @@ class SelfPlayTrainer:
                                   run.rec_side[:plies], rec_idx, run.rec_p[:plies], final,
                                   eng.board_size, exact_endgame=self.exact_endgame,
                                   exact_node_limit=self.exact_node_limit,
-                                  exact_wld=self.exact_wld)
+                                  exact_wld=self.exact_wld, exact_policy=self.exact_policy)
         out.update(stats)
         return out
 
@@ -189,6 +198,8 @@ class SelfPlayTrainer:
                     "samples": int(data["states"].shape[0]),
                     "exact_rows": int(data.get("exact_rows", 0)),
                     "exact_unsolved": int(data.get("exact_unsolved", 0)),
+                    "exact_policy_rows": int(data.get("exact_policy_rows", 0)),
+                    "exact_policy_unsolved": int(data.get("exact_policy_unsolved", 0)),
                     "adjudicated": int(data.get("adjudicated", 0)),
                     "adjudicate_unsolved": int(data.get("adjudicate_unsolved", 0)),
                     "already_over": int(data.get("already_over", 0))})

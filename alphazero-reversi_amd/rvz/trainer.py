@@ -22,14 +22,16 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .engine import SOLVE_MAX_EMPTIES, board_canonical, solve, solve_wld
+from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
+                     solve_moves, solve_moves_wld, solve_wld)
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
                         rec_idx: torch.Tensor, rec_p: torch.Tensor, final_status: torch.Tensor,
                         board_size: int = 8, canonical=None, exact_endgame: int = 0,
                         solver=None, exact_node_limit: int = 2 ** 24,
-                        exact_wld: bool = False) -> Dict[str, torch.Tensor]:
+                        exact_wld: bool = False, exact_policy: int = 0,
+                        moves_solver=None) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -49,6 +51,19 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     exact_wld = True: the default solver is rvz.solve_wld (rvz_solve_window with the window
     (-1, +1)) instead: the same targets, since only the sign is kept, from a smaller search;
     exact_rows / exact_unsolved can differ only through the node limit.
+    exact_policy = N > 0 (independent of exact_endgame): every kept record with at most N empty
+    squares whose every move the per-move solver decides (rvz.best_moves' `complete`) gets the
+    policy target mask / mask.sum(), float32: uniform over the proven-optimal moves (the pass
+    index for a root that can only pass), so its argmax, which DDPTrainer trains on, is the
+    lowest-index optimal move. Rows above N, and rows with an abandoned move, keep their MCTS
+    target bit for bit; states and value targets are untouched. Two more keys then, 0-d int64
+    (no host synchronisation): "exact_policy_rows", the rows replaced, and
+    "exact_policy_unsolved", the rows within N with an abandoned move. N = 0 (the default) is
+    off: the keys and bytes of before.
+    moves_solver(black, white, status, board_size, max_empties) -> (scores, count, ...): default
+    rvz.solve_moves (the rvz_solve_moves HIP kernel) at the full window, or with exact_wld
+    rvz.solve_moves_wld and the window (-1, 1) (optimal then means: of the best win / draw / loss
+    class), both with node_limit = exact_node_limit. A replacement is read at that same window.
     """
     if canonical is None:
         canonical = board_canonical
@@ -77,6 +92,18 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
         out["value_targets"] = torch.where(solved.reshape(-1, 1), exact, out["value_targets"])
         out["exact_rows"] = solved.sum()
         out["exact_unsolved"] = (move == -4).sum()
+    if exact_policy:
+        if moves_solver is None:
+            def moves_solver(b, w, s, bs, me):
+                return (solve_moves_wld if exact_wld else solve_moves)(b, w, s, bs, me,
+                                                                      exact_node_limit)
+        scores, count = moves_solver(black, white, st, board_size, int(exact_policy))[:2]
+        scores, count = scores.to(policy.device), count.to(policy.device)
+        mask, complete = best_moves(scores, count, *((-1, 1) if exact_wld else (-64, 64)))[1:]
+        exact = mask.to(torch.float32) / mask.sum(dim=1, keepdim=True).clamp(min=1)
+        out["policy_targets"] = torch.where(complete.unsqueeze(1), exact, policy)
+        out["exact_policy_rows"] = complete.sum()
+        out["exact_policy_unsolved"] = ((count >= 1) & (scores == SOLVE_ABANDONED).any(dim=1)).sum()
     return out
 
 

@@ -323,6 +323,42 @@ int rvz_solve_window(int32_t board_size, int32_t n, const uint64_t *black, const
                      const int32_t *status, int32_t max_empties, int64_t node_limit,
                      int32_t alpha, int32_t beta, int32_t order_min_empties,
                      int32_t *out_score, int32_t *out_move, int64_t *out_nodes, void *hip_stream);
+/* The value of every root move (kernel k_solve_moves): per row, rvz_solve_window of each child.
+ * Everything not stated here is rvz_solve_window's: the rules, the row layout, the in-kernel
+ * validation, alpha / beta / order_min_empties, asynchronous and graph-capturable, and the 32 row
+ * counters, which the three calls share. out_scores int32 [n][S*S+1], out_count int32 [n],
+ * out_nodes (nullable) int64 [n][S*S+1]; index S*S is the pass.
+ * A root that is not over and has k >= 1 legal squares: out_count = k, and for each legal square
+ * s, with c = make_move(root, s) (auto-pass and game end inside, as everywhere):
+ *   c is over: out_scores[s] = the final disc difference from the root's side, out_nodes[s] = 1;
+ *   otherwise the entry is rvz_solve_window's answer for c as a row with the same max_empties,
+ *   node_limit and order_min_empties: window (alpha, beta) and its score when c kept the root's
+ *   side (auto-pass), window (-beta, -alpha) and its score negated when the side changed;
+ *   out_nodes[s] is that call's count. A child that call abandons (-4) gives out_scores[s] =
+ *   RVZ_SOLVE_ABANDONED with its out_nodes; node_limit bounds every move on its own.
+ * So with m the move's exact value in the root's terms every entry r is fail-soft:
+ *   alpha < m < beta: r == m;   m <= alpha: m <= r <= alpha;   m >= beta: beta <= r <= m,
+ * and min(max(r, alpha), beta) == min(max(m, alpha), beta). Moves share no bounds: each is
+ * searched with the caller's whole window. Every other entry of the row, the pass included, is
+ * RVZ_SOLVE_NOT_A_MOVE with out_nodes 0.
+ * A pass root (not over, no legal square): out_count = 1, entry S*S holds rvz_solve_window's
+ * score and nodes for the root itself (RVZ_SOLVE_ABANDONED for its -4), every square is
+ * RVZ_SOLVE_NOT_A_MOVE.
+ * Row codes in out_count, the whole row RVZ_SOLVE_NOT_A_MOVE with nodes 0: -2 the root is over,
+ * -3 more than max_empties empty squares, -5 malformed row.
+ * The call writes every element of the three outputs for all n rows (no pre-fill needed), each
+ * from exactly one lane. A row's outputs depend on the row, the arguments and the build alone,
+ * not on n, the row's index, its neighbours or the launch geometry. The unit of work a lane takes
+ * is one root move, so a row's moves are searched side by side.
+ * RVZ_EINVAL (before any HIP call) as rvz_solve_window (out_scores and out_count taking the place
+ * of out_score and out_move), and when n * (S*S + 1) does not fit in int32. n = 0 returns RVZ_OK
+ * without a launch. */
+#define RVZ_SOLVE_NOT_A_MOVE (-128)
+#define RVZ_SOLVE_ABANDONED (-127)
+int rvz_solve_moves(int32_t board_size, int32_t n, const uint64_t *black, const uint64_t *white,
+                    const int32_t *status, int32_t max_empties, int64_t node_limit,
+                    int32_t alpha, int32_t beta, int32_t order_min_empties, int32_t *out_scores,
+                    int32_t *out_count, int64_t *out_nodes, void *hip_stream);
 
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
