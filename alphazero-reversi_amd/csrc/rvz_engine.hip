@@ -498,7 +498,8 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
                                              uint32_t carry,
                                              XT* __restrict__ leaf_x, int32_t* __restrict__ need,
                                              unsigned long long& ab,
-                                             uint64_t* leaf_bits = nullptr) {
+                                             uint64_t* leaf_bits = nullptr,
+                                             bool unread = false) {
     constexpr int NSQ = Geo<BS>::NSQ;
     Node* nodes = v.nodes + (size_t)g * v.M;
     uint32_t* meta = v.meta + (size_t)g * v.M;
@@ -662,6 +663,18 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
                 if (rn >= 0) root_n = rn;
                 break;
             }
+            if (unread && depth == 1 && parent_n == 0) {
+                // k_play's unread row: a fresh child of a root with at least as many legal moves
+                // as the search has batches after the first. Every one of those batches goes
+                // whole to the next unvisited child (N == 0 scores inf, mcts.py:96-97), so no
+                // selection of this search reads the child's value or its children's priors, and
+                // the tree is dropped after the act: the visits alone are backed up
+                // (backup_visits_only's arithmetic, now; lane 0 the root, lane 1 the child) and
+                // no row is queued. pend stays 0 (the caller's expand cleared it).
+                if (lane <= 1) nodes[path_reg].n += remaining;
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                return -1;
+            }
             WT_NOW(tl0);
             // the leaf's position: the path's moves on the root's game (a truncated path, an
             // error already flagged, replays its first PATH_CAP - 1 moves)
@@ -721,7 +734,7 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
         v.plen[g] = plen;
     }
     ab += 12;
-    return copies;   // the queued copies of the batch's NN row (0: no row)
+    return copies;   // the queued copies of the batch's NN row (0: no row; -1: a row left unread)
 }
 
 // One search round: the previous batch's expand + backup (when a submit is pending), then the
@@ -2136,6 +2149,7 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
     pa.tmask = 0;
     pa.tmaxd = 0;
     pa.tstats = reinterpret_cast<unsigned long long*>(a->table_stats);
+    pa.unread = reinterpret_cast<unsigned long long*>(a->rows_unread);
     pa.rec_black = a->rec_black;
     pa.rec_white = a->rec_white;
     pa.rec_side = a->rec_side;

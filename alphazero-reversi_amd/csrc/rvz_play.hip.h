@@ -14,7 +14,9 @@
 //    code of k_resnet_h2) and 16-board passes of the FC heads (heads_fc16, as k_heads_mfma).
 // Each per-game computation is the one the unfused launches make, and an h2 row's outputs depend
 // only on its position (test_h2_live_rows), so the games are bit-identical to SelfPlayRunner's
-// (tests/test_gpu_play.py). Inside a ply there is no kernel boundary, launch ramp or tail: the
+// (tests/test_gpu_play.py). One exception changes rows, not games: with skip_last a search whose
+// root has at least E - 1 legal moves evaluates the root's row only (the unread rows, DESIGN
+// §2.13; tests/test_gpu_unread_rows.py). Inside a ply there is no kernel boundary, launch ramp or tail: the
 // two workgroups on a CU overlap one's search phase with the other's trunk passes.
 
 struct PlayArgs {
@@ -47,6 +49,7 @@ struct PlayArgs {
     unsigned tmask;             // slots - 1
     int tmaxd;                  // positions with at most this many discs are looked up / stored
     unsigned long long* tstats; // += {hits, inserts}, or null
+    unsigned long long* unread; // += the rows left unread (k_play's unread rule), or null
     // self-play records (or null): the position before each committed act and its policy vector,
     // [plies][G] (rec_p [plies][G][NPOL]); hist holds the act's index
     uint64_t* rec_black;
@@ -384,9 +387,10 @@ void k_play(PlayCtx ctx0) {
         task_plies = queue ? 1 : c.a.plies;
     }
     bool ovf = false;
-    // the workgroup's rows, table hits and inserts, in LDS (no registers held across the phases)
-    __shared__ unsigned s_cnt[3];
-    if (tid < 3) s_cnt[tid] = 0u;
+    // the workgroup's rows, table hits, inserts and unread rows, in LDS (no registers held across
+    // the phases)
+    __shared__ unsigned s_cnt[4];
+    if (tid < 4) s_cnt[tid] = 0u;
     if (tid == 0) {
         const PlayArgs& a = play_ctx().a;
         s_tgen = a.tab ? __hip_atomic_load(a.tgen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -504,10 +508,17 @@ void k_play(PlayCtx ctx0) {
                             FT_ADD(0, ft_e);
                         }
                         const int bsz = min(a.B, a.S - k * a.B);
+                        // the unread rows (with skip_last): a root with at least
+                        // E - 1 legal moves gives each batch after the first a fresh child, whose
+                        // row no selection reads. The root's own row (batch 0) is evaluated.
+                        const bool unread = a.skip_last && !first && m_nchild(root_meta) >= E - 1;
                         const int copies = select_phase<BS, float>(v, g, lane, first, bsz, k, root,
                                                                    root_meta, root_n, carry, a.x,
-                                                                   a.need, ab, st_bits + 3 * j);
+                                                                   a.need, ab, st_bits + 3 * j,
+                                                                   unread);
                         ++k;
+                        // (a last batch's row is the deferred one with or without the rule)
+                        if (copies < 0 && k < E && lane == 0) atomicAdd(&s_cnt[3], 1u);
                         // the last batch's row with skip_last: left unevaluated (rvz_search_skip)
                         if (copies > 0 && !(k == E && a.skip_last)) {
                             if (a.tab) {   // an earlier evaluation of this position: no new row
@@ -716,4 +727,6 @@ void k_play(PlayCtx ctx0) {
         if (s_cnt[1]) atomicAdd(ts, (unsigned long long)s_cnt[1]);
         if (s_cnt[2]) atomicAdd(ts + 1, (unsigned long long)s_cnt[2]);
     }
+    unsigned long long* un = play_ctx().a.unread;
+    if (un && tid == 0 && s_cnt[3]) atomicAdd(un, (unsigned long long)s_cnt[3]);
 }

@@ -281,6 +281,9 @@ class Engine:
             self.play_rows = torch.zeros(1, dtype=torch.int64, device=self.device)
             # {table hits, table inserts} of play() calls (rvz_play_table)
             self.table_stats = torch.zeros(2, dtype=torch.int64, device=self.device)
+            # rows play() left unread (skip_last_eval: searches whose batches after the first
+            # each go to a fresh root child)
+            self.play_unread = torch.zeros(1, dtype=torch.int64, device=self.device)
         n = self.lib.rvz_play_scratch_size(self._h)
         sc = getattr(self, "_play_scratch", None)
         if sc is None or sc.numel() < n:
@@ -355,7 +358,7 @@ class Engine:
                           hist.data_ptr() if hist is not None else None,
                           self.play_rows.data_ptr(),
                           budget.data_ptr() if budget is not None else None,
-                          self.table_stats.data_ptr(), *rec)
+                          self.table_stats.data_ptr(), *rec, self.play_unread.data_ptr())
         self._stream()
         self._call("rvz_play", C.byref(a))
 

@@ -378,7 +378,11 @@ typedef struct rvz_play_args {
     float *scratch;              /* rvz_play_scratch_size(e) floats, 16-byte aligned */
     float *ovf;                  /* the evaluator's sticky f16-overflow word (set to 1), nullable */
     int32_t plies;               /* plies every game commits in this call, >= 1 */
-    int32_t skip_last_eval;      /* each search's last batch unevaluated (rvz_search_skip) */
+    int32_t skip_last_eval;      /* each search's last batch unevaluated (rvz_search_skip), and
+                                    no row for a search's batches after the first when its root
+                                    has at least as many legal moves as there are such batches:
+                                    each goes whole to a fresh child (N == 0 scores inf,
+                                    mcts.py:96-97), so nothing reads those rows. Same games. */
     int32_t reset;               /* finished games restart (rvz_env_autoreset's reset) */
     int32_t games_per_workgroup; /* > 0: static schedule, each workgroup owns that many games for
                                     every ply; <= 0: task queue, the workgroups draw (group of
@@ -405,6 +409,10 @@ typedef struct rvz_play_args {
     uint64_t *rec_white;
     int32_t *rec_side;           /* int32 [plies][n_games] */
     double *rec_p;
+    int64_t *rows_unread;        /* int64 [1] += the rows the call left unread (skip_last_eval: the
+                                    child rows of searches whose root has at least as many legal
+                                    moves as batches after the first; their last batch's row, which
+                                    skip_last_eval defers anyway, is not counted), nullable */
 } rvz_play_args;
 /* A task-queue wait that times out (a workgroup waiting for its group's previous ply, bounded
  * spin) sets device error bit 16 (rvz_check): the other workgroups then stop drawing tasks and the
