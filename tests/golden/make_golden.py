@@ -7,6 +7,9 @@ Run in the build container only (the reference never travels to the GPU box):
 Outputs (all plain npz, no pickles):
   board_vectors.npz   F-board: seeded random-playout positions -> reference legal mask, and one
                       make_move per position (legal, illegal or pass) -> resulting state + bool.
+  board_vectors_synthetic.npz  the same record on synthetic positions that no playout reaches
+                      (tests/synthetic_positions.py): explicit passes, sparse, one-colour, empty
+                      and full boards, long wrapping runs.
   mcts_<tag>.npz      F-mcts:  full reference games (src/mcts/mcts.py get_action_probs driving
                       src/game/game.py), every NN call recorded (leaf planes as bitmasks, the
                       reference's own softmax row and value), every ply's visits / p / action.
@@ -96,6 +99,62 @@ def make_board_vectors(n_games: int = 300, seed: int = 1234):
         black_after=u64(post, 0), white_after=u64(post, 1), side_after=i32(post, 2),
         passed_after=i32(post, 3), over_after=i32(post, 4), winner_after=i32(post, 5))
     print(f"board_vectors: {len(pre)} positions")
+
+
+def make_synthetic_vectors(seed: int = 2718):
+    """board_vectors_synthetic.npz: board_vectors.npz's keys plus `kind`, on the positions of
+    tests/synthetic_positions.py (states no playout reaches: the mover without a legal square,
+    one colour absent, empty and full boards, long wrapping runs), each set directly on a fresh
+    reference game (board.black / white / current_player / passed_moves_in_a_row and the
+    ReversiGame mirrors); get_valid_moves() and one make_move per row, as make_board_vectors."""
+    ReversiGame, _, _ = _import_reference()
+    tests = os.path.dirname(OUT)
+    for p in (tests, os.path.dirname(tests)):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import synthetic_positions as SP
+
+    def placed(black, white, side, passed):
+        game = ReversiGame()
+        b = game.board
+        b.black, b.white = black, white
+        b.current_player = game.current_player = side
+        b.passed_moves_in_a_row = passed
+        b.game_over = game.game_over = False
+        b.winner = game.winner = None
+        b._update_board_state()
+        return game
+
+    def state(game):
+        b = game.board
+        return (b.black, b.white, game.current_player, int(b.passed_moves_in_a_row),
+                int(game.game_over), -1 if game.winner is None else int(game.winner))
+
+    def legal_fn(P, Q):        # the mask of the side holding P: put it to move as BLACK
+        return _mask(placed(P, Q, 1, 0).get_valid_moves())
+
+    kind, pre, legal, mv, ok, post = [], [], [], [], [], []
+    for k, black, white, side, passed, sq in SP.rows(8, seed, legal_fn):
+        game = placed(black, white, side, passed)
+        pre.append(state(game))
+        legal.append(_mask(game.get_valid_moves()))
+        res = game.make_move(*(divmod(sq, 8) if sq >= 0 else (-1, -1)))
+        kind.append(k); mv.append(sq); ok.append(int(res)); post.append(state(game))
+    u64 = lambda rows, i: np.array([r[i] for r in rows], dtype=np.uint64)  # noqa: E731
+    i32 = lambda rows, i: np.array([r[i] for r in rows], dtype=np.int32)  # noqa: E731
+    d = dict(
+        black=u64(pre, 0), white=u64(pre, 1), side=i32(pre, 2), passed=i32(pre, 3),
+        over=i32(pre, 4), winner=i32(pre, 5), legal=np.array(legal, dtype=np.uint64),
+        move=np.array(mv, dtype=np.int32), ok=np.array(ok, dtype=np.int32),
+        black_after=u64(post, 0), white_after=u64(post, 1), side_after=i32(post, 2),
+        passed_after=i32(post, 3), over_after=i32(post, 4), winner_after=i32(post, 5),
+        kind=np.array(kind, dtype=np.int32))
+    SP.check_coverage(d)
+    path = os.path.join(OUT, "board_vectors_synthetic.npz")
+    np.savez_compressed(path, **d)
+    assert os.path.getsize(path) < os.path.getsize(os.path.join(OUT, "board_vectors.npz"))
+    print(f"board_vectors_synthetic: {len(pre)} positions, "
+          + ", ".join(f"({SP.KIND_NAMES[k]}) {kind.count(k)}" for k in range(6)))
 
 
 # ---------------------------------------------------------------------------------- F-mcts
@@ -255,11 +314,13 @@ def make_elo_fixture(n_updates: int = 200, seed: int = 11):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["board", "net", "mcts", "elo"]
+    which = sys.argv[1:] or ["board", "synthetic", "net", "mcts", "elo"]
     if "elo" in which:
         make_elo_fixture()
     if "board" in which:
         make_board_vectors()
+    if "synthetic" in which:
+        make_synthetic_vectors()
     if "net" in which:
         make_net_fixture()
     runs = {"s100_t1": (2, 32, 100, [0, 1, 2, 3], 1.0),

@@ -11,11 +11,23 @@ import torch
 
 
 class OracleGames:
+    """games: the starting Game of every seed (copied), or None for the start position. A
+    starting position need not be one a game from the start reaches: at a root that is not over
+    and has no legal square the reference's search visits nothing (mcts.py:339, 567-579: the root
+    is a terminal leaf and no pass child exists), get_action_probs takes argmax of an all-zero
+    vector, square 0 (mcts.py:679-692), and make_move refuses it (board.py:178-179): the ply
+    reports index 0, draws nothing and leaves the game as it is.
+    leaf_log: one int32 [n] array per batch of the last ply(): the traversal copies waiting for
+    each game's row (0: no row for that game in that batch)."""
+
     def __init__(self, O, seeds, sims: int, temperature: float = 1.0, bs: int = 8,
-                 batch: int = 64):
+                 batch: int = 64, games=None):
         self.O, self.bs, self.S, self.T, self.B = O, bs, int(sims), float(temperature), batch
-        self.games = [O.new_game(bs) for _ in seeds]
+        self.games = [O.new_game(bs) for _ in seeds] if games is None else \
+            [g.copy() for g in games]
+        assert len(self.games) == len(seeds)
         self.mts = [O.MT(int(s)) for s in seeds]
+        self.leaf_log = []
 
     def ply(self, ev):
         """One ply of every sampled game: returns (visits int32 [n, npol], idx [n], p f64
@@ -25,11 +37,15 @@ class OracleGames:
         planes = np.stack([O.canonical(g, bs) for g in self.games])
         srch = O.Search(len(self.games), self.S, self.B, 1.0, bs=bs)
         srch.begin(self.games)
-        dev = ev.device
+        dev = getattr(ev, "device", "cuda")
+        self.leaf_log = []
         while (r := srch.step()) is not None:
+            self.leaf_log.append(r[1])
             x = torch.from_numpy(O.leaf_planes(r[0], bs)).to(dev)
             logits, value = ev(x)
-            probs = rvz.policy_softmax(logits, bs)
+            # an evaluator with outputs_probs hands over softmaxed rows (Engine.search)
+            probs = logits if getattr(ev, "outputs_probs", False) else \
+                rvz.policy_softmax(logits, bs)
             srch.submit(probs.cpu().numpy(), value.cpu().numpy())
         vis = srch.visits()
         idx, ps = [], []
@@ -40,7 +56,8 @@ class OracleGames:
                 continue
             u = self.mts[j].random_sample() if O.action_needs_draw(vis[j], self.T) else 0.0
             a, p, _ = O.action(vis[j], self.T, u)
-            assert O.make_move(g, -1 if a == bs * bs else a, bs)
+            # refused only at a root without a legal square (class docstring)
+            assert O.make_move(g, -1 if a == bs * bs else a, bs) or not vis[j].any()
             idx.append(a)
             ps.append(p)
         return vis, np.array(idx), np.stack(ps), planes

@@ -297,3 +297,89 @@ def host_solver(black, white, status, board_size, max_empties, unsolved=()):
             s, m, k = negamax(g, board_size)
             score[i], move[i], nodes[i] = s, expected_move(g, m, board_size), k
     return torch.from_numpy(score), torch.from_numpy(move), torch.from_numpy(nodes)
+
+
+# ---------------------------------------------------------------- synthetic rows (solver tests)
+SYNTHETIC_MAX_EMPTIES = 7
+
+
+@functools.lru_cache(maxsize=None)
+def _synthetic_rows(bs: int):
+    import os
+
+    import synthetic_positions as SP
+    if bs == 8:
+        path = os.path.join(os.path.dirname(__file__), "golden", "board_vectors_synthetic.npz")
+        with np.load(path) as z:
+            d = {k: z[k] for k in ("kind", "black", "white", "side", "passed")}
+        rows = [tuple(int(d[k][i]) for k in ("kind", "black", "white", "side", "passed"))
+                for i in range(len(d["kind"]))]
+    else:
+        rows = [r[:5] for r in SP.rows(bs, 314, lambda P, Q: O.legal(P, Q, bs))]
+    nsq = bs * bs
+    full = (1 << nsq) - 1
+    seen, out = set(), []
+
+    def add(black, white, side, passed):
+        for s in (side, 3 - side):
+            t = (black, white, s, 0, -1, passed)
+            if t not in seen:
+                seen.add(t)
+                out.append(t)
+
+    for kind, black, white, side, passed in rows:
+        if kind <= SP.E and nsq - SP.popcount(black | white) <= SYNTHETIC_MAX_EMPTIES:
+            add(black, white, side, passed)
+    # the fixture's densities leave 3 to 7 empties to one-colour boards only: kind (a)'s
+    # construction at those densities too, so that the synthetic batch holds real searches
+    rng = random.Random(99)
+    for e in range(3, SYNTHETIC_MAX_EMPTIES + 1):
+        for _ in range(10):
+            black = white = 0
+            for c in rng.sample(range(nsq), nsq - e):
+                if rng.random() < 0.5:
+                    black |= 1 << c
+                else:
+                    white |= 1 << c
+            add(black, white, 1, rng.choice((0, 1)))
+    for sq in (0, nsq // 2 + 1, nsq - 1):          # one colour, one square empty
+        for passed in (0, 1):
+            add(full ^ 1 << sq, 0, 1, passed)
+            add(0, full ^ 1 << sq, 1, passed)
+    return tuple(out)
+
+
+def synthetic_rows(bs: int = 8):
+    """The solver tests' synthetic batch: the rows of kinds (a) to (e) of
+    tests/synthetic_positions.py with at most SYNTHETIC_MAX_EMPTIES empty squares (8x8: the
+    committed fixture's positions; 6x6: its twin built with the oracle), each also with the other
+    side to move, duplicates dropped, plus 10 random boards at each of 3 to 7 empties (the
+    fixture's densities skip them) and the one-colour boards with one empty square."""
+    return [O.Game(*t) for t in _synthetic_rows(bs)]
+
+
+@functools.lru_cache(maxsize=None)
+def synthetic_solved(bs: int = 8):
+    """negamax of every synthetic row, computed once per session: ((score, move, nodes), ...)."""
+    return tuple(negamax(g, bs) for g in synthetic_rows(bs))
+
+
+def synthetic_kinds(bs: int = 8):
+    """Host counts over the synthetic batch: pass roots (no legal square, not over), roots where
+    the other side has none either, and roots whose best move (negamax's) flips nothing."""
+    n_pass = n_stuck = n_noflip = 0
+    for g, (_, move, _) in zip(synthetic_rows(bs), synthetic_solved(bs)):
+        P, Q = (g.black, g.white) if g.side == 1 else (g.white, g.black)
+        if O.legal(P, Q, bs) == 0:
+            n_pass += 1
+            n_stuck += O.legal(Q, P, bs) == 0
+        elif O.flips(move, P, Q, bs) == 0:
+            n_noflip += 1
+    return {"pass": n_pass, "stuck": n_stuck, "noflip": n_noflip}
+
+
+def check_synthetic_kinds(bs: int = 8):
+    got = synthetic_kinds(bs)
+    print(f"synthetic solver rows {bs}x{bs}: {len(synthetic_rows(bs))} rows, {got}")
+    assert min(got.values()) >= 10, got
+    return got

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_oracle_board import load_vectors
+import synthetic_positions as SP
+from test_oracle_board import SYNTHETIC, load_vectors
 
 pytestmark = pytest.mark.gpu
 
@@ -18,9 +19,13 @@ def _u64(t):
     return t.cpu().numpy().view(np.uint64)
 
 
-@pytest.fixture(scope="module")
-def vec():
-    return load_vectors()
+@pytest.fixture(scope="module", params=["playout", "synthetic"])
+def vec(request):
+    """board_vectors.npz (playouts from the start position) and board_vectors_synthetic.npz
+    (tests/synthetic_positions.py: states no playout reaches), both recorded from the reference."""
+    d = load_vectors() if request.param == "playout" else load_vectors(SYNTHETIC)
+    d["name"] = request.param
+    return d
 
 
 def _status(d, pre=""):
@@ -53,7 +58,7 @@ def test_apply_bit_exact(vec):
 def test_canonical_matches_oracle(vec, oracle):
     import rvz
     d = vec
-    n = 2000
+    n = min(2000, len(d["black"]))
     planes = rvz.board_canonical(_s64(d["black"][:n]), _s64(d["white"][:n]),
                                  _status(d)[:n].contiguous()).cpu().numpy()
     for i in range(0, n, 7):
@@ -65,7 +70,7 @@ def test_canonical_matches_oracle(vec, oracle):
 def test_engine_env_roundtrip_and_apply(vec):
     import rvz
     d = vec
-    n = 4096
+    n = min(4096, len(d["black"]))
     eng = rvz.Engine(n, num_simulations=64, batch_size=64)
     eng.set_state(_s64(d["black"][:n]), _s64(d["white"][:n]), _status(d)[:n].contiguous())
     np.testing.assert_array_equal(_u64(eng.legal()), d["legal"][:n])
@@ -75,6 +80,12 @@ def test_engine_env_roundtrip_and_apply(vec):
     np.testing.assert_array_equal(ok.cpu().numpy(), d["ok"][:n])
     np.testing.assert_array_equal(_u64(b), d["black_after"][:n])
     np.testing.assert_array_equal(st.cpu().numpy()[:, 0], d["side_after"][:n])
+    if d["name"] == "synthetic":
+        assert n == len(d["black"])
+        np.testing.assert_array_equal(_u64(w), d["white_after"])
+        post = st.cpu().numpy()
+        for j, k in enumerate(("side", "over", "winner", "passed")):
+            np.testing.assert_array_equal(post[:, j], d[k + "_after"])
     eng.check()
 
 
@@ -108,6 +119,52 @@ def test_board_6x6_matches_oracle(oracle):
         assert bool(okk[i]) == r
         assert (int(bb[i]), int(ww[i]), *map(int, ss[i])) == \
             (g.black, g.white, g.side, g.over, g.winner, g.passed)
+
+
+def test_synthetic_6x6_matches_oracle(oracle):
+    """The 6x6 twin of board_vectors_synthetic.npz: the same constructions (kinds (a) to (f) of
+    tests/synthetic_positions.py) on the 6-stride board, answered by the oracle (no reference
+    exists for 6x6), through rvz.board_legal / rvz.board_apply and the engine's env forms. On 6x6
+    the index-order runs of 7 to 15 wrap across three rows while legal_dir keeps the 8x8
+    construction's five steps."""
+    import rvz
+    rows = SP.rows(6, 314, lambda P, Q: oracle.legal(P, Q, 6))
+    n = len(rows)
+    assert sorted({r[0] for r in rows}) == list(range(6))
+    b = _s64([r[1] for r in rows])
+    w = _s64([r[2] for r in rows])
+    st = torch.tensor([[r[3], 0, -1, r[4]] for r in rows], dtype=torch.int32).cuda()
+    mv = torch.tensor([r[5] for r in rows], dtype=torch.int32).cuda()
+    eng = rvz.Engine(n, num_simulations=64, batch_size=64, board_size=6)
+    eng.set_state(b, w, st)
+    for x, y in zip(eng.get_state(), (b, w, st)):
+        assert torch.equal(x, y)
+    legal = _u64(rvz.board_legal(b, w, st, board_size=6))
+    np.testing.assert_array_equal(_u64(eng.legal()), legal)
+    eok = eng.apply(mv).cpu().numpy()
+    eb, ew, es = (t.cpu().numpy() for t in eng.get_state())
+    ok = rvz.board_apply(b, w, st, mv, board_size=6).cpu().numpy()
+    bb, ww, ss = _u64(b), _u64(w), st.cpu().numpy()
+    np.testing.assert_array_equal(eok, ok)
+    np.testing.assert_array_equal(eb.view(np.uint64), bb)
+    np.testing.assert_array_equal(ew.view(np.uint64), ww)
+    np.testing.assert_array_equal(es, ss)
+    eng.check()
+    passes = ended = refused = 0
+    for i, (_, black, white, side, passed, sq) in enumerate(rows):
+        P, Q = (black, white) if side == 1 else (white, black)
+        assert int(legal[i]) == oracle.legal(P, Q, 6), i
+        g = oracle.Game(black, white, side, 0, -1, passed)
+        r = oracle.make_move(g, sq, 6)
+        assert bool(ok[i]) == r, i
+        assert (int(bb[i]), int(ww[i]), *map(int, ss[i])) == \
+            (g.black, g.white, g.side, g.over, g.winner, g.passed), i
+        passes += sq == -1 and r
+        ended += sq == -1 and r and bool(g.over)
+        refused += sq == -1 and not r
+    print(f"6x6 synthetic: {n} rows, {passes} explicit passes ({ended} end the game), "
+          f"{refused} refused")
+    assert passes >= 30 and ended >= 15 and refused >= 15
 
 
 # ---- the reference's test_game.py, through the drop-in ReversiGame (rules on the GPU)

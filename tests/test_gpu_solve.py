@@ -234,3 +234,28 @@ def test_trainer_hook():
     assert r["exact_rows"] == late and r["exact_unsolved"] == 0
     r = off.run_iteration()
     assert r["exact_rows"] == 0 and r["exact_unsolved"] == 0
+
+
+@pytest.mark.parametrize("bs", [8, 6])
+def test_synthetic_rows(bs):
+    """Positions no playout reaches (solve_ref.synthetic_rows: the synthetic fixture's rows with
+    at most 7 empties, both sides to move, and the 6x6 twin): score and move equal the unpruned
+    negamax, and rvz_solve (full window, index order) visits no more positions than it."""
+    R.check_synthetic_kinds(bs)
+    games, host = R.synthetic_rows(bs), R.synthetic_solved(bs)
+    score, move, nodes = gpu_solve(games, bs, max_empties=R.SYNTHETIC_MAX_EMPTIES)
+    for i, (g, (hs, hm, hk)) in enumerate(zip(games, host)):
+        assert (score[i], move[i]) == (hs, R.expected_move(g, hm, bs)), \
+            (bs, i, g.astuple(), score[i], move[i], hs, hm)
+        assert 1 <= nodes[i] <= hk, (bs, i, g.astuple(), nodes[i], hk)
+        assert nodes[i] == W.window_ab(g, bs, -W.INF, W.INF)[2], (bs, i, g.astuple())
+    # max_empties = 0: the empty board and the one-colour boards with one empty square are not
+    # searched (-3), a full board is
+    nsq = bs * bs
+    full = (1 << nsq) - 1
+    zero = [R.O.Game(0, 0, 1, 0, -1, 0), R.O.Game(full ^ 1, 0, 2, 0, -1, 0),
+            R.O.Game(0, full ^ 1 << nsq - 1, 1, 0, -1, 1), R.O.Game(full, 0, 2, 0, -1, 0)]
+    s0, m0, k0 = gpu_solve(zero, bs, max_empties=0)
+    assert list(m0[:3]) == [-3] * 3 and not s0[:3].any() and not k0[:3].any()
+    hs, hm, hk = R.negamax(zero[3], bs)
+    assert hm == -1 and (s0[3], m0[3]) == (hs, nsq) == (-nsq, nsq) and 1 <= k0[3] <= hk

@@ -391,3 +391,23 @@ def test_trainer_exact_policy():
     assert late >= 8 and changed >= 1, (late, changed)
     assert d1["exact_policy_rows"].dim() == 0 and d1["exact_policy_unsolved"].dim() == 0
     assert int(d1["exact_policy_rows"]) == late and int(d1["exact_policy_unsolved"]) == 0
+
+
+@pytest.mark.parametrize("bs", [8, 6])
+def test_synthetic_rows(bs):
+    """Every entry of rvz_solve_moves on solve_ref.synthetic_rows (positions no playout reaches)
+    against solve_moves_ref.moves_ab, at (-64, 64) and (-1, 1)."""
+    R.check_synthetic_kinds(bs)
+    games = R.synthetic_rows(bs)
+    me = R.SYNTHETIC_MAX_EMPTIES
+    for alpha, beta in ((-64, 64), (-1, 1)):
+        want = V.stack([V.moves_ab(g, bs, alpha, beta, max_empties=me) for g in games])
+        same(gpu_moves(games, bs, alpha=alpha, beta=beta, max_empties=me), want,
+             (bs, alpha, beta))
+    nsq = bs * bs
+    empty = [R.O.Game(0, 0, 1, 0, -1, 0)]
+    scores, count, nodes = gpu_moves(empty, bs, max_empties=0)
+    assert count[0] == -3 and (scores == NOT_A_MOVE).all() and not nodes.any()
+    scores, count, nodes = gpu_moves(empty, bs, max_empties=14)
+    assert count[0] == -3                              # 36 or 64 empties: above any max_empties
+    assert scores.shape == (1, nsq + 1)

@@ -335,3 +335,23 @@ def test_adjudicated_iteration(fused):
     r = adj.run_iteration()                # iteration 0 again: the same games
     assert r["adjudicate_unsolved"] == 0 and r["adjudicated"] == int(d_adj["adjudicated"])
     assert r["already_over"] == int(d_adj["already_over"]) and r["board_steps"] <= G * K
+
+
+@pytest.mark.parametrize("order", [0, 4])
+@pytest.mark.parametrize("bs", [8, 6])
+def test_synthetic_rows(bs, order):
+    """rvz_solve_window's fail-soft contract on solve_ref.synthetic_rows (positions no playout
+    reaches, pass roots and roots where neither side can move among them) at (-1, 1) and
+    (-64, 64); with ordering off also node for node the host's search in index order."""
+    R.check_synthetic_kinds(bs)
+    games, host = R.synthetic_rows(bs), R.synthetic_solved(bs)
+    values = [W.child_values(g, bs) for g in games]
+    for alpha, beta in ((-1, 1), (-64, 64)):
+        score, move, nodes = gpu_window(games, bs, alpha, beta, order,
+                                        max_empties=R.SYNTHETIC_MAX_EMPTIES)
+        for i, g in enumerate(games):
+            W.check_result(g, bs, alpha, beta, host[i][0], score[i], move[i], values[i])
+            assert nodes[i] >= 1
+            if order == 0:
+                want = W.window_ab(g, bs, alpha, beta)
+                assert (score[i], move[i], nodes[i]) == want, (bs, alpha, beta, g.astuple(), want)

@@ -5,11 +5,13 @@ import os
 import numpy as np
 import pytest
 
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "board_vectors.npz")
+GOLDEN_DIR = os.path.join(os.path.dirname(__file__), "golden")
+GOLDEN = os.path.join(GOLDEN_DIR, "board_vectors.npz")
+SYNTHETIC = os.path.join(GOLDEN_DIR, "board_vectors_synthetic.npz")
 
 
-def load_vectors():
-    with np.load(GOLDEN) as z:     # materialise once: NpzFile re-inflates on every access
+def load_vectors(path=GOLDEN):
+    with np.load(path) as z:       # materialise once: NpzFile re-inflates on every access
         return {k: z[k] for k in z.files}
 
 
@@ -43,6 +45,27 @@ def test_make_move_matches_reference(oracle):
         n_illegal += not ok
         n_pass += int(d["move"][i]) == -1
     assert n_illegal > 100 and n_pass > 100   # the fixture covers the False paths too
+
+
+def test_synthetic_fixture_matches_reference(oracle):
+    """Every row of board_vectors_synthetic.npz (tests/synthetic_positions.py: explicit passes
+    that succeed, end the game or are refused, sparse / one-colour / empty / full boards, long
+    wrapping runs, recorded from the reference): the oracle's legal mask and make_move. The
+    fixture's coverage counts are asserted from its own arrays."""
+    import synthetic_positions as SP
+    d = load_vectors(SYNTHETIC)
+    SP.check_coverage(d)
+    assert set(load_vectors()) | {"kind"} == set(d)
+    assert sorted(set(d["kind"].tolist())) == list(range(6)) and len(d["black"]) < 5000
+    for i in range(len(d["black"])):
+        g = _game(oracle, d, i)
+        P, Q = (g.black, g.white) if g.side == 1 else (g.white, g.black)
+        assert oracle.legal(P, Q) == int(d["legal"][i]), i
+        ok = oracle.make_move(g, int(d["move"][i]))
+        exp = tuple(int(d[k][i]) for k in ("black_after", "white_after", "side_after",
+                                            "over_after", "winner_after", "passed_after"))
+        assert ok == bool(d["ok"][i]), i
+        assert g.astuple() == exp, i
 
 
 # ---- test_game.py restated (the reference's only known-answer tests for the board)
