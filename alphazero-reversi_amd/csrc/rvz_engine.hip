@@ -489,8 +489,104 @@ __device__ __forceinline__ int memo_expand_backup(const View& v, int g, int lane
     return backup_path(nodes, path_reg, plen, val, copies, lane, true);
 }
 
+// k_play's forced searches (rvz_play_args.skip_forced_roots): the search's
+// batches E (0: the path is off), simulations S and batch size B
+struct Forced {
+    int E, S, B;
+};
+
+// A search whose root (not over) has L >= E - 1 legal moves, whole, in one step: batch 0 ends on
+// the root, batch k >= 1 goes whole to child k - 1 (N == 0 scores inf, mcts.py:96-97; §2.13), so
+// the visit counts are known before any NN output: min(B, S - k B) on child k - 1 for
+// k = 1 .. E - 1, S on the root. The act reads the children's N, the root's meta word and
+// root_legal only, and the tree is dropped after it: the priors (0 here) and every W stay unread,
+// so neither the root's NN row nor the root noise is needed. Lane s = square s writes child
+// popcount(rl below s), the order expand_backup_phase gives the children. With a carried root
+// the children take the links memo_expand_backup would give them, and a visited child with a
+// link is expanded from the previous tree as select_phase's walk would (its block, its value in
+// bval), so that the act's carry names it and the next search gets its output without a row;
+// blocks e0 .. e0 + E - 1 at most, this search's half of the pool.
+// Returns the rows the search left out, counted as the batch-by-batch search would have met
+// them: the children's rows between the first and the last batch, + 256 for the root's own row.
+// Out of line, arguments by value: the callers' register allocation is that of the code
+// without it.
+template <int BS>
+__device__ __noinline__ int forced_search(const View& v, int g, int lane, int side,
+                                          uint32_t root_meta, uint64_t rl, int half,
+                                          uint32_t carry, Forced fz) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    Node* nodes = v.nodes + (size_t)g * v.M;
+    uint32_t* meta = v.meta + (size_t)g * v.M;
+    const int L = __popcll(rl), nv = fz.E - 1;   // children; visited children (nv <= L)
+    const int e0 = half * v.E, base = 1 + e0 * NSQ;
+    const bool linked_root = v.memo && link_ok(carry);
+    const bool mine = lane < NSQ && ((rl >> lane) & 1ull);
+    const int idx = __popcll(rl & ((1ull << lane) - 1ull));
+    if (base + NSQ > v.M) {
+        if (lane == 0) atomicOr(v.err, ERR_POOL);
+        return 0;
+    }
+    uint32_t lk = LINK_NONE;   // the child's node in the previous tree, if expanded there
+    if (linked_root && mine) {
+        const int oc = 1 + link_block(carry) * NSQ + idx;
+        const uint32_t ocm = meta[oc];
+        if (m_nchild(ocm) > 0 && !m_term(ocm)) lk = link_pack(oc, m_nchild(ocm), m_block(ocm));
+    }
+    const bool visited = mine && idx < nv;
+    uint64_t lmask = __ballot(visited && link_ok(lk));
+    if (1 + (e0 + 1 + __popcll(lmask)) * NSQ > v.M) {
+        if (lane == 0) atomicOr(v.err, ERR_POOL);
+        lmask = 0ull;
+    }
+    const bool expd = (lmask >> lane) & 1ull;
+    const int ce = e0 + 1 + __popcll(lmask & ((1ull << lane) - 1ull));   // an expanded child's block
+    if (mine) {
+        Node c;
+        c.n = visited ? min(fz.B, fz.S - (idx + 1) * fz.B) : 0;
+        c.w = 0.0f; c.p = 0.0f; c.c = __uint_as_float(LINK_NONE);
+        nodes[base + idx] = c;
+        uint32_t cm = meta_pack(lane, 3 - side);
+        if (expd) cm |= ((uint32_t)link_nchild(lk) << 11) | ((uint32_t)ce << 18);
+        meta[base + idx] = cm;
+    }
+    int e = e0 + 1;
+    for (uint64_t rest = lmask; rest != 0ull; rest &= rest - 1ull, ++e) {
+        // memo_expand_backup's expansion of the child at square s into block e
+        const int s = __ffsll((unsigned long long)rest) - 1;
+        const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)lk, s);
+        const int nch = link_nchild(l), ob = 1 + link_block(l) * NSQ, nb = 1 + e * NSQ;
+        if (lane < nch) {
+            const Node oc = nodes[ob + lane];
+            const uint32_t ocm = meta[ob + lane];
+            Node c;
+            c.n = 0; c.w = 0.0f; c.p = oc.p;
+            c.c = __uint_as_float(m_nchild(ocm) > 0 && !m_term(ocm)
+                                      ? link_pack(ob + lane, m_nchild(ocm), m_block(ocm))
+                                      : LINK_NONE);
+            nodes[nb + lane] = c;
+            meta[nb + lane] = meta_pack(m_sq(ocm), side);
+        }
+        if (lane == 0)
+            v.bval[(size_t)g * 2 * v.E + e] = v.bval[(size_t)g * 2 * v.E + link_block(l)];
+    }
+    if (lane == 0) {
+        Node r;
+        r.n = fz.S; r.w = 0.0f; r.p = 1.0f; r.c = __int_as_float(0x7fc00000);
+        nodes[0] = r;
+        meta[0] = root_meta | ((uint32_t)L << 11) | ((uint32_t)e0 << 18);
+        v.nexp[g] = e;
+        v.pend[g] = 0;
+        v.plen[g] = 0;
+    }
+    // the act reads the root, its children and their meta words back in this wave
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    return __popcll(__ballot(mine && idx < nv - 1 && !link_ok(lk))) + (linked_root ? 0 : 256);
+}
+
 // select: mcts.py:348-386 for one batch of `bsz` traversals + _process_batch pass 1 (:561-585).
 // root / root_meta / root_n were loaded (or produced by the expand phase) by the caller.
+// fz (k_play; fz.E > 0 at a search's first batch only): a root with at least fz.E - 1 legal
+// moves is searched whole by forced_search; returns -2 - its count, nothing is queued.
 template <int BS, typename XT>
 __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int first, int bsz,
                                              int eb,
@@ -499,7 +595,7 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
                                              XT* __restrict__ leaf_x, int32_t* __restrict__ need,
                                              unsigned long long& ab,
                                              uint64_t* leaf_bits = nullptr,
-                                             bool unread = false) {
+                                             bool unread = false, Forced fz = Forced{0, 0, 0}) {
     constexpr int NSQ = Geo<BS>::NSQ;
     Node* nodes = v.nodes + (size_t)g * v.M;
     uint32_t* meta = v.meta + (size_t)g * v.M;
@@ -518,6 +614,8 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
         }
         const uint64_t rl = root.over ? 0ull : legal_wave<BS>(mine(root), theirs(root), lane);
         if (lane == 0) v.root_legal[g] = rl;
+        if (fz.E > 0 && !root.over && __popcll(rl) >= fz.E - 1)
+            return -2 - forced_search<BS>(v, g, lane, root.side, root_meta, rl, half, carry, fz);
         if (v.noise_eps > 0.0f && rl != 0ull) root_noise_sample(v, g, lane, root, rl);
         ab += 20 + 8;
     }
@@ -2150,6 +2248,10 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
     pa.tmaxd = 0;
     pa.tstats = reinterpret_cast<unsigned long long*>(a->table_stats);
     pa.unread = reinterpret_cast<unsigned long long*>(a->rows_unread);
+    // forced searches go with the deferred last batch (hence E >= 2): the act then takes the
+    // visit counts alone
+    pa.skip_forced = a->skip_forced_roots && pa.skip_last ? 1 : 0;
+    pa.roots_unread = reinterpret_cast<unsigned long long*>(a->roots_unread);
     pa.rec_black = a->rec_black;
     pa.rec_white = a->rec_white;
     pa.rec_side = a->rec_side;

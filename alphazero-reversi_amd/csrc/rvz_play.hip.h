@@ -70,6 +70,10 @@ struct PlayArgs {
                          // arrived,
     unsigned gate_t;     // or this long after a waiter's arrival (s_memrealtime ticks, 100 MHz);
     unsigned gate_late;  // a workgroup arriving this soon after a round opened joins it at once
+    // forced searches (rvz_play_args.skip_forced_roots): with skip_last, a search
+    // whose root has at least E - 1 legal moves is played whole at its first step (forced_search)
+    int skip_forced;
+    unsigned long long* roots_unread;   // += the root rows those searches left out, or null
 };
 constexpr int PLAY_GPW_MAX = 64;
 // the 8x8 / 64-filter (C2) geometry keeps its head-conv rows in LDS for the FC heads (no
@@ -387,10 +391,10 @@ void k_play(PlayCtx ctx0) {
         task_plies = queue ? 1 : c.a.plies;
     }
     bool ovf = false;
-    // the workgroup's rows, table hits, inserts and unread rows, in LDS (no registers held across
-    // the phases)
-    __shared__ unsigned s_cnt[4];
-    if (tid < 4) s_cnt[tid] = 0u;
+    // the workgroup's rows, table hits, inserts, unread rows and unread root rows, in LDS (no
+    // registers held across the phases)
+    __shared__ unsigned s_cnt[5];
+    if (tid < 5) s_cnt[tid] = 0u;
     if (tid == 0) {
         const PlayArgs& a = play_ctx().a;
         s_tgen = a.tab ? __hip_atomic_load(a.tgen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -512,10 +516,20 @@ void k_play(PlayCtx ctx0) {
                         // E - 1 legal moves gives each batch after the first a fresh child, whose
                         // row no selection reads. The root's own row (batch 0) is evaluated.
                         const bool unread = a.skip_last && !first && m_nchild(root_meta) >= E - 1;
+                        const Forced fz{first && a.skip_forced ? E : 0, a.S, a.B};
                         const int copies = select_phase<BS, float>(v, g, lane, first, bsz, k, root,
                                                                    root_meta, root_n, carry, a.x,
                                                                    a.need, ab, st_bits + 3 * j,
-                                                                   unread);
+                                                                   unread, fz);
+                        if (copies <= -2) {   // a forced search: every batch placed, act next
+                            k = E;
+                            const int left = -2 - copies;   // child rows, + 256: the root's row
+                            if (lane == 0) {
+                                if (left & 255) atomicAdd(&s_cnt[3], (unsigned)(left & 255));
+                                if (left >> 8) atomicAdd(&s_cnt[4], 1u);
+                            }
+                            continue;
+                        }
                         ++k;
                         // (a last batch's row is the deferred one with or without the rule)
                         if (copies < 0 && k < E && lane == 0) atomicAdd(&s_cnt[3], 1u);
@@ -729,4 +743,6 @@ void k_play(PlayCtx ctx0) {
     }
     unsigned long long* un = play_ctx().a.unread;
     if (un && tid == 0 && s_cnt[3]) atomicAdd(un, (unsigned long long)s_cnt[3]);
+    unsigned long long* ur = play_ctx().a.roots_unread;
+    if (ur && tid == 0 && s_cnt[4]) atomicAdd(ur, (unsigned long long)s_cnt[4]);
 }

@@ -129,7 +129,8 @@ class PlayArgs(C.Structure):
                 ("hist", C.c_void_p), ("rows_evaluated", C.c_void_p),
                 ("ply_budget", C.c_void_p), ("table_stats", C.c_void_p),
                 ("rec_black", C.c_void_p), ("rec_white", C.c_void_p), ("rec_side", C.c_void_p),
-                ("rec_p", C.c_void_p), ("rows_unread", C.c_void_p)]
+                ("rec_p", C.c_void_p), ("rows_unread", C.c_void_p),
+                ("skip_forced_roots", C.c_int32), ("roots_unread", C.c_void_p)]
 
 
 def load() -> C.CDLL:

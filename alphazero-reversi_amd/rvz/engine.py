@@ -284,6 +284,9 @@ class Engine:
             # rows play() left unread (skip_last_eval: searches whose batches after the first
             # each go to a fresh root child)
             self.play_unread = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if getattr(self, "play_roots_unread", None) is None:
+            # root rows play() left out (skip_forced_roots: the forced searches' own roots)
+            self.play_roots_unread = torch.zeros(1, dtype=torch.int64, device=self.device)
         n = self.lib.rvz_play_scratch_size(self._h)
         sc = getattr(self, "_play_scratch", None)
         if sc is None or sc.numel() < n:
@@ -295,7 +298,7 @@ class Engine:
              plies_done: torch.Tensor, games_done: torch.Tensor, reset: bool = True,
              skip_last_eval: bool = False, hist: Optional[torch.Tensor] = None,
              games_per_workgroup: int = 0, budget: Optional[torch.Tensor] = None,
-             records=None):
+             records=None, skip_forced_roots: bool = False):
         """rvz_play: every game commits `plies` plies (search of num_simulations + move + the
         autoreset bookkeeping of autoreset()) in ONE launch, the h2 LeafEvaluator's trunk and
         heads inside it; the same games, moves and counters as search() + act() + autoreset()
@@ -304,7 +307,10 @@ class Engine:
         min(plies, budget[g]) plies (the others stay as they are), or None. records: (black
         int64 [plies, G], white int64 [plies, G], side int32 [plies, G], p float64
         [plies, G, npol]): the position before every act and its policy vector (hist: the move;
-        p_buf is then not written), or None. Graph-capturable once play_buffers() ran outside
+        p_buf is then not written), or None. skip_forced_roots (with skip_last_eval): a search
+        whose root has at least as many legal moves as it has batches after the first is played
+        whole at its first step, without its root's row (play_roots_unread counts those rows);
+        the same games. Graph-capturable once play_buffers() ran outside
         the capture (it runs here on the first eager call)."""
         from .network import LeafEvaluator
         if not isinstance(evaluator, LeafEvaluator):
@@ -340,6 +346,7 @@ class Engine:
             rec = tuple(t.data_ptr() for t in records)
         n = self.lib.rvz_play_scratch_size(self._h)
         ready = (getattr(self, "play_rows", None) is not None and
+                 getattr(self, "play_roots_unread", None) is not None and
                  getattr(self, "_play_scratch", None) is not None and
                  self._play_scratch.numel() >= n and getattr(evaluator, "_ovf", None) is not None)
         if not ready:
@@ -358,7 +365,8 @@ class Engine:
                           hist.data_ptr() if hist is not None else None,
                           self.play_rows.data_ptr(),
                           budget.data_ptr() if budget is not None else None,
-                          self.table_stats.data_ptr(), *rec, self.play_unread.data_ptr())
+                          self.table_stats.data_ptr(), *rec, self.play_unread.data_ptr(),
+                          int(bool(skip_forced_roots)), self.play_roots_unread.data_ptr())
         self._stream()
         self._call("rvz_play", C.byref(a))
 

@@ -29,7 +29,7 @@ class SelfPlayRunner:
                  fused_softmax: bool = True, autoreset: bool = False, seed_base: int = 42,
                  record: bool = False, max_plies: int = 60, seed_stride: int = None,
                  skip_last_eval: bool = False, fused_bookkeeping: bool = True,
-                 fused: bool = False, temperature_schedule=None):
+                 fused: bool = False, temperature_schedule=None, skip_forced_roots=None):
         self.eng = engine
         # temperature_schedule: None (the engine's setting stays as it is) or (moves, late): a
         # game's first `moves` moves at `temperature`, the later ones at `late`
@@ -37,6 +37,13 @@ class SelfPlayRunner:
         if temperature_schedule is not None:
             engine.temperature_schedule(*temperature_schedule)
         self.skip_last_eval = bool(skip_last_eval)
+        # skip_forced_roots (Engine.play): None = on when fused and skip_last_eval (the same games,
+        # fewer rows) and a search has three batches or more. At two batches every
+        # search with a legal move is forced (its one child batch is the deferred last one) and
+        # nothing would ever be evaluated, looked up or stored: such a run keeps its root rows
+        # unless the caller asks (True)
+        self.skip_forced_roots = (bool(fused) and bool(skip_last_eval) and engine.n_batches >= 3
+                                  if skip_forced_roots is None else bool(skip_forced_roots))
         # fused: each ply() is ONE rvz_play launch (Engine.play: search + the h2 evaluator +
         # act + autoreset per workgroup) instead of the per-batch launches; same games
         self.fused = bool(fused)
@@ -110,7 +117,8 @@ class SelfPlayRunner:
             eng.play(self.evaluator, plies, self.temperature, self.seeds, self.seed_stride,
                      self._plies, self._done, reset=self.autoreset,
                      skip_last_eval=self.skip_last_eval, hist=hist,
-                     games_per_workgroup=self.play_group, records=rec)
+                     games_per_workgroup=self.play_group, records=rec,
+                     skip_forced_roots=self.skip_forced_roots)
             if self.record:
                 self.post_status.copy_(eng.get_state()[2])
             return

@@ -413,6 +413,16 @@ typedef struct rvz_play_args {
                                     child rows of searches whose root has at least as many legal
                                     moves as batches after the first; their last batch's row, which
                                     skip_last_eval defers anyway, is not counted), nullable */
+    int32_t skip_forced_roots;   /* with skip_last_eval: a search (of two batches or more) whose root
+                                    is not over and has at least as many legal moves as batches
+                                    after the first is played whole at its first step: its visit
+                                    counts are fixed by the move order alone (batch size on each of
+                                    the first children in move order, the remainder on the last), so
+                                    the root's own row is left out as well, and no batch walks the
+                                    tree. Same games. 0: off (the rows of skip_last_eval alone) */
+    int64_t *roots_unread;       /* int64 [1] += the root rows skip_forced_roots left out (forced
+                                    searches whose root took no NN output from the memo), nullable;
+                                    rows_unread keeps counting the child rows of those searches */
 } rvz_play_args;
 /* A task-queue wait that times out (a workgroup waiting for its group's previous ply, bounded
  * spin) sets device error bit 16 (rvz_check): the other workgroups then stop drawing tasks and the

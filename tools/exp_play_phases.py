@@ -2,7 +2,8 @@
 (tools/ab_lib_build.sh ptime -DRVZ_PLAY_TIMING; RVZ_LIB=tools/_ab/librvz_ptime.so): per workgroup
 the shader clocks of the search phase (to its barrier), the trunk passes and the FC heads, the
 loop cycles, passes and rows; summarised over the workgroups of PLIES plies of the C2 workload.
-GAMES (4096), SIMS (800), PLIES (20), NET (6x64), WARM (3)."""
+GAMES (4096), SIMS (800), PLIES (20), NET (6x64), WARM (3); FORCED (1): the timed launch and the
+warm-up plies play forced searches whole (skip_forced_roots), 0: batch by batch."""
 import ctypes as C
 import json
 import os
@@ -25,8 +26,9 @@ net = rvz.AlphaZeroNetwork(8, blocks, filters).cuda().eval()
 eng = rvz.Engine(G, S, 64, memo=True)
 if int(os.environ.get("TABLE", 1)):        # bench.py's default --evals table
     eng.table(1 << 20, 14)
+FORCED = bool(int(os.environ.get("FORCED", 1)))
 run = rvz.SelfPlayRunner(eng, rvz.LeafEvaluator(net), autoreset=True, seed_base=42,
-                         skip_last_eval=True, fused=True)
+                         skip_last_eval=True, fused=True, skip_forced_roots=FORCED)
 run.play_group = int(os.environ.get("GROUP", -6))
 run.start()
 if int(os.environ.get("STAGGER", 1)):      # bench.py's phase stagger (--stagger-order blocked:
@@ -48,7 +50,8 @@ t0 = torch.cuda.Event(enable_timing=True)
 t1 = torch.cuda.Event(enable_timing=True)
 t0.record()
 eng.play(run.evaluator, PLIES, 1.0, run.seeds, run.seed_stride, run._plies, run._done,
-         reset=True, skip_last_eval=True, games_per_workgroup=run.play_group)
+         reset=True, skip_last_eval=True, games_per_workgroup=run.play_group,
+         skip_forced_roots=FORCED)
 t1.record()
 torch.cuda.synchronize()
 ms = t0.elapsed_time(t1)
@@ -62,6 +65,7 @@ end_us = (b[:, 10] - b[:, 10].max()) / 100.0   # s_memrealtime ticks (100 MHz) b
 pt = pt[used]
 tot = b[:, 3]
 out = {"workgroups": int(used.sum()), "launch_ms": round(ms, 3), "plies": PLIES,
+       "forced": FORCED, "rows": int(b[:, 6].sum()),
        "clock_GHz_est": round(float(np.median(tot)) / (ms * 1e6), 3),
        "search_frac": round(float((b[:, 0] / tot).mean()), 4),
        "trunk_frac": round(float((b[:, 1] / tot).mean()), 4),
