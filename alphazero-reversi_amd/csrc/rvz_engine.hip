@@ -2079,10 +2079,12 @@ int rvz_act(rvz_engine* e, double temperature, const double* u, int32_t apply, i
 
 static int64_t play_al4(int64_t n) { return (n + 3) / 4 * 4; }
 
-// scratch (floats): [queue words: q_next + pad, q_done[G]] (one 16-B-aligned block at the start,
-// zeroed per launch), leaf planes, need, head-conv rows, logits, value
+// scratch (floats): [queue words: q_next + pad, q_done[G] (64-bit {published | claimed} words)]
+// (one 16-B-aligned block at the start, zeroed per launch), leaf planes, need, head-conv rows,
+// logits, value
 // + the pass gate's words (PlayArgs::gate: 8 XCDs x 128 bytes)
-static int64_t play_qwords(int64_t G) { return 4 + play_al4(G) + 8 * 32; }
+static int64_t play_gwords(int64_t G) { return 2 * play_al4(G); }
+static int64_t play_qwords(int64_t G) { return 4 + play_gwords(G) + 8 * 32; }
 int64_t rvz_play_scratch_size(const rvz_engine* e) {
     if (!e) return RVZ_EINVAL;
     const int64_t G = e->v.G;
@@ -2188,11 +2190,11 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
     // -games_per_workgroup games (0: RVZ_PLAY_GROUP)
     const bool queue = a->games_per_workgroup <= 0;
     pa.q_next = queue ? reinterpret_cast<unsigned*>(sc) : nullptr;
-    pa.q_done = queue ? reinterpret_cast<unsigned*>(sc) + 4 : nullptr;
+    pa.q_done = queue ? reinterpret_cast<unsigned long long*>(sc + 4) : nullptr;
     pa.n_groups = 0;
     // the per-XCD pass gate (rvz_play.hip.h play_gate, rvz_play_gate; 8x8 at 128 / 256 filters, queue
     // schedule only: its words are zeroed with the queue's)
-    pa.gate = queue ? reinterpret_cast<unsigned long long*>(sc + 4 + play_al4(G)) : nullptr;
+    pa.gate = queue ? reinterpret_cast<unsigned long long*>(sc + 4 + play_gwords(G)) : nullptr;
     {   // rvz_play_gate's setting (default: RVZ_PLAY_GATE_DEFAULT), RVZ_PLAY_GATE overriding it
         double frac = e->gate_frac, us = e->gate_us, late = e->gate_late_us;
         if (frac < 0.0) {

@@ -57,11 +57,17 @@ struct PlayArgs {
     int32_t* rec_side;
     double* rec_p;
     // schedule. Static (q_next null): workgroup w owns game group w for all `plies` plies.
-    // Queue: tasks t = (group t % n_groups, ply t / n_groups) drawn in order from q_next; a
-    // group's ply p starts after q_done[group] reached p (its ply p-1 published: agent-scope
-    // release by the workgroup that played it, acquire by the next). Both zeroed per launch.
+    // Queue (q_next non-null; the word counts the groups whose last ply is published: the
+    // workgroups leave the launch when it reaches n_groups): group g has one word q_done[g] =
+    // {published:32 | claimed:32}, the plies of this launch whose results are visible and the
+    // plies some workgroup has taken; published <= claimed <= published + 1, claimed <= plies.
+    // A workgroup scans the words and takes the least-advanced ready group (claimed == published
+    // < plies) by compare-and-swap of claimed; after playing the ply it adds one to published
+    // (agent-scope release by the workgroup that played it, acquire by the next). It leaves the task
+    // loop when every group's claimed == plies; when nothing is ready but plies are left, some running
+    // workgroup holds them, so it sleeps and rescans (bounded: ERR_SCHED). Zeroed per launch.
     unsigned* q_next;
-    unsigned* q_done;  // [n_groups]
+    unsigned long long* q_done;  // [n_groups]
     int n_groups;
     // the per-XCD pass gate (play_gate; gate null or gate_frac 0: off): [8][16] words, one
     // 128-byte line per XCD, zeroed per launch with the queue words
@@ -332,8 +338,9 @@ __device__ __forceinline__ const PlayCtx& play_ctx() {
 // RVZ_PLAY_TIMING (tools/exp_play_phases.py, instrumented builds only): per workgroup, shader
 // clocks (s_memtime) spent in [0] the search phase (to its barrier), [1] the trunk passes,
 // [2] the FC heads, [3] the whole launch; [4] cycles of the loop, [5] trunk passes, [6] rows,
-// [7] the workgroup's XCC / CU (HW_ID); [8] cycles waiting for a task's previous ply (queue),
-// [9] tasks, [10] the launch clock at the workgroup's end (s_memrealtime, 100 MHz)
+// [7] the workgroup's XCC / CU (HW_ID); [8] cycles drawing tasks (queue: the scans of the group
+// words and the waits when nothing was ready), [9] tasks, [10] the launch clock at the
+// workgroup's end (s_memrealtime, 100 MHz), [11] empty scans (nothing ready, plies left)
 #ifdef RVZ_PLAY_TIMING
 __device__ unsigned long long g_play_t[16384][12];
 #define PT_NOW(t) const unsigned long long t = __builtin_amdgcn_s_memtime()
@@ -380,14 +387,13 @@ void k_play(PlayCtx ctx0) {
     __shared__ unsigned s_tgen;
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int E, G, gpw, total, queue, task_plies;
+    int E, G, gpw, queue, task_plies;
     {
         const PlayCtx& c = play_ctx();
         E = c.v.E;
         G = c.v.G;
         gpw = c.a.gpw;
         queue = c.a.q_next != nullptr;
-        total = queue ? c.a.n_groups * c.a.plies : 0;
         task_plies = queue ? 1 : c.a.plies;
     }
     bool ovf = false;
@@ -415,51 +421,90 @@ void k_play(PlayCtx ctx0) {
             ply0 = 0;
         } else {
             PT_NOW(t_q0);
-            if (tid == 0) {
+            if (wave == 0) {   // wave 0 scans the group words, lane 0 claims
                 const PlayCtx& c = play_ctx();
                 const PlayArgs& a = c.a;
+                const int n = a.n_groups;
+                const unsigned plies = (unsigned)a.plies;
+                // ties go to the lowest index after this rotation: at the launch's start the
+                // workgroups pick different groups instead of all claiming group 0
+                const int rot = (int)((unsigned long long)blockIdx.x * (unsigned)n / gridDim.x);
+                int tg = -1, tp = 0;
                 // once a wait timed out (ERR_SCHED) no workgroup draws another task: the launch
                 // drains, and the engine state is undefined until the games are reset (rvz.h)
-                const bool failed = __hip_atomic_load(c.v.err, __ATOMIC_RELAXED,
-                                                      __HIP_MEMORY_SCOPE_AGENT) & ERR_SCHED;
-                const unsigned t =
-                    failed ? (unsigned)total
-                           : __hip_atomic_fetch_add(a.q_next, 1u, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-                int tg = -1, tp = 0;
-                if ((int)t < total) {
-                    tg = (int)(t % (unsigned)a.n_groups);
-                    tp = (int)(t / (unsigned)a.n_groups);
-                    // the group's previous ply: played (and published) by the workgroup that
-                    // drew it n_groups tasks ago, which is running; bounded spin, abandoned as
-                    // soon as another workgroup's wait timed out
-                    unsigned spins = 0;
-                    while ((int)__hip_atomic_load(a.q_done + tg, __ATOMIC_RELAXED,
-                                                  __HIP_MEMORY_SCOPE_AGENT) < tp) {
-                        __builtin_amdgcn_s_sleep(4);
-                        ++spins;
-                        if (spins > a.spin_limit ||
-                            ((spins & 1023u) == 0 &&
-                             (__hip_atomic_load(c.v.err, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT) & ERR_SCHED))) {
-                            atomicOr(c.v.err, ERR_SCHED);
-                            tg = -1;
-                            break;
+                bool stop = __hip_atomic_load(c.v.err, __ATOMIC_RELAXED,
+                                              __HIP_MEMORY_SCOPE_AGENT) & ERR_SCHED;
+                unsigned spins = 0;
+                while (!stop) {
+                    // the least-advanced ready group: min over {published, rotated index}
+                    unsigned long long best = ~0ull;
+                    bool left = false;   // a group with plies nobody has claimed yet
+                    for (int i = tid; i < n; i += 64) {
+                        const unsigned long long w = __hip_atomic_load(
+                            a.q_done + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        const unsigned pub = (unsigned)(w >> 32), cl = (unsigned)w;
+                        if (cl < plies) {
+                            left = true;
+                            if (cl == pub) {
+                                const int r = i - rot + (i < rot ? n : 0);
+                                const unsigned long long key =
+                                    ((unsigned long long)pub << 32) | (unsigned)r;
+                                best = key < best ? key : best;
+                            }
                         }
                     }
-                    // ONE acquire after the match
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) {
+                        const unsigned long long o = __shfl_xor(best, off, 64);
+                        best = o < best ? o : best;
+                    }
+                    if (best != ~0ull) {
+                        const unsigned p = (unsigned)(best >> 32);
+                        int g = (int)(unsigned)best + rot;
+                        g -= g >= n ? n : 0;
+                        int won = 0;
+                        if (tid == 0) {   // claimed: p -> p + 1 while published is still p
+                            unsigned long long want = ((unsigned long long)p << 32) | p;
+                            won = __hip_atomic_compare_exchange_strong(
+                                a.q_done + g, &want, want + 1ull, __ATOMIC_RELAXED,
+                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        if (__builtin_amdgcn_readfirstlane(won)) {
+                            tg = g;
+                            tp = (int)p;
+                            break;
+                        }
+                        continue;   // another workgroup took it: rescan
+                    }
+                    if (__ballot(left) == 0) break;   // every group's plies are claimed
+                    // nothing ready, but an in-flight group has plies left: its workgroup is
+                    // running and will publish; bounded spin, abandoned as soon as another
+                    // workgroup's wait timed out
+                    __builtin_amdgcn_s_sleep(4);
+                    ++spins;
+                    PT_ADD(11, 1);
+                    if (spins > a.spin_limit ||
+                        ((spins & 1023u) == 0 &&
+                         (__hip_atomic_load(c.v.err, __ATOMIC_RELAXED,
+                                            __HIP_MEMORY_SCOPE_AGENT) & ERR_SCHED))) {
+                        if (tid == 0) atomicOr(c.v.err, ERR_SCHED);
+                        stop = true;
+                    }
                 }
-                s_task[0] = tg;
-                s_task[1] = tp;
+                // ONE acquire after the claim
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (tid == 0) {
+                    s_task[0] = tg;
+                    s_task[1] = tp;
+                }
             }
             __syncthreads();   // the other waves load the group's state after the acquire
             gi = __builtin_amdgcn_readfirstlane(s_task[0]);
             ply0 = __builtin_amdgcn_readfirstlane(s_task[1]);
-            if (gi < 0) break;
             PT_NOW(t_q1);
             PT_ADD(8, t_q1 - t_q0);
+            if (gi < 0) break;
             PT_ADD(9, 1);
         }
         const int g0 = gi * gpw;
@@ -710,8 +755,11 @@ void k_play(PlayCtx ctx0) {
             if (tid == 0) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __hip_atomic_store(play_ctx().a.q_done + gi, (unsigned)(ply0 + 1), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(play_ctx().a.q_done + gi, 1ull << 32, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);   // published += 1
+                if (ply0 + 1 == play_ctx().a.plies)   // the group's last ply: one group fewer
+                    __hip_atomic_fetch_add(play_ctx().a.q_next, 1u, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
@@ -731,6 +779,32 @@ void k_play(PlayCtx ctx0) {
                 __builtin_amdgcn_s_getreg((31 << 11) | 4);
     }
 #endif
+    // The launch's end (queue): a workgroup that found every ply claimed has no task left, but
+    // other workgroups are still playing theirs. It stays until every group's last ply is
+    // published (q_next counts them), asleep on that one word: it runs no pass and is off the
+    // gate's count, so it costs the others nothing, and the launch ends when the last task does
+    // either way. This is the one wait every launch of two or more workgroups has, under the same
+    // bound and error protocol as a draw's: the ready schedule leaves a balanced launch no other,
+    // and RVZ_PLAY_SPIN_LIMIT=0 times out here (test_queue_wait_timeout_drains_and_reports).
+    if (queue && tid == 0) {
+        const PlayCtx& c = play_ctx();
+        const PlayArgs& a = c.a;
+        unsigned spins = 0;
+        bool stop = __hip_atomic_load(c.v.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+                    ERR_SCHED;
+        while (!stop && (int)__hip_atomic_load(a.q_next, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT) < a.n_groups) {
+            __builtin_amdgcn_s_sleep(4);
+            ++spins;
+            if (spins > a.spin_limit ||
+                ((spins & 1023u) == 0 &&
+                 (__hip_atomic_load(c.v.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) &
+                  ERR_SCHED))) {
+                atomicOr(c.v.err, ERR_SCHED);
+                stop = true;
+            }
+        }
+    }
     float* ovw = play_ctx().a.ovf;
     if (ovf && ovw) *ovw = 1.0f;   // benign race: every writer stores 1
     unsigned long long* rows = play_ctx().a.rows;

@@ -424,8 +424,11 @@ typedef struct rvz_play_args {
                                     searches whose root took no NN output from the memo), nullable;
                                     rows_unread keeps counting the child rows of those searches */
 } rvz_play_args;
-/* A task-queue wait that times out (a workgroup waiting for its group's previous ply, bounded
- * spin) sets device error bit 16 (rvz_check): the other workgroups then stop drawing tasks and the
+/* The task queue is a ready schedule: a workgroup takes the least-advanced group whose previous
+ * ply is published (one {published | claimed} word per group in the scratch, zeroed per launch),
+ * so it waits only when every group with plies left is being played by another workgroup.
+ * A task-queue wait that times out (a workgroup that found no ready group while plies were left,
+ * bounded spin) sets device error bit 16 (rvz_check): the other workgroups then stop drawing tasks and the
  * launch drains, leaving games at different ply counts. The engine state is then undefined until
  * every game is reset (rvz_env_reset). */
 int64_t rvz_play_scratch_size(const rvz_engine *e);

@@ -82,6 +82,8 @@ out = {"workgroups": int(used.sum()), "launch_ms": round(ms, 3), "plies": PLIES,
        "heads_weights_wait_kcycles_per_cycle": round(float(pt[:, 4].sum() / b[:, 4].sum()) / 1e3, 2),
        "heads_compute_kcycles_per_cycle": round(float(pt[:, 5].sum() / b[:, 4].sum()) / 1e3, 2),
        "queue_wait_frac": round(float((b[:, 8] / tot).mean()), 4),
+       "empty_scans_total": int(b[:, 11].sum()),
+       "workgroups_with_empty_scans": int((b[:, 11] > 0).sum()),
        "tasks_per_wg_min_med_max": [int(b[:, 9].min()), int(np.median(b[:, 9])), int(b[:, 9].max())],
        "wg_end_us_before_last_median_max": [round(float(-np.median(end_us)), 1),
                                              round(float(-end_us.min()), 1)],
