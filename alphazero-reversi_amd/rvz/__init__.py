@@ -14,9 +14,12 @@ Batched core:
                             optional move ordering (rvz_solve_window)
     solve_moves, solve_moves_wld   the value of every root move (rvz_solve_moves); best_moves
                             reduces them to the proven-optimal moves of each row
+    alphabeta               depth-limited heuristic search of a batch of positions (rvz_alphabeta),
+                            alphabeta_weights its default evaluation; arena.AlphaBetaPlayer plays it
 """
 from ._lib import RvzError, load  # noqa: F401
-from .engine import (SOLVE_ABANDONED, SOLVE_NOT_A_MOVE, Engine, action_probs,  # noqa: F401
+from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa: F401
+                     SOLVE_NOT_A_MOVE, Engine, action_probs, alphabeta, alphabeta_weights,
                      best_moves, board_apply, board_canonical, board_legal, dirichlet_noise,
                      policy_softmax, solve, solve_moves, solve_moves_wld, solve_window, solve_wld)
 from .game import Board, ReversiGame  # noqa: F401

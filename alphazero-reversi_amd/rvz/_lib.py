@@ -24,6 +24,9 @@ RVZ_LEAF_F32, RVZ_LEAF_BF16 = 0, 1
 RVZ_DRAWS = 64          # move-sampling draws held per game (rvz_env_set_draws)
 RVZ_SOLVE_MAX_EMPTIES = 14   # rvz_solve: the deepest root its per-lane stack holds
 RVZ_SOLVE_NOT_A_MOVE, RVZ_SOLVE_ABANDONED = -128, -127     # rvz_solve_moves: entries without a score
+RVZ_AB_MAX_DEPTH = 12        # rvz_alphabeta: the deepest search its per-lane stack holds
+RVZ_AB_WIN = 20000           # rvz_alphabeta: a finished game scores +-(RVZ_AB_WIN + |disc difference|)
+RVZ_AB_HEUR_MAX = 16000      # rvz_alphabeta: sum |weights[s]| + NSQ * |weights[NSQ]| at most
 
 
 class RvzError(RuntimeError):
@@ -91,6 +94,8 @@ SIGNATURES = {
                                    C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "rvz_solve_moves": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int64,
                                   C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "rvz_alphabeta": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, C.c_int64, _P, _P,
+                                _P, _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),

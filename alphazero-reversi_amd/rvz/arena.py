@@ -17,6 +17,10 @@ tournament draws — one ``random_sample()`` per MCTS move from the NumPy stream
 (arena.py:175-188, mcts.py:684) — so the same seeds give the reference's tournament; lockstep
 passes find each game's place in the streams (``Arena._play_reference_order``).
 ``draw_order="batched"`` keeps round 3's cheaper order (one draw per game per ply).
+
+``AlphaBetaPlayer`` is the fixed, net-independent opponent: a depth-limited alpha-beta search with
+a classical evaluation (rvz.alphabeta), optionally exact in the endgame (rvz.solve). It is
+deterministic and draws from neither stream, so ratings against it compare across runs.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import engine as _engine
 from .engine import Engine
 from .network import leaf_evaluator
 
@@ -121,6 +126,70 @@ class ELOPlayer:
         """Searches start from a fresh root every move (mcts.py:334): nothing to reset."""
 
 
+class AlphaBetaPlayer:
+    """A depth-limited alpha-beta player with a classical evaluation (rvz.alphabeta): each ply,
+    its games take the search's move (the lowest-index best square). model is None, as the random
+    player's; the arena tells the two apart by `alphabeta`. weights: rvz.alphabeta's (None: the
+    default table of the board). solve_empties = N > 0: a game with at most N empty squares takes
+    rvz.solve's move instead (exact play to the end); a row the solver abandons at node_limit
+    keeps the alpha-beta move. A row rvz.alphabeta itself abandons at node_limit raises
+    RuntimeError. Deterministic: the player draws from neither of the arena's generators."""
+
+    alphabeta = True
+
+    def __init__(self, player_id: str, depth: int = 4, weights: Optional[Sequence[int]] = None,
+                 board_size: int = 8, solve_empties: int = 0, node_limit: int = 2 ** 24,
+                 device: str = "cuda"):
+        if not 1 <= int(depth) <= _engine.AB_MAX_DEPTH:
+            raise ValueError(f"depth must be in [1, {_engine.AB_MAX_DEPTH}], got {depth!r}")
+        if not 0 <= int(solve_empties) <= _engine.SOLVE_MAX_EMPTIES:
+            raise ValueError("solve_empties must be in "
+                             f"[0, {_engine.SOLVE_MAX_EMPTIES}], got {solve_empties!r}")
+        self.player_id = player_id
+        self.model = None
+        self.device = torch.device(device)
+        self.board_size = int(board_size)
+        self.depth = int(depth)
+        self.weights = (_engine.alphabeta_weights(self.board_size) if weights is None
+                        else [int(x) for x in weights])
+        self.solve_empties = int(solve_empties)
+        self.node_limit = int(node_limit)
+
+    def reset(self):
+        """Every move is a fresh search: nothing to reset."""
+
+    def moves(self, black: torch.Tensor, white: torch.Tensor, status: torch.Tensor) -> np.ndarray:
+        """The player's move in every row that is not over (rows that are over: -1): a square,
+        or -1 for the pass. One rvz.alphabeta call over the batch, and with solve_empties one
+        rvz.solve call."""
+        nsq = self.board_size ** 2
+        _, mv, _ = _engine.alphabeta(black, white, status, self.board_size, self.depth,
+                                     self.weights, self.node_limit)
+        sm = None
+        if self.solve_empties > 0:
+            _, sm, _ = _engine.solve(black, white, status, self.board_size, self.solve_empties,
+                                     self.node_limit)
+        mv = mv.cpu().numpy().astype(np.int64)
+        if (mv == -4).any():
+            raise RuntimeError(f"AlphaBetaPlayer {self.player_id}: rvz_alphabeta abandoned a row at "
+                               f"node_limit = {self.node_limit} (depth {self.depth})")
+        if (mv == -5).any():
+            raise RuntimeError(f"AlphaBetaPlayer {self.player_id}: malformed position")
+        if sm is not None:
+            sm = sm.cpu().numpy().astype(np.int64)
+            mv = np.where(sm >= 0, sm, mv)         # -3 above solve_empties, -4 abandoned: kept
+        return np.where((mv < 0) | (mv == nsq), -1, mv)
+
+
+def _is_alphabeta(player) -> bool:
+    return bool(getattr(player, "alphabeta", False))
+
+
+def _is_random(player) -> bool:
+    """The random player: ELOPlayer(model=None). It alone calls random.choice()."""
+    return player.model is None and not _is_alphabeta(player)
+
+
 class _BatchedDraws:
     """draw_order "batched": one random_sample() per game per ply from the arena's NumPy
     generator (used by the games whose mover searches), random choices in (sorted player id,
@@ -186,13 +255,13 @@ class Arena:
         random.seed(seed) would leave the reference's global ones (the reference draws from
         those, arena.py:178-188). draw_order: see ``play_games``."""
         self.elo = elo_system if elo_system is not None else ELORatingSystem()
-        self.players: Dict[str, ELOPlayer] = {}
+        self.players: Dict[str, object] = {}      # ELOPlayer | AlphaBetaPlayer
         self.np_rng = np.random.RandomState(seed)
         self.py_rng = random.Random(seed)
         self.draw_order = draw_order
         self.reference_order_passes = 0
 
-    def add_player(self, player: ELOPlayer):
+    def add_player(self, player):
         self.players[player.player_id] = player
         self.elo.add_player(player.player_id)
 
@@ -245,11 +314,15 @@ class Arena:
         (random-player games + 2) passes, each as long as one game, with every other game
         played about once. `reference_order_passes` reports the count; the engines are built
         once per call. Both generators end where the sequential loop leaves them.
+
+        An AlphaBetaPlayer draws nothing: its moves add no NumPy draws and no choice() calls to
+        its games, and a game without a *random* player is not serialised, whoever else plays it.
         """
         G = len(black_ids)
         nsq = self._board_size(black_ids, white_ids) ** 2
         mcts = {p: self.players[p].model is not None for p in set(black_ids) | set(white_ids)}
-        mcts_only = [mcts[black_ids[g]] and mcts[white_ids[g]] for g in range(G)]
+        rand = {p: _is_random(self.players[p]) for p in mcts}
+        no_random = [not (rand[black_ids[g]] or rand[white_ids[g]]) for g in range(G)]
         cache: Dict = {}
         rs = np.random.RandomState()
         rs.set_state(self.np_rng.get_state())
@@ -275,7 +348,7 @@ class Arena:
             for g in range(G):
                 if inputs[g] == prev[g]:
                     continue
-                if not mcts_only[g]:          # one random-player game per pass (docstring)
+                if not no_random[g]:          # one random-player game per pass (docstring)
                     if rand_seen:
                         continue
                     rand_seen = True
@@ -300,7 +373,7 @@ class Arena:
 
     def _board_size(self, black_ids, white_ids) -> int:
         sizes = {self.players[p].board_size for p in set(black_ids) | set(white_ids)
-                 if self.players[p].model is not None}
+                 if not _is_random(self.players[p])}
         if len(sizes) > 1:
             raise ValueError(f"players of one batch play on one board size, got {sorted(sizes)}")
         return sizes.pop() if sizes else 8
@@ -350,6 +423,12 @@ class Arena:
                 if not games_k.any():
                     continue
                 pl = self.players[pid]
+                if _is_alphabeta(pl):                  # one rvz.alphabeta call over its games
+                    st_k = st.clone()
+                    st_k[:, 1] = torch.where(torch.from_numpy(games_k).to(dev), st[:, 1],
+                                             torch.ones_like(st[:, 1]))
+                    move[games_k] = pl.moves(b, w, st_k)[games_k]
+                    continue
                 if pl.model is None:                   # random player: random.choice(valid)
                     legal = env.legal().cpu().numpy().view(np.uint64)
                     for g in np.flatnonzero(games_k):

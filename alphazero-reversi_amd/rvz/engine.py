@@ -25,6 +25,9 @@ U64 = 0xFFFFFFFFFFFFFFFF
 SOLVE_MAX_EMPTIES = _lib.RVZ_SOLVE_MAX_EMPTIES
 SOLVE_NOT_A_MOVE = _lib.RVZ_SOLVE_NOT_A_MOVE      # solve_moves: not a legal move of the row
 SOLVE_ABANDONED = _lib.RVZ_SOLVE_ABANDONED        # solve_moves: the move's search hit node_limit
+AB_MAX_DEPTH = _lib.RVZ_AB_MAX_DEPTH              # alphabeta: the deepest search
+AB_WIN = _lib.RVZ_AB_WIN                          # alphabeta: |score| of a finished game, at least
+AB_HEUR_MAX = _lib.RVZ_AB_HEUR_MAX                # alphabeta: the bound on a weight table
 
 
 def to_signed64(x: int) -> int:
@@ -258,6 +261,13 @@ class Engine:
             order_min_empties = WLD_ORDER_MIN_EMPTIES
         return solve_moves_wld(b, w, st, self.board_size, max_empties, node_limit,
                                order_min_empties)
+
+    def alphabeta(self, depth: int = 4, weights: Optional[Sequence[int]] = None,
+                  node_limit: int = 2 ** 24):
+        """rvz.alphabeta on the engine's current env state, as solve(): (score, move, nodes) per
+        game. Reads only."""
+        b, w, st = self._env_snapshot()
+        return alphabeta(b, w, st, self.board_size, depth, weights, node_limit)
 
     def legal(self) -> torch.Tensor:
         self._stream()
@@ -754,6 +764,69 @@ def best_moves(scores: torch.Tensor, count: torch.Tensor, alpha: int = -64, beta
     mask = solved & (clamped == best.unsqueeze(1)) & complete.unsqueeze(1)
     best = torch.where(complete, best, torch.zeros_like(best))
     return best, mask, complete
+
+
+# alphabeta_weights: the value of a square by its distance from the nearest edges (row and
+# column folded onto one quadrant, the smaller first), and the weight of one legal move more
+_AB_SQUARE_CLASS = {(0, 0): 100, (0, 1): -20, (0, 2): 10, (0, 3): 5, (1, 1): -50, (1, 2): -2,
+                    (1, 3): -2, (2, 2): -1, (2, 3): -1, (3, 3): -1}
+_AB_MOBILITY = 10
+
+
+def alphabeta_weights(board_size: int = 8):
+    """The default evaluation of alphabeta(): a list of S*S + 1 ints, the square table in square
+    index order and the mobility weight last. A classical table: corners 100, the squares
+    diagonally next to a corner -50 (the lowest), the edge squares next to a corner -20, the
+    other edge squares 10 and 5, the second ring -2, the centre -1; one legal move more than the
+    opponent is worth 10. Invariant under the eight board symmetries and within
+    RVZ_AB_HEUR_MAX (8x8: 928 + 64 * 10 = 1568; 6x6: 860 + 36 * 10 = 1220)."""
+    if board_size not in (6, 8):
+        raise RvzError("alphabeta_weights: board_size must be 8 or 6")
+    bs = int(board_size)
+    fold = lambda i: min(i, bs - 1 - i)
+    table = [_AB_SQUARE_CLASS[tuple(sorted((fold(s // bs), fold(s % bs))))] for s in range(bs * bs)]
+    return table + [_AB_MOBILITY]
+
+
+def alphabeta(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int = 8,
+              depth: int = 4, weights: Optional[Sequence[int]] = None, node_limit: int = 2 ** 24):
+    """rvz_alphabeta: the depth-limited value of n positions under the engine's rules (negamax
+    `depth` placed discs deep with fail-soft alpha-beta pruning, one position per lane; passes cost
+    no depth). Inputs as solve(). weights: S*S + 1 ints, the value of each square to its owner
+    and, last, of one legal move more than the opponent (None: alphabeta_weights(board_size));
+    sum |square| + S*S * |mobility| <= RVZ_AB_HEUR_MAX. Returns (score int32 [n], move int32 [n],
+    nodes int64 [n]) on the inputs' device: score is the search's value for the side to move,
+    +-(RVZ_AB_WIN + |final disc difference|) where the game is played out (0 for a draw); move is
+    the lowest-index best square, S*S for a forced pass, -2 for a root that is over (score
+    valid), -4 abandoned at node_limit visited positions, -5 for a malformed row (score 0 for
+    -4 / -5); nodes counts the positions visited. 1 <= depth <= RVZ_AB_MAX_DEPTH."""
+    lib = _lib.load()
+    nsq = int(board_size) ** 2
+    if weights is None:
+        weights = alphabeta_weights(board_size)
+    wl = [int(x) for x in weights]
+    if board_size in (6, 8) and len(wl) != nsq + 1:
+        raise RvzError(f"alphabeta: weights must hold {nsq + 1} ints (S*S squares, then mobility)")
+    if any(not -2 ** 31 <= x < 2 ** 31 for x in wl):
+        raise RvzError("alphabeta: a weight does not fit int32")
+    wt = (C.c_int32 * max(len(wl), 1))(*wl)       # host memory: read during the call only
+    n = black.numel()
+    if status.shape != (n, 4) or white.numel() != n:
+        raise RvzError("alphabeta: black and white hold one entry per row, status is [n, 4]")
+    dev = black.device
+    b = black.to(torch.int64).contiguous()
+    w = white.to(dev, torch.int64).contiguous()
+    st = status.to(dev, torch.int32).contiguous()
+    score = torch.empty(n, dtype=torch.int32, device=dev)
+    move = torch.empty(n, dtype=torch.int32, device=dev)
+    nodes = torch.empty(n, dtype=torch.int64, device=dev)
+    pb, pw, pst, pscore, pmove, pnodes, stream = (
+        [ptr(t) for t in (b, w, st, score, move, nodes)] + [_lib.stream_handle(dev)]
+        if n else [None] * 7)
+    check(lib.rvz_alphabeta(int(board_size), n, pb, pw, pst, int(depth),
+                            C.cast(wt, C.c_void_p), int(node_limit), pscore, pmove, pnodes,
+                            stream), None, "rvz_alphabeta")
+    return score, move, nodes
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

@@ -360,6 +360,62 @@ int rvz_solve_moves(int32_t board_size, int32_t n, const uint64_t *black, const 
                     int32_t alpha, int32_t beta, int32_t order_min_empties, int32_t *out_scores,
                     int32_t *out_count, int64_t *out_nodes, void *hip_stream);
 
+/* ---- depth-limited heuristic search -------------------------------------------------------
+ * Stateless, on caller arrays: the value of n independent positions by a negamax that stops
+ * `depth` placed discs below the root and scores the frontier with a classical evaluation (a
+ * square table plus mobility), one position per lane (csrc/rvz_alphabeta.hip): a fixed,
+ * net-independent opponent of adjustable strength. The rules are rvz_solve's: the legal mask
+ * without file masks, the flip walk, make_move with its auto-pass and game end, moves in
+ * increasing square index. The row layout (black / white uint64 [n], status int32 [n][4]) and
+ * the device pointers are rvz_solve's too.
+ * With NSQ = S*S, weights int32 [NSQ + 1] on the HOST, and for a position g that is not over,
+ * P the mover's discs and O the other side's:
+ *   h(g) = sum over squares s of weights[s] * ([s in P] - [s in O])
+ *        + weights[NSQ] * (popcount(legal(P, O)) - popcount(legal(O, P)))
+ * in integer arithmetic, from the mover's side. For a position that is over, with
+ * diff = discs(side to move) - discs(other side):
+ *   T(g) = RVZ_AB_WIN + diff when diff > 0, -RVZ_AB_WIN + diff when diff < 0, 0 when diff == 0,
+ * so a proven result always outranks a heuristic one. Then
+ *   value(g, d) = T(g) if g is over, h(g) if d == 0, else the maximum over g's legal squares s
+ *   in increasing index of, with c = make_move(g, s): value(c, d - 1) if c kept g's side
+ *   (auto-pass), -value(c, d - 1) otherwise.
+ * A ply of depth is one placed disc: an auto-pass inside make_move costs none, and neither does
+ * a pass root (not over, the mover without a legal square): its value is -value(child after the
+ * pass, d), or T when the pass ends the game (passed = 1, or the other side has no move either),
+ * and its move is NSQ.
+ * The weights are validated on the host before any HIP call:
+ *   sum over s of |weights[s]| + NSQ * |weights[NSQ]| <= RVZ_AB_HEUR_MAX,
+ * hence |h| < RVZ_AB_WIN - 64 and every score fits int16. They are read at call time and travel
+ * by value in the kernel's arguments: the call allocates nothing, copies nothing and does not
+ * synchronise; it is asynchronous on hip_stream and graph-capturable, and a captured call keeps
+ * the weights of its capture.
+ * out_score int32 [n]: value(row, depth). out_move int32 [n]: the lowest-index root square that
+ * reaches out_score; NSQ for a pass root; or a row code, checked in the kernel (no host
+ * synchronisation):
+ *   -2  the row is already over: out_score = T(row), nodes 1;
+ *   -4  abandoned at node_limit: out_score 0, nodes = node_limit (rvz_solve's counting: the
+ *       root counts, and so does every committed move, frontier and finished children included);
+ *   -5  malformed row (rvz_solve's three checks): out_score 0, nodes 0.
+ * There is no -3. out_nodes (nullable) int64 [n]: the positions visited for the row.
+ * Score and move equal the unpruned definition exactly (fail-soft alpha-beta, the root's
+ * children searched with (best so far, +inf) and compared strictly). A row's three outputs
+ * depend on the row, the arguments and the build alone, not on n, the row's index, its
+ * neighbours or the launch geometry.
+ * At most 32 rvz_alphabeta calls may be executing at once on one device: each takes one of 32
+ * row counters in turn (a captured call keeps the one of its capture). The counters are the
+ * kernel's own, so rvz_solve* calls and rvz_alphabeta calls never share one.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, depth outside
+ * [1, RVZ_AB_MAX_DEPTH], node_limit <= 0, null weights, the weight bound violated, a null
+ * black / white / status / out_score / out_move with n > 0. n = 0 returns RVZ_OK without a
+ * launch. */
+#define RVZ_AB_MAX_DEPTH 12
+#define RVZ_AB_WIN 20000
+#define RVZ_AB_HEUR_MAX 16000
+int rvz_alphabeta(int32_t board_size, int32_t n, const uint64_t *black, const uint64_t *white,
+                  const int32_t *status, int32_t depth, const int32_t *weights /* host */,
+                  int64_t node_limit, int32_t *out_score, int32_t *out_move,
+                  int64_t *out_nodes /* nullable */, void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
