@@ -1,0 +1,203 @@
+// rvz_symmetry.hip — the eight symmetries of the square board on bitboards and training rows
+// (rvz_board_symmetry, rvz_training_rows; contracts in include/rvz.h).
+//
+// Numbering: k = 4 * f + r, T_k(x) = fliplr(rot90(x, r)) if f else rot90(x, r) on an [S][S] array
+// indexed (row, col) (NumPy's rot90: counter-clockwise). In coordinates, T_k(x)[i][j] =
+// x[src_k(i, j)] with
+//   k = 0 (i, j)          k = 1 (j, S-1-i)      k = 2 (S-1-i, S-1-j)   k = 3 (S-1-j, i)
+//   k = 4 (i, S-1-j)      k = 5 (S-1-j, S-1-i)  k = 6 (S-1-i, j)       k = 7 (j, i)
+//
+// k_board_symmetry: one lane per board, the transform in registers. 8x8: with t = the transpose
+// (three delta swaps) for odd k, else x, every image is t, its 64-bit reversal, its byte swap, or
+// both (the mirror of the columns). 6x6: a 36-step bit gather through src_k.
+//
+// k_training_rows: one wavefront per input row, lane = output square. The row's bitboards and
+// side are wave-uniform; each lane looks up its source square, the three image bitboards are
+// three ballots, and the policy row moves through one cross-lane read, so nothing is recomputed
+// and no table lives in memory. Per image the wave stores the 3*S*S plane floats as float4 (48
+// lanes on 8x8, 27 on 6x6), the S*S+1 policy floats as dwords and one quirk word: 1028 B on 8x8
+// (1032 B with the quirk), 580 B (584 B) on 6x6, each byte written once.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rvz.h"
+#include "rvz_rules.hip.h"
+
+namespace {
+
+using namespace rvz;
+
+constexpr int SYM_THREADS = 256;                 // 4 waves, one input row each per step
+constexpr int SYM_WAVES = SYM_THREADS / 64;
+constexpr int SYM_MAX_BLOCKS = 2048;             // grid-stride beyond that
+
+// the source square of output square s under T_k (k in [0, 8))
+template <int BS>
+__device__ __forceinline__ int sym_src(int s, int k) {
+    const int i = s / BS, j0 = s % BS;
+    const int j = (k & 4) ? BS - 1 - j0 : j0;
+    const int r = k & 3;
+    const int si = r == 0 ? i : (r == 1 ? j : (r == 2 ? BS - 1 - i : BS - 1 - j));
+    const int sj = r == 0 ? j : (r == 1 ? BS - 1 - i : (r == 2 ? BS - 1 - j : i));
+    return si * BS + sj;
+}
+
+__device__ __forceinline__ uint64_t delta_swap(uint64_t x, uint64_t mask, int shift) {
+    const uint64_t t = mask & (x ^ (x << shift));
+    return x ^ t ^ (t >> shift);
+}
+
+// T_k of an 8x8 bitboard (k in [0, 8)): transpose for odd k, then the reversal of all 64 bits
+// (rotation by 180 degrees) for k in {2, 3, 4, 5} and the byte swap (rows mirrored) for k in
+// {1, 3, 4, 6}; reversal and byte swap together mirror the columns.
+__device__ __forceinline__ uint64_t sym_image8(uint64_t x, int k) {
+    uint64_t t = delta_swap(x, 0x0F0F0F0F00000000ull, 28);
+    t = delta_swap(t, 0x3333000033330000ull, 14);
+    t = delta_swap(t, 0x5500550055005500ull, 7);
+    t = (k & 1) ? t : x;
+    const uint64_t rv = __brevll(t);
+    t = ((0x3Cu >> k) & 1u) ? rv : t;
+    const uint64_t sw = __builtin_bswap64(t);
+    return ((0x5Au >> k) & 1u) ? sw : t;
+}
+
+template <int BS>
+__device__ __forceinline__ uint64_t sym_image(uint64_t x, int k) {
+    if constexpr (BS == 8) {
+        return sym_image8(x, k);
+    } else {
+        uint64_t y = 0;
+#pragma unroll 4
+        for (int s = 0; s < Geo<BS>::NSQ; ++s) y |= ((x >> sym_src<BS>(s, k)) & 1ull) << s;
+        return y;
+    }
+}
+
+// out_* may be the input pointers themselves: every lane reads its row before it writes it
+template <int BS>
+__global__ __launch_bounds__(SYM_THREADS) void k_board_symmetry(
+    int n, const uint64_t* black, const uint64_t* white, const int32_t* __restrict__ sym,
+    uint64_t* out_black, uint64_t* out_white) {
+    const long long step = (long long)gridDim.x * SYM_THREADS;      // n + step can pass 2^31
+    for (long long i = (long long)blockIdx.x * SYM_THREADS + threadIdx.x; i < n; i += step) {
+        const int k = sym[i];
+        const uint64_t b = black[i], w = white[i];
+        const bool ok = k >= 0 && k < 8;
+        out_black[i] = ok ? sym_image<BS>(b, k & 7) : 0ull;
+        out_white[i] = ok ? sym_image<BS>(w, k & 7) : 0ull;
+    }
+}
+
+// One image of one row, by the whole wave. P, O, V (mover, opponent, legal mask of the original),
+// pass and k are wave-uniform; pv is the lane's own policy entry (lane = square). k outside
+// [0, 8): an all-zero row and quirk -1.
+template <int BS>
+__device__ __forceinline__ void write_image(int lane, uint64_t P, uint64_t O, uint64_t V, float pv,
+                                            float pass, int k, size_t row,
+                                            float* __restrict__ out_states,
+                                            float* __restrict__ out_policy,
+                                            int32_t* __restrict__ out_quirk) {
+    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    const bool ok = k >= 0 && k < 8;
+    const bool sq = lane < NSQ;
+    const int src = sq ? sym_src<BS>(lane, k & 7) : lane;
+    const bool take = ok && sq;
+    const uint64_t TP = __ballot(take && ((P >> src) & 1ull));
+    const uint64_t TO = __ballot(take && ((O >> src) & 1ull));
+    const uint64_t TV = __ballot(take && ((V >> src) & 1ull));
+    const float moved = __shfl(pv, src, 64);
+
+    if (lane < 3 * NSQ / 4) {                    // NSQ % 4 == 0: a float4 stays within one plane
+        const int e = 4 * lane, plane = e / NSQ, s = e % NSQ;
+        const uint64_t B = plane == 0 ? TP : (plane == 1 ? TO : TV);
+        const uint32_t nib = (uint32_t)(B >> s) & 0xFu;
+        reinterpret_cast<float4*>(out_states + row * (3 * NSQ))[lane] =
+            make_float4((float)(nib & 1u), (float)((nib >> 1) & 1u), (float)((nib >> 2) & 1u),
+                        (float)(nib >> 3));
+    }
+    float* prow = out_policy + row * NPOL;
+    if (lane < NPOL) prow[lane] = ok ? (sq ? moved : pass) : 0.0f;
+    if (NPOL > 64 && lane == 0) prow[NSQ] = ok ? pass : 0.0f;
+    if (out_quirk) {             // wave-uniform; the image position's own mask, a direction per lane
+        const uint64_t own = legal_wave<BS>(TP, TO, lane);
+        if (lane == 0) out_quirk[row] = ok ? (int32_t)(own != TV) : -1;
+    }
+}
+
+template <int BS, int FAN>
+__global__ __launch_bounds__(SYM_THREADS) void k_training_rows(
+    int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
+    const int32_t* __restrict__ status, const float* __restrict__ policy,
+    const int32_t* __restrict__ sym, float* __restrict__ out_states,
+    float* __restrict__ out_policy, int32_t* __restrict__ out_quirk) {
+    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int step = gridDim.x * SYM_WAVES;
+    for (int i = blockIdx.x * SYM_WAVES + wave; i < n; i += step) {     // wave-uniform trip count
+        const int side = status[4 * i];
+        const uint64_t b = black[i], w = white[i];
+        const uint64_t P = side == 1 ? b : w, O = side == 1 ? w : b;    // as k_board_canonical
+        const uint64_t V = legal<BS>(P, O);
+        const float* prow = policy + (size_t)i * NPOL;
+        const float pv = lane < NSQ ? prow[lane] : 0.0f;
+        const float pass = prow[NSQ];
+        if constexpr (FAN == 1) {
+            write_image<BS>(lane, P, O, V, pv, pass, sym[i], (size_t)i, out_states, out_policy,
+                            out_quirk);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                write_image<BS>(lane, P, O, V, pv, pass, k, (size_t)i * 8 + k, out_states,
+                                out_policy, out_quirk);
+        }
+    }
+}
+
+int blocks_for(int64_t units, int per_block) {
+    const int64_t need = (units + per_block - 1) / per_block;
+    return (int)(need < SYM_MAX_BLOCKS ? need : SYM_MAX_BLOCKS);
+}
+
+}  // namespace
+
+extern "C" int rvz_board_symmetry(int32_t bs, int32_t n, const uint64_t* black,
+                                  const uint64_t* white, const int32_t* sym, uint64_t* out_black,
+                                  uint64_t* out_white, void* stream) {
+    if ((bs != 8 && bs != 6) || n < 0 ||
+        (n > 0 && (!black || !white || !sym || !out_black || !out_white)))
+        return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    dim3 grid(blocks_for(n, SYM_THREADS)), block(SYM_THREADS);
+    if (bs == 8)
+        hipLaunchKernelGGL(k_board_symmetry<8>, grid, block, 0, (hipStream_t)stream, n, black,
+                           white, sym, out_black, out_white);
+    else
+        hipLaunchKernelGGL(k_board_symmetry<6>, grid, block, 0, (hipStream_t)stream, n, black,
+                           white, sym, out_black, out_white);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}
+
+extern "C" int rvz_training_rows(int32_t bs, int32_t n, const uint64_t* black,
+                                 const uint64_t* white, const int32_t* status, const float* policy,
+                                 const int32_t* sym, int32_t fan, float* out_states,
+                                 float* out_policy, int32_t* out_quirk, void* stream) {
+    if ((bs != 8 && bs != 6) || n < 0 || (fan != 1 && fan != 8)) return RVZ_EINVAL;
+    if ((int64_t)n * fan * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
+    if (n > 0 && (!black || !white || !status || !policy || !out_states || !out_policy ||
+                  (fan == 1 && !sym) || ((uintptr_t)out_states & 15u) != 0))   // float4 stores
+        return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    dim3 grid(blocks_for(n, SYM_WAVES)), block(SYM_THREADS);
+    hipStream_t s = (hipStream_t)stream;
+#define RVZ_SYM_LAUNCH(BS, FAN)                                                                  \
+    hipLaunchKernelGGL((k_training_rows<BS, FAN>), grid, block, 0, s, n, black, white, status,   \
+                       policy, sym, out_states, out_policy, out_quirk)
+    if (bs == 8) {
+        if (fan == 1) RVZ_SYM_LAUNCH(8, 1); else RVZ_SYM_LAUNCH(8, 8);
+    } else {
+        if (fan == 1) RVZ_SYM_LAUNCH(6, 1); else RVZ_SYM_LAUNCH(6, 8);
+    }
+#undef RVZ_SYM_LAUNCH
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}

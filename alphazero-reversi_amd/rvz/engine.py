@@ -14,6 +14,7 @@ the current torch stream of that device (graph-capturable: no host syncs inside 
 from __future__ import annotations
 
 import ctypes as C
+import numbers
 from typing import Callable, Optional, Sequence, Tuple
 
 import torch
@@ -574,6 +575,111 @@ def board_canonical(black: torch.Tensor, white: torch.Tensor, status: torch.Tens
     check(lib.rvz_board_canonical(board_size, n, ptr(black), ptr(white), ptr(status), ptr(out),
                                   _lib.stream_handle(black.device)), None, "rvz_board_canonical")
     return out
+
+
+# ------------------------------------------------------------------ board symmetries
+# include/rvz.h: k = 4*f + r, T_k(x) = fliplr(rot90(x, r)) if f else rot90(x, r);
+# T_k(x)[i][j] = x[_sym_src(k, i, j, S)]
+def _sym_src(k: int, i: int, j: int, S: int):
+    if k & 4:
+        j = S - 1 - j
+    return ((i, j), (j, S - 1 - i), (S - 1 - i, S - 1 - j), (S - 1 - j, i))[k & 3]
+
+
+# each T_k as the permutation of a 3x3 board's squares (3x3 tells all eight apart)
+_SYM_PERMS = [tuple(3 * a + b for a, b in (_sym_src(k, i, j, 3) for i in range(3) for j in range(3)))
+              for k in range(8)]
+
+
+def _sym_index(k, what: str) -> int:
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= k < 8:
+        raise RvzError(f"{what}: a symmetry is an int in [0, 8), not {k!r}")
+    return int(k)
+
+
+def symmetry_compose(a: int, b: int) -> int:
+    """The symmetry c with T_c(x) == T_a(T_b(x)) for every board x (b is applied first)."""
+    a, b = _sym_index(a, "symmetry_compose"), _sym_index(b, "symmetry_compose")
+    # T_a(T_b(x))[s] = T_b(x)[src_a(s)] = x[src_b(src_a(s))]
+    return _SYM_PERMS.index(tuple(_SYM_PERMS[b][s] for s in _SYM_PERMS[a]))
+
+
+def symmetry_inverse(k: int) -> int:
+    """The symmetry c with T_c(T_k(x)) == x for every board x."""
+    k = _sym_index(k, "symmetry_inverse")
+    return next(c for c in range(8) if symmetry_compose(c, k) == 0)
+
+
+def board_symmetry(black: torch.Tensor, white: torch.Tensor, sym: torch.Tensor,
+                   board_size: int = 8):
+    """rvz_board_symmetry: the images of n boards under the eight symmetries of the square board
+    (include/rvz.h has the numbering). black / white int64 [n] (bit patterns), sym [n] integers,
+    device tensors. Returns (black', white') int64 [n]: row i transformed by T_sym[i]; both 0 for
+    a sym[i] outside [0, 8). On 6x6 input bits at or above 36 are ignored."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    lib = _lib.load()
+    n = black.numel()
+    if black.dim() != 1 or white.shape != (n,) or sym.shape != (n,):
+        raise RvzError("board_symmetry: black, white and sym hold one entry per board")
+    if black.dtype != torch.int64 or white.dtype != torch.int64:
+        raise RvzError("board_symmetry: black and white are int64 bit patterns")
+    if sym.dtype.is_floating_point or sym.dtype == torch.bool:
+        raise RvzError("board_symmetry: sym holds integers")
+    dev = black.device
+    b, w = black.contiguous(), white.to(dev).contiguous()
+    sy = sym.to(dev, torch.int32).contiguous()
+    ob, ow = torch.empty_like(b), torch.empty_like(w)
+    if n:
+        check(lib.rvz_board_symmetry(board_size, n, ptr(b), ptr(w), ptr(sy), ptr(ob), ptr(ow),
+                                     _lib.stream_handle(dev)), None, "rvz_board_symmetry")
+    return ob, ow
+
+
+def training_rows(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
+                  policy: torch.Tensor, sym: Optional[torch.Tensor] = None, board_size: int = 8,
+                  all_images: bool = False, quirk: bool = False):
+    """rvz_training_rows: augmented training rows straight from the bitboards. black / white
+    int64 [n], status int32 [n, 4] (only the side is read), policy float32 [n, S*S+1], device
+    tensors. all_images=False: sym [n] integers, output row i is row i's image under T_sym[i].
+    all_images=True: sym is ignored, output row 8*i + k is the image under T_k (rows [::8] are the
+    untransformed rows). Returns (states float32 [m, 3, S, S], policy float32 [m, S*S+1]) with
+    m = n or 8*n, and with quirk=True also quirk int32 [m]: 1 where the engine's own legal mask of
+    the image position differs from the image of the original's mask (the third plane is always
+    the latter), 0 where they agree, -1 for a row whose sym is outside [0, 8) (a zero row)."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    npol = board_size * board_size + 1
+    lib = _lib.load()
+    n = black.numel()
+    if black.dim() != 1 or white.shape != (n,) or status.shape != (n, 4):
+        raise RvzError("training_rows: black and white hold one entry per row, status is [n, 4]")
+    if black.dtype != torch.int64 or white.dtype != torch.int64:
+        raise RvzError("training_rows: black and white are int64 bit patterns")
+    if policy.shape != (n, npol) or policy.dtype != torch.float32:
+        raise RvzError(f"training_rows: policy must be float32 [n, {npol}]")
+    fan = 8 if all_images else 1
+    if n * fan * npol >= 2 ** 31:
+        raise RvzError("training_rows: n * fan * (S*S + 1) does not fit int32")
+    dev = black.device
+    sy = None
+    if not all_images:
+        if sym is None or sym.shape != (n,) or sym.dtype.is_floating_point or \
+                sym.dtype == torch.bool:
+            raise RvzError("training_rows: sym holds one integer per row (or pass all_images=True)")
+        sy = sym.to(dev, torch.int32).contiguous()
+    b, w = black.contiguous(), white.to(dev).contiguous()
+    st = status.to(dev, torch.int32).contiguous()
+    pol = policy.to(dev).contiguous()
+    states = torch.empty(n * fan, 3, board_size, board_size, dtype=torch.float32, device=dev)
+    out_p = torch.empty(n * fan, npol, dtype=torch.float32, device=dev)
+    q = torch.empty(n * fan, dtype=torch.int32, device=dev) if quirk else None
+    if n:
+        check(lib.rvz_training_rows(board_size, n, ptr(b), ptr(w), ptr(st), ptr(pol),
+                                    ptr(sy) if sy is not None else None, fan, ptr(states),
+                                    ptr(out_p), ptr(q) if quirk else None,
+                                    _lib.stream_handle(dev)), None, "rvz_training_rows")
+    return (states, out_p, q) if quirk else (states, out_p)
 
 
 def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor, salt: int,

@@ -41,7 +41,8 @@ class SelfPlayTrainer:
                  root_noise=None, temperature_schedule=None, exact_endgame: int = 0,
                  exact_node_limit: int = 2 ** 24, exact_wld: bool = False,
                  adjudicate_empties: int = 0, adjudicate_node_limit: int = 2 ** 24,
-                 exact_policy: int = 0):
+                 exact_policy: int = 0, symmetries: Optional[str] = None,
+                 symmetry_seed: Optional[int] = None):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -64,6 +65,16 @@ class SelfPlayTrainer:
         adjudicate_node_limit positions is dropped from the iteration's data). The last N plies
         are not searched and yield no training rows; every row's value target is the perfect-play
         outcome from the stopping position.
+        symmetries: None (off), "all" or "random": board symmetry augmentation of the iteration's
+        training rows (records_to_training; the rvz_training_rows HIP kernel), in generate() and
+        with adjudication on alike. "all" turns every row into its 8 images and so multiplies the
+        memory of the data by 8: about 16 GB for C4's 32,768 games per rank (some 2 M rows of
+        1032 B become 16 M). "random" keeps one image per row, at the memory of before: the
+        setting meant for large runs. symmetry_seed: the seed of "random"'s draws; None (the
+        default) is seed + iteration, spread over ranks as train_epoch spreads its seed
+        ((seed + iteration) * world + rank); an int is used as given, every iteration.
+        run_iteration reports symmetry_rows and symmetry_quirk_rows (the rows whose third plane,
+        the image of the original's legal mask, differs from the engine's own mask of the image).
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
@@ -79,6 +90,10 @@ class SelfPlayTrainer:
         self.exact_policy = int(exact_policy)
         if not 0 <= self.exact_policy <= SOLVE_MAX_EMPTIES:
             raise ValueError(f"exact_policy must be in [0, {SOLVE_MAX_EMPTIES}]")
+        if symmetries not in (None, "all", "random"):
+            raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
+        self.symmetries = symmetries
+        self.symmetry_seed = None if symmetry_seed is None else int(symmetry_seed)
         self.adjudicate_empties = int(adjudicate_empties)
         self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
@@ -122,6 +137,12 @@ class SelfPlayTrainer:
         self.runner.seeds.copy_(torch.arange(self.games, dtype=torch.int64,
                                              device=self.device) + base)
 
+    def _symmetry_args(self) -> dict:
+        seed = self.symmetry_seed
+        if seed is None:
+            seed = (self.seed + self.iteration) * self.world + self.rank
+        return {"symmetries": self.symmetries, "symmetry_seed": seed}
+
     def generate(self) -> Dict[str, torch.Tensor]:
         """One iteration's self-play: every game of this rank from the start to its end.
         Returns the training arrays (states, policy_targets, value_targets) on the device."""
@@ -145,7 +166,8 @@ class SelfPlayTrainer:
                                    run.rec_p, run.post_status, self.eng.board_size,
                                    exact_endgame=self.exact_endgame,
                                    exact_node_limit=self.exact_node_limit,
-                                   exact_wld=self.exact_wld, exact_policy=self.exact_policy)
+                                   exact_wld=self.exact_wld, exact_policy=self.exact_policy,
+                                   **self._symmetry_args())
 
     def _adjudicated(self, plies: int) -> Dict[str, torch.Tensor]:
         """generate()'s tail with adjudication on: the games stand after `plies` plies."""
@@ -165,7 +187,8 @@ class SelfPlayTrainer:
                                   run.rec_side[:plies], rec_idx, run.rec_p[:plies], final,
                                   eng.board_size, exact_endgame=self.exact_endgame,
                                   exact_node_limit=self.exact_node_limit,
-                                  exact_wld=self.exact_wld, exact_policy=self.exact_policy)
+                                  exact_wld=self.exact_wld, exact_policy=self.exact_policy,
+                                  **self._symmetry_args())
         out.update(stats)
         return out
 
@@ -202,5 +225,7 @@ class SelfPlayTrainer:
                     "exact_policy_unsolved": int(data.get("exact_policy_unsolved", 0)),
                     "adjudicated": int(data.get("adjudicated", 0)),
                     "adjudicate_unsolved": int(data.get("adjudicate_unsolved", 0)),
-                    "already_over": int(data.get("already_over", 0))})
+                    "already_over": int(data.get("already_over", 0)),
+                    "symmetry_rows": int(data.get("symmetry_rows", 0)),
+                    "symmetry_quirk_rows": int(data.get("symmetry_quirk_rows", 0))})
         return out

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
-                     solve_moves, solve_moves_wld, solve_wld)
+                     solve_moves, solve_moves_wld, solve_wld, training_rows)
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
@@ -31,7 +31,8 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
                         board_size: int = 8, canonical=None, exact_endgame: int = 0,
                         solver=None, exact_node_limit: int = 2 ** 24,
                         exact_wld: bool = False, exact_policy: int = 0,
-                        moves_solver=None) -> Dict[str, torch.Tensor]:
+                        moves_solver=None, symmetries: Optional[str] = None,
+                        symmetry_seed: int = 0, augment=None) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -64,7 +65,23 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     rvz.solve_moves (the rvz_solve_moves HIP kernel) at the full window, or with exact_wld
     rvz.solve_moves_wld and the window (-1, 1) (optimal then means: of the best win / draw / loss
     class), both with node_limit = exact_node_limit. A replacement is read at that same window.
+    symmetries: None (the default: off, the keys and bytes of before), "all" or "random": board
+    symmetry augmentation (include/rvz.h has the numbering T_0 .. T_7). It runs last, on the final
+    policy and value targets, after the exact_endgame / exact_policy replacements. "all": every
+    kept record becomes 8 rows, row 8*i + k its image under T_k (rows [::8] are the rows of
+    symmetries=None), the value target repeated. "random": one image per kept record, sym drawn
+    with torch.randint(0, 8, ...) from a CPU torch.Generator seeded with symmetry_seed, so the
+    result is a pure function of the records and the seed. The states of an image are the images
+    of the original's three planes: its third plane is the image of the original's legal mask
+    (policy mass only where it is 1), not the engine's own mask of the image position, which can
+    differ because move generation wraps around the board edges. Two more keys then, 0-d int64
+    device tensors (no host synchronisation): "symmetry_rows", the rows after augmentation, and
+    "symmetry_quirk_rows", the rows where those two masks differ. `canonical` is not called.
+    augment(black, white, status, policy, sym, board_size, all_images) -> (states, policy, quirk):
+    default rvz.training_rows (the rvz_training_rows HIP kernel) with quirk=True.
     """
+    if symmetries not in (None, "all", "random"):
+        raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
     if canonical is None:
         canonical = board_canonical
     P, G = rec_idx.shape
@@ -74,7 +91,7 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     side = rec_side.t().reshape(-1)[live]
     st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
                       torch.zeros_like(side)], dim=1).to(torch.int32).contiguous()
-    states = canonical(black, white, st, board_size)
+    states = canonical(black, white, st, board_size) if symmetries is None else None
     policy = rec_p.permute(1, 0, 2).reshape(P * G, -1)[live].to(torch.float32)
     winner = final_status[:, 2].to(torch.int32).unsqueeze(0).expand(P, G).t().reshape(-1)[live]
     over = final_status[:, 1].unsqueeze(0).expand(P, G).t().reshape(-1)[live]
@@ -104,6 +121,23 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
         out["policy_targets"] = torch.where(complete.unsqueeze(1), exact, policy)
         out["exact_policy_rows"] = complete.sum()
         out["exact_policy_unsolved"] = ((count >= 1) & (scores == SOLVE_ABANDONED).any(dim=1)).sum()
+    if symmetries is not None:
+        if augment is None:
+            def augment(b, w, s, p, sym, bs, all_images):
+                return training_rows(b, w, s, p, sym, bs, all_images, quirk=True)
+        every = symmetries == "all"
+        sym = None
+        if not every:
+            g = torch.Generator().manual_seed(int(symmetry_seed))
+            sym = torch.randint(0, 8, (black.numel(),), generator=g,
+                                dtype=torch.int32).to(black.device)
+        out["states"], out["policy_targets"], quirk = augment(
+            black, white, st, out["policy_targets"].contiguous(), sym, board_size, every)
+        if every:
+            out["value_targets"] = out["value_targets"].repeat_interleave(8, dim=0)
+        out["symmetry_rows"] = torch.tensor(out["states"].shape[0], dtype=torch.int64,
+                                            device=out["states"].device)
+        out["symmetry_quirk_rows"] = (quirk == 1).sum()
     return out
 
 

@@ -416,6 +416,65 @@ int rvz_alphabeta(int32_t board_size, int32_t n, const uint64_t *black, const ui
                   int64_t node_limit, int32_t *out_score, int32_t *out_move,
                   int64_t *out_nodes /* nullable */, void *hip_stream);
 
+/* ---- board symmetries of training records -------------------------------------------------
+ * The eight symmetries of the square board (csrc/rvz_symmetry.hip), for augmenting self-play
+ * records: a position, its search policy and its outcome have seven equally valid mirror and
+ * rotation images. Numbering, used everywhere: k = 4*f + r with r in [0, 4), f in {0, 1}, and for
+ * an [S][S] array x indexed (row, col)
+ *   T_k(x) = np.fliplr(np.rot90(x, r)) if f else np.rot90(x, r)        (NumPy is the definition)
+ * In coordinates, T_k(x)[i][j] = x[src_k(i, j)] with
+ *   k = 0: (i, j)            k = 1: (j, S-1-i)        k = 2: (S-1-i, S-1-j)    k = 3: (S-1-j, i)
+ *   k = 4: (i, S-1-j)        k = 5: (S-1-j, S-1-i)    k = 6: (S-1-i, j)        k = 7: (j, i)
+ * so T_0 is the identity, T_4 mirrors the columns, T_6 the rows, T_7 is the transpose and T_5 the
+ * anti-transpose. A bitboard is the [S][S] 0/1 array with square s = row*S + col at bit s. A
+ * policy row of S*S+1 entries transforms its first S*S entries as an [S][S] array; entry S*S, the
+ * pass, stays in place.
+ * The engine's rules are NOT symmetric: move generation applies no file masks (board.py:102-124),
+ * so lines wrap around the board edges, and for some positions legal(T(pos)) != T(legal(pos)).
+ * rvz_training_rows defines the third input plane of an image as the IMAGE OF THE ORIGINAL'S legal
+ * mask, which keeps every sample consistent with its policy target (mass only where plane 3 is 1),
+ * and reports through out_quirk the rows where the engine's own mask of the image position differs.
+ * Both entry points are stateless, on caller arrays (device pointers), asynchronous on hip_stream
+ * and graph-capturable: no allocation, no copy, no synchronisation, no table in memory. */
+/* The images of n boards, one lane per board, transformed in registers (8x8: a transpose by three
+ * delta swaps, a bit reversal and a byte swap; 6x6: a bit gather). black / white uint64 [n],
+ * sym int32 [n]; out_black[i] / out_white[i] = T_sym[i] of row i's two bitboards. On 6x6 input
+ * bits at or above 36 are ignored and no such bit is ever set in an output. out_black / out_white
+ * may be exactly black / white (in place); any other overlap is undefined. A sym[i] outside
+ * [0, 8) writes 0 to both outputs of that row (checked in the kernel, no host synchronisation).
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, a null pointer with n > 0.
+ * n = 0 returns RVZ_OK without a launch. */
+int rvz_board_symmetry(int32_t board_size, int32_t n, const uint64_t *black,
+                       const uint64_t *white, const int32_t *sym, uint64_t *out_black,
+                       uint64_t *out_white, void *hip_stream);
+/* Augmented training rows straight from the bitboards, one wavefront per input row, lane = output
+ * square; every output byte is written once. black / white uint64 [n], status int32 [n][4] (only
+ * the side is read, as rvz_board_canonical), policy float32 [n][S*S+1], sym int32 [n], fan 1 | 8.
+ *   fan = 1: output row i is the image of input row i under T_sym[i];
+ *   fan = 8: sym is ignored (may be NULL); output row 8*i + k is the image under T_k, so rows
+ *            0, 8, 16, ... are the untransformed rows.
+ * out_states float32 [n*fan][3][S][S], 16-byte aligned: T applied to each of the three planes
+ * rvz_board_canonical writes for the ORIGINAL position (mover, opponent, the engine's legal mask
+ * of the original); for k = 0 the bytes are rvz_board_canonical's.
+ * out_policy float32 [n*fan][S*S+1]: the permuted row, out[s] = policy[src_k(s)] for s < S*S and
+ * out[S*S] = policy[S*S]; the values are moved, never recomputed.
+ * out_quirk (nullable) int32 [n*fan]: 1 when the engine's legal mask of the image position (mover
+ * T(P), opponent T(O)) differs from the image of the original's mask (the wrap-around quirk), 0
+ * when they agree, -1 for a row whose sym is outside [0, 8); that row's states and policy are all
+ * zero (fan = 1 only; checked in the kernel, no host synchronisation).
+ * Every output element of all n*fan rows is written by exactly one lane (no pre-fill needed). A
+ * row's outputs depend on that row and its sym alone, not on n, the row's index or its neighbours.
+ * The outputs must not overlap the inputs or each other.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, fan not 1 | 8,
+ * n * fan * (S*S + 1) not fitting in int32, and with n > 0 a null black / white / status / policy /
+ * out_states / out_policy, a null sym with fan = 1, or an out_states that is not 16-byte aligned.
+ * n = 0 returns RVZ_OK without a launch. */
+int rvz_training_rows(int32_t board_size, int32_t n, const uint64_t *black, const uint64_t *white,
+                      const int32_t *status, const float *policy,
+                      const int32_t *sym /* nullable with fan = 8 */, int32_t fan,
+                      float *out_states, float *out_policy, int32_t *out_quirk /* nullable */,
+                      void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
