@@ -682,6 +682,69 @@ def training_rows(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor
     return (states, out_p, q) if quirk else (states, out_p)
 
 
+def merge_positions(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
+                    policy: torch.Tensor, value: torch.Tensor, board_size: int = 8,
+                    table_log2: int = 0, trim: bool = True):
+    """rvz_merge_positions: one row per distinct position, carrying the mean of the targets of all
+    its occurrences. black / white int64 [n], status int32 [n, 4] (only the side is read), policy
+    float32 [n, S*S+1] in [0, 1], value float32 [n] or [n, 1] in [-1, 1], device tensors. Two rows
+    are the same position iff their (mover, opponent) bitboards are equal, so a row and its
+    colour-swapped twin merge. Returns a dict: "m" the number of distinct positions, and for the
+    m positions in order of first occurrence "first" int32 (the lowest input row of the group),
+    "count" int32 (its members), "policy" float32 [m, S*S+1] and "value" float32 [m] (the means,
+    summed in fixed point: bitwise reproducible; a group of one keeps its row's bits); "group"
+    int32 [n] maps every input row to its output row, -1 for a malformed row (overlapping discs,
+    bits off the board, a side other than 1 or 2, a target out of range or NaN), which joins no
+    group. trim=True: m is an int and the four per-position arrays are sliced to m, at the cost of
+    the function's one host read. trim=False: they are returned at length n with the rows from m
+    on unwritten, m is a 0-d int32 device tensor and nothing synchronises (with n = 0, m is 0).
+    table_log2: 0 for the default hash table, else a table of 2^table_log2 > n slots; the
+    results do not depend on it."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    npol = board_size * board_size + 1
+    lib = _lib.load()
+    n = black.numel()
+    if black.dim() != 1 or white.shape != (n,) or status.shape != (n, 4):
+        raise RvzError("merge_positions: black and white hold one entry per row, status is [n, 4]")
+    if black.dtype != torch.int64 or white.dtype != torch.int64:
+        raise RvzError("merge_positions: black and white are int64 bit patterns")
+    if policy.shape != (n, npol) or policy.dtype != torch.float32:
+        raise RvzError(f"merge_positions: policy must be float32 [n, {npol}]")
+    if value.shape not in ((n,), (n, 1)) or value.dtype != torch.float32:
+        raise RvzError("merge_positions: value must be float32 [n] or [n, 1]")
+    if n * npol >= 2 ** 31:
+        raise RvzError("merge_positions: n * (S*S + 1) does not fit int32")
+    if isinstance(table_log2, bool) or not isinstance(table_log2, numbers.Integral):
+        raise RvzError(f"merge_positions: table_log2 is an int, not {table_log2!r}")
+    size = lib.rvz_merge_scratch_size(board_size, n, int(table_log2))
+    if size < 0:
+        raise RvzError(f"merge_positions: table_log2 = {table_log2} must be 0 or give more than "
+                       f"n = {n} slots (at most 2^30)")
+    dev = black.device
+    b, w = black.contiguous(), white.to(dev).contiguous()
+    st = status.to(dev, torch.int32).contiguous()
+    pol = policy.to(dev).contiguous()
+    val = value.to(dev).reshape(n).contiguous()
+    m = torch.zeros((), dtype=torch.int32, device=dev)
+    first = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(n, dtype=torch.int32, device=dev)
+    out_p = torch.empty(n, npol, dtype=torch.float32, device=dev)
+    out_v = torch.empty(n, dtype=torch.float32, device=dev)
+    group = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
+        check(lib.rvz_merge_positions(board_size, n, ptr(b), ptr(w), ptr(st), ptr(pol), ptr(val),
+                                      int(table_log2), ptr(scratch), ptr(m), ptr(first),
+                                      ptr(count), ptr(out_p), ptr(out_v), ptr(group),
+                                      _lib.stream_handle(dev)), None, "rvz_merge_positions")
+    if trim:
+        m = int(m.item())
+        first, count, out_p, out_v = first[:m], count[:m], out_p[:m], out_v[:m]
+    return {"m": m, "first": first, "count": count, "policy": out_p, "value": out_v,
+            "group": group}
+
+
 def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor, salt: int,
                     alpha: float, board_size: int = 8, bits: bool = False):
     """rvz_dirichlet_noise: the eta rows Engine.root_noise mixes into the roots' priors, by the

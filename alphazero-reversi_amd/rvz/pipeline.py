@@ -42,7 +42,7 @@ class SelfPlayTrainer:
                  exact_node_limit: int = 2 ** 24, exact_wld: bool = False,
                  adjudicate_empties: int = 0, adjudicate_node_limit: int = 2 ** 24,
                  exact_policy: int = 0, symmetries: Optional[str] = None,
-                 symmetry_seed: Optional[int] = None):
+                 symmetry_seed: Optional[int] = None, merge_positions: bool = False):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -75,6 +75,13 @@ class SelfPlayTrainer:
         ((seed + iteration) * world + rank); an int is used as given, every iteration.
         run_iteration reports symmetry_rows and symmetry_quirk_rows (the rows whose third plane,
         the image of the original's legal mask, differs from the engine's own mask of the image).
+        merge_positions: True merges the iteration's records into one training row per distinct
+        position (records_to_training; the rvz_merge_positions HIP kernels), carrying the mean
+        search policy and the mean outcome of all its occurrences and, under "position_counts",
+        their number: the start position is one row, not one per game. It runs before
+        `symmetries`, in generate() and with adjudication on alike. train_epoch walks the merged
+        rows unweighted, so every distinct position is seen once per pass. run_iteration reports
+        merge_rows and merge_input_rows (0 when off).
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
@@ -94,6 +101,7 @@ class SelfPlayTrainer:
             raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
         self.symmetries = symmetries
         self.symmetry_seed = None if symmetry_seed is None else int(symmetry_seed)
+        self.merge_positions = bool(merge_positions)
         self.adjudicate_empties = int(adjudicate_empties)
         self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
@@ -143,6 +151,9 @@ class SelfPlayTrainer:
             seed = (self.seed + self.iteration) * self.world + self.rank
         return {"symmetries": self.symmetries, "symmetry_seed": seed}
 
+    def _merge_args(self) -> dict:
+        return {"merge_positions": True} if self.merge_positions else {}
+
     def generate(self) -> Dict[str, torch.Tensor]:
         """One iteration's self-play: every game of this rank from the start to its end.
         Returns the training arrays (states, policy_targets, value_targets) on the device."""
@@ -167,7 +178,7 @@ class SelfPlayTrainer:
                                    exact_endgame=self.exact_endgame,
                                    exact_node_limit=self.exact_node_limit,
                                    exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                   **self._symmetry_args())
+                                   **self._symmetry_args(), **self._merge_args())
 
     def _adjudicated(self, plies: int) -> Dict[str, torch.Tensor]:
         """generate()'s tail with adjudication on: the games stand after `plies` plies."""
@@ -188,7 +199,7 @@ class SelfPlayTrainer:
                                   eng.board_size, exact_endgame=self.exact_endgame,
                                   exact_node_limit=self.exact_node_limit,
                                   exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                  **self._symmetry_args())
+                                  **self._symmetry_args(), **self._merge_args())
         out.update(stats)
         return out
 
@@ -227,5 +238,7 @@ class SelfPlayTrainer:
                     "adjudicate_unsolved": int(data.get("adjudicate_unsolved", 0)),
                     "already_over": int(data.get("already_over", 0)),
                     "symmetry_rows": int(data.get("symmetry_rows", 0)),
-                    "symmetry_quirk_rows": int(data.get("symmetry_quirk_rows", 0))})
+                    "symmetry_quirk_rows": int(data.get("symmetry_quirk_rows", 0)),
+                    "merge_rows": int(data.get("merge_rows", 0)),
+                    "merge_input_rows": int(data.get("merge_input_rows", 0))})
         return out

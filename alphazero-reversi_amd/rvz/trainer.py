@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
                      solve_moves, solve_moves_wld, solve_wld, training_rows)
+from .engine import merge_positions as _merge_positions
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
@@ -32,7 +33,8 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
                         solver=None, exact_node_limit: int = 2 ** 24,
                         exact_wld: bool = False, exact_policy: int = 0,
                         moves_solver=None, symmetries: Optional[str] = None,
-                        symmetry_seed: int = 0, augment=None) -> Dict[str, torch.Tensor]:
+                        symmetry_seed: int = 0, augment=None, merge_positions: bool = False,
+                        merger=None) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -79,6 +81,21 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     "symmetry_quirk_rows", the rows where those two masks differ. `canonical` is not called.
     augment(black, white, status, policy, sym, board_size, all_images) -> (states, policy, quirk):
     default rvz.training_rows (the rvz_training_rows HIP kernel) with quirk=True.
+    merge_positions = True (the default False is off: the keys and bytes of before): one row per
+    distinct position, two records being the same position iff their (mover, opponent) bitboards
+    are equal (their states are then equal too). It runs after the exact_endgame / exact_policy
+    replacements (exact targets are functions of the position, so a group's members agree and
+    their mean reproduces them) and before `symmetries`, which then work on each group's first
+    record and the merged policy. The rows are the distinct positions in order of first
+    occurrence: states the canonical planes of each group's first record (`canonical` is called
+    on those alone), policy_targets and value_targets the means over the group, summed in fixed
+    point and so bitwise reproducible (include/rvz.h); a position recorded once keeps its targets
+    bit for bit. Three more keys then: "position_counts" int32 [rows], each row's number of
+    records (repeated 8 times under symmetries="all"), and two 0-d int64 device tensors,
+    "merge_rows", the rows after merging, and "merge_input_rows", the records merged. Reading the
+    number of rows is this option's one host synchronisation.
+    merger(black, white, status, policy, value, board_size) -> dict with "m", "first", "count",
+    "policy", "value": default rvz.merge_positions (the rvz_merge_positions HIP kernels).
     """
     if symmetries not in (None, "all", "random"):
         raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
@@ -91,7 +108,8 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     side = rec_side.t().reshape(-1)[live]
     st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
                       torch.zeros_like(side)], dim=1).to(torch.int32).contiguous()
-    states = canonical(black, white, st, board_size) if symmetries is None else None
+    states = (canonical(black, white, st, board_size)
+              if symmetries is None and not merge_positions else None)
     policy = rec_p.permute(1, 0, 2).reshape(P * G, -1)[live].to(torch.float32)
     winner = final_status[:, 2].to(torch.int32).unsqueeze(0).expand(P, G).t().reshape(-1)[live]
     over = final_status[:, 1].unsqueeze(0).expand(P, G).t().reshape(-1)[live]
@@ -121,6 +139,22 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
         out["policy_targets"] = torch.where(complete.unsqueeze(1), exact, policy)
         out["exact_policy_rows"] = complete.sum()
         out["exact_policy_unsolved"] = ((count >= 1) & (scores == SOLVE_ABANDONED).any(dim=1)).sum()
+    if merge_positions:
+        if merger is None:
+            merger = _merge_positions
+        rows_in = black.numel()
+        merged = merger(black, white, st, out["policy_targets"].contiguous(),
+                        out["value_targets"].reshape(-1).contiguous(), board_size)
+        m = int(merged["m"])
+        first = merged["first"][:m].to(black.device, torch.int64)
+        black, white, st = (t[first].contiguous() for t in (black, white, st))
+        if symmetries is None:
+            out["states"] = canonical(black, white, st, board_size)
+        out["policy_targets"] = merged["policy"][:m]
+        out["value_targets"] = merged["value"][:m].reshape(-1, 1)
+        out["position_counts"] = merged["count"][:m]
+        out["merge_rows"] = torch.tensor(m, dtype=torch.int64, device=black.device)
+        out["merge_input_rows"] = torch.tensor(rows_in, dtype=torch.int64, device=black.device)
     if symmetries is not None:
         if augment is None:
             def augment(b, w, s, p, sym, bs, all_images):
@@ -135,6 +169,8 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
             black, white, st, out["policy_targets"].contiguous(), sym, board_size, every)
         if every:
             out["value_targets"] = out["value_targets"].repeat_interleave(8, dim=0)
+            if merge_positions:
+                out["position_counts"] = out["position_counts"].repeat_interleave(8)
         out["symmetry_rows"] = torch.tensor(out["states"].shape[0], dtype=torch.int64,
                                             device=out["states"].device)
         out["symmetry_quirk_rows"] = (quirk == 1).sum()

@@ -475,6 +475,53 @@ int rvz_training_rows(int32_t board_size, int32_t n, const uint64_t *black, cons
                       float *out_states, float *out_policy, int32_t *out_quirk /* nullable */,
                       void *hip_stream);
 
+/* ---- one training row per distinct position ----------------------------------------------
+ * Self-play plays many games at once, so the same position is recorded many times (the start
+ * position once per game), each time with another noisy search policy and another outcome.
+ * rvz_merge_positions (csrc/rvz_merge.hip) turns n records into one row per distinct position,
+ * carrying the mean of the members' targets.
+ * Identity: with P the mover's bitboard and O the opponent's (P = side == 1 ? black : white, as
+ * rvz_board_canonical), two rows are the same position iff their (P, O) are equal: the network's
+ * three input planes are functions of (P, O), and the targets are relative to the mover. A
+ * black-to-move row and its colour-swapped white-to-move twin therefore merge. Of status only
+ * the side is read.
+ * Order: output row j is the j-th distinct position in order of first occurrence; out_first[j] is
+ * the lowest input index of its group (strictly increasing in j), out_count[j] its members,
+ * out_group[i] the output row of input row i. Rows at and above m = *out_m of out_first,
+ * out_count, out_policy and out_value are not written.
+ * Sums: fixed point, so that no result depends on the order of the hardware's adds. With
+ * q(x) = (int64) rint((double) x * 2^36) (the product is exact), entry e of a group of c members
+ * is (float) ((double) sum of q(x_e) / ((double) c * 2^36)), the division and both conversions
+ * IEEE round-to-nearest; |sum| < 2^61. A group of one member copies its row's policy and value
+ * bit for bit (moved, never recomputed), so merging all-distinct rows is the identity.
+ * A row is malformed if black & white != 0, a bit at or above S*S is set, the side is not 1 or 2,
+ * a policy entry is outside [0, 1] or the value outside [-1, 1] (NaN fails both): it gets
+ * out_group -1, joins no group and is not counted in m (checked in the kernel, no host
+ * synchronisation).
+ * A row's group and every group's outputs depend on the inputs alone, not on timing, the launch
+ * geometry or table_log2. Device pointers, asynchronous on hip_stream, graph-capturable: no
+ * allocation, no copy, no memset, no synchronisation; the scratch needs no preparation. Outputs
+ * must not overlap the inputs, the scratch or each other.
+ * table_log2: 0 for the default hash table (the smallest power of two >= 2n slots), else 2^table_log2
+ * slots, which must exceed n (tests force long probe chains with it). The scratch holds the
+ * table, five int32 per row and 8 * (S*S + 2) bytes of sums for each of at most n / 2 groups of
+ * two or more.
+ * The environment variable RVZ_MERGE_HOT=0 (experiments) turns off the per-workgroup LDS
+ * pre-reduction of large groups' sums; the results are the same bytes.
+ * rvz_merge_scratch_size: the scratch's bytes, non-decreasing in n; negative for bad arguments.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, n * (S*S + 1) >= 2^31, a
+ * table_log2 that is negative, above 30 or gives no more than n slots, and with n > 0 a null
+ * pointer or a scratch that is not 16-byte aligned. n = 0 returns RVZ_OK without a launch, and
+ * then nothing, *out_m included, is written. */
+int64_t rvz_merge_scratch_size(int32_t board_size, int32_t n, int32_t table_log2);
+int rvz_merge_positions(int32_t board_size, int32_t n, const uint64_t *black,
+                        const uint64_t *white, const int32_t *status /* [n][4] */,
+                        const float *policy /* [n][S*S+1] */, const float *value /* [n] */,
+                        int32_t table_log2, void *scratch, int32_t *out_m /* [1] */,
+                        int32_t *out_first /* [n] */, int32_t *out_count /* [n] */,
+                        float *out_policy /* [n][S*S+1] */, float *out_value /* [n] */,
+                        int32_t *out_group /* [n] */, void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
