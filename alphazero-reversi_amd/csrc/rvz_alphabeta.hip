@@ -8,13 +8,15 @@
 // the first maximum kept. h is the caller's square table plus a mobility term, T the final disc
 // difference pushed beyond every h by RVZ_AB_WIN.
 //
-// Shape: rvz_solve.hip's (its head has the reasons): one position per LANE, persistent lanes
-// that take the next row from a per-call device counter in the iteration that finishes a row, an
-// explicit stack in LDS laid out [depth][field][lane] in dwords, so a wave's access to one field
-// of one depth covers 64 consecutive banks. No recursion, no run-time-indexed register array:
-// the kernel uses no scratch. It is its own state machine and not a mode of solve_rows: the
-// solver bounds its stack by the empty squares and packs alpha / beta / best as int8; here the
-// bound is the caller's depth, and a score needs 16 bits.
+// Shape: rvz_solve.hip's: one position per LANE, persistent lanes that take the next row from a
+// per-call device counter in the iteration that finishes a row, an explicit stack in LDS laid
+// out [depth][field][lane] in dwords, no recursion, no run-time-indexed register array, no
+// scratch. The head of rvz_negamax.hip.h has the reasons; that header holds what the two files
+// have in common around their loops (geometry, the stack's size, the row counter, of which this
+// translation unit has a copy of its own, and the host side of a launch) and says why the loops
+// are two texts. This one is its own state machine and not a mode of solve_rows: the solver
+// bounds its stack by the empty squares and packs alpha / beta / best as int8; here the bound is
+// the caller's depth, and a score needs 16 bits.
 //
 // Frame (what the return needs), 6 dwords = 24 B: the moves left (2), the flip mask of the move
 // being searched (2: the undo), {square, kept-side flag, best} and {alpha, beta} with the three
@@ -38,34 +40,17 @@
 // the first-maximum move equal the unpruned definition. The argument is the solver's
 // and does not look at what a leaf is: h(leaf) and T(leaf) are numbers that depend on the leaf
 // alone, never on the window. Node counts depend on the row and the arguments alone.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <atomic>
-
-#include "../../include/rvz.h"
-#include "rvz_rules.hip.h"
+#include "rvz_negamax.hip.h"
 
 using namespace rvz;
 
 namespace {
 
-constexpr int AB_THREADS = 128;                    // 2 waves per workgroup
-constexpr int AB_WG_PER_CU = 4;                    // 8 waves per CU by LDS
 constexpr int AB_FRAMES = RVZ_AB_MAX_DEPTH;
 constexpr int AB_FIELDS = 6;
 constexpr int AB_INF = 32000;                      // |score| <= RVZ_AB_WIN + 64; fits int16
-constexpr int AB_SLOTS = 32;                       // row counters: calls in flight at once
-static_assert(AB_FRAMES * AB_FIELDS * AB_THREADS * 4 * AB_WG_PER_CU <= 160 * 1024,
-              "2 waves per SIMD must fit in the CU's LDS");
 static_assert(RVZ_AB_WIN + 64 < AB_INF && AB_INF <= INT16_MAX, "scores are packed as int16");
 static_assert(RVZ_AB_HEUR_MAX < RVZ_AB_WIN - 64, "a proven result outranks a heuristic one");
-
-// the next row index of each call in flight; zeroed on the call's stream by k_alphabeta_zero.
-// The solver's counters (rvz_solve.hip) are another array.
-__device__ unsigned int g_ab_next_row[AB_SLOTS];
-
-__global__ void k_alphabeta_zero(int slot) { g_ab_next_row[slot] = 0u; }
 
 // weights[s] for s < NSQ, the mobility weight at [NSQ] (8x8: all 65; 6x6: the first 37)
 struct ab_weights {
@@ -91,14 +76,14 @@ __device__ __forceinline__ int heuristic(const ab_weights& wt, uint64_t P, uint6
 }
 
 template <int BS>
-__global__ __launch_bounds__(AB_THREADS) void k_alphabeta(
+__global__ __launch_bounds__(NM_THREADS) void k_alphabeta(
     int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
     const int32_t* __restrict__ status, int max_depth, const ab_weights wt, long long node_limit,
     int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
     long long* __restrict__ out_nodes, int slot) {
     constexpr int NSQ = Geo<BS>::NSQ;
     constexpr uint64_t FULL = Geo<BS>::FULL;
-    __shared__ uint32_t stk[AB_FRAMES * AB_FIELDS * AB_THREADS];
+    __shared__ uint32_t stk[stack_dwords<AB_FRAMES, AB_FIELDS>()];
     uint32_t* const my = stk + threadIdx.x;        // field f of depth d: my[(d * FIELDS + f) * T]
 
     bool active = false, exhausted = false;
@@ -117,7 +102,7 @@ __global__ __launch_bounds__(AB_THREADS) void k_alphabeta(
     for (;;) {
         // ---- an idle lane takes the next row and settles everything that needs no search
         if (!active && !exhausted) {
-            const unsigned r = atomicAdd(&g_ab_next_row[slot], 1u);
+            const unsigned r = next_row(slot);
             if (r >= (unsigned)n) {
                 exhausted = true;
             } else {
@@ -174,11 +159,11 @@ __global__ __launch_bounds__(AB_THREADS) void k_alphabeta(
                 else emit(best, bestsq, nodes);
             } else {
                 --depth;
-                const uint32_t* fr = my + depth * AB_FIELDS * AB_THREADS;
-                rem = (uint64_t)fr[0] | ((uint64_t)fr[AB_THREADS] << 32);
-                const uint64_t f = (uint64_t)fr[2 * AB_THREADS] |
-                                   ((uint64_t)fr[3 * AB_THREADS] << 32);
-                const uint32_t pk = fr[4 * AB_THREADS], ab = fr[5 * AB_THREADS];
+                const uint32_t* fr = my + depth * AB_FIELDS * NM_THREADS;
+                rem = (uint64_t)fr[0] | ((uint64_t)fr[NM_THREADS] << 32);
+                const uint64_t f = (uint64_t)fr[2 * NM_THREADS] |
+                                   ((uint64_t)fr[3 * NM_THREADS] << 32);
+                const uint32_t pk = fr[4 * NM_THREADS], ab = fr[5 * NM_THREADS];
                 const int sq = pk & 63, keep = (pk >> 6) & 1;
                 const int v = keep ? best : -best;
                 if (!keep) { const uint64_t t = P; P = O; O = t; }
@@ -224,14 +209,14 @@ __global__ __launch_bounds__(AB_THREADS) void k_alphabeta(
                     emit(0, -4, nodes);
                 } else {
                     const int keep = Mo ? 0 : 1;
-                    uint32_t* fr = my + depth * AB_FIELDS * AB_THREADS;
+                    uint32_t* fr = my + depth * AB_FIELDS * NM_THREADS;
                     fr[0] = (uint32_t)rem;
-                    fr[AB_THREADS] = (uint32_t)(rem >> 32);
-                    fr[2 * AB_THREADS] = (uint32_t)f;
-                    fr[3 * AB_THREADS] = (uint32_t)(f >> 32);
-                    fr[4 * AB_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
+                    fr[NM_THREADS] = (uint32_t)(rem >> 32);
+                    fr[2 * NM_THREADS] = (uint32_t)f;
+                    fr[3 * NM_THREADS] = (uint32_t)(f >> 32);
+                    fr[4 * NM_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
                                          ((uint32_t)(best & 0xFFFF) << 16);
-                    fr[5 * AB_THREADS] = (uint32_t)(alpha & 0xFFFF) |
+                    fr[5 * NM_THREADS] = (uint32_t)(alpha & 0xFFFF) |
                                          ((uint32_t)(beta & 0xFFFF) << 16);
                     ++depth;
                     if (keep) {
@@ -247,8 +232,6 @@ __global__ __launch_bounds__(AB_THREADS) void k_alphabeta(
         }
     }
 }
-
-std::atomic<unsigned> g_ab_slot{0};
 
 }  // namespace
 
@@ -271,21 +254,10 @@ extern "C" int rvz_alphabeta(int32_t bs, int32_t n, const uint64_t* black, const
     if (bound > RVZ_AB_HEUR_MAX) return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
     hipStream_t s = (hipStream_t)stream;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        return RVZ_EHIP;
-    const int slot = (int)(g_ab_slot.fetch_add(1u, std::memory_order_relaxed) % AB_SLOTS);
-    hipLaunchKernelGGL(k_alphabeta_zero, dim3(1), dim3(1), 0, s, slot);
-    const int64_t need = ((int64_t)n + AB_THREADS - 1) / AB_THREADS;
-    const int wgs = cus * AB_WG_PER_CU;
-    dim3 g(need < wgs ? (int)need : wgs), block(AB_THREADS);
-    if (bs == 8)
-        hipLaunchKernelGGL(k_alphabeta<8>, g, block, 0, s, n, black, white, status, depth, wt,
-                           (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
-    else
-        hipLaunchKernelGGL(k_alphabeta<6>, g, block, 0, s, n, black, white, status, depth, wt,
-                           (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    int slot = 0;
+    const int wgs = negamax_prepare(n, s, &slot);
+    if (wgs < 0) return wgs;
+    return negamax_launch(bs, k_alphabeta<8>, k_alphabeta<6>, wgs, s, n, black, white, status,
+                          depth, wt, (long long)node_limit, out_score, out_move,
+                          (long long*)out_nodes, slot);
 }

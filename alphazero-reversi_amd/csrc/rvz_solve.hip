@@ -7,20 +7,16 @@
 // game from g's side to move, both sides playing the maximum, the children made by make_move<BS>
 // (auto-pass included), moves in increasing square order, the first maximum kept.
 //
-// Shape: one position per LANE. A self-play iteration yields tens of thousands of small, unequal
-// trees with at most ~12 root moves each, so a wave per position would idle most lanes; here the
-// 64 lanes of a wave step one explicit-stack state machine in lockstep, each on its own position.
-// Lanes are persistent: a lane whose row is done takes the next row index from a device counter
-// in the same loop iteration, so a wave stays full until the batch drains; the grid is sized from
-// the CU count. Nothing a row computes depends on which lane, wave or launch it landed in.
+// Shape: one position per LANE, persistent lanes that take the next row from a per-call device
+// counter, an explicit stack in LDS laid out [depth][field][lane], no scratch: the head of
+// rvz_negamax.hip.h has the reasons. That header holds what this file and rvz_alphabeta.hip have
+// in common around their loops (geometry, the stack's size, the row counter, the host side of a
+// launch), and says why the loops themselves are two texts.
 //
 // Per lane, in registers: the current node (mover's discs P, the other side's O, the moves not
-// yet tried, alpha / beta / best) and the row's bookkeeping. Per lane, in LDS: one frame per ply
-// above the current node, [depth][field][lane] in dwords, so a wave's access to one field of one
-// depth covers 64 consecutive banks. A frame is what the return needs: the moves left (2 dwords),
-// the flip mask of the move being searched (2 dwords: the undo), and {square, kept-side flag,
-// alpha, beta, best} packed in one dword: 20 bytes. No recursion and no run-time-indexed register
-// array: the kernels use no scratch.
+// yet tried, alpha / beta / best) and the row's bookkeeping. A frame is what the return needs:
+// the moves left (2 dwords), the flip mask of the move being searched (2 dwords: the undo), and
+// {square, kept-side flag, alpha, beta, best} packed in one dword: 20 bytes.
 //
 // Depth: every ply places a disc, and a frame is pushed only when the child has a move, i.e. at
 // least one empty square left, so a row with E empties pushes at most E - 1 frames;
@@ -67,31 +63,15 @@
 // and plain lanes of one wave run the same instructions in every iteration and a scan never holds
 // the other lanes up for more than it costs itself. A node with one untried move is not scanned.
 // Scans visit no position: `nodes` counts committed moves only.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <atomic>
-
-#include "../../include/rvz.h"
-#include "rvz_rules.hip.h"
+#include "rvz_negamax.hip.h"
 
 using namespace rvz;
 
 namespace {
 
-constexpr int SOLVE_THREADS = 128;                 // 2 waves per workgroup
-constexpr int SOLVE_WG_PER_CU = 4;                 // 8 waves per CU by LDS
 constexpr int FRAMES = RVZ_SOLVE_MAX_EMPTIES;
 constexpr int FIELDS = 5;
 constexpr int SINF = 127;                          // |score| <= 64; fits the packed int8 fields
-constexpr int SLOTS = 32;                          // row counters: calls in flight at once
-static_assert(FRAMES * FIELDS * SOLVE_THREADS * 4 * SOLVE_WG_PER_CU <= 160 * 1024,
-              "2 waves per SIMD must fit in the CU's LDS");
-
-// the next row index of each call in flight; zeroed on the call's stream by k_solve_zero
-__device__ unsigned int g_next_row[SLOTS];
-
-__global__ void k_solve_zero(int slot) { g_next_row[slot] = 0u; }
 
 enum { MODE_FULL = 0, MODE_WINDOW = 1, MODE_MOVES = 2 };
 
@@ -107,7 +87,7 @@ __device__ __forceinline__ void solve_rows(
     constexpr bool WIN = MODE != MODE_FULL, MOVES = MODE == MODE_MOVES;
     constexpr int NSQ = Geo<BS>::NSQ;
     constexpr uint64_t FULL = Geo<BS>::FULL;
-    __shared__ uint32_t stk[FRAMES * FIELDS * SOLVE_THREADS];
+    __shared__ uint32_t stk[stack_dwords<FRAMES, FIELDS>()];
     uint32_t* const my = stk + threadIdx.x;        // field f of depth d: my[(d * FIELDS + f) * T]
 
     bool active = false, exhausted = false;
@@ -134,7 +114,7 @@ __device__ __forceinline__ void solve_rows(
     for (;;) {
         // ---- an idle lane takes the next row and settles everything that needs no search
         if (!active && !exhausted) {
-            const unsigned r = atomicAdd(&g_next_row[slot], 1u);
+            const unsigned r = next_row(slot);
             if (r >= (unsigned)n) {
                 exhausted = true;
             } else {
@@ -256,11 +236,11 @@ __device__ __forceinline__ void solve_rows(
                 else emit(best, WIN && best <= walpha ? -6 : bestsq, nodes);
             } else {
                 --depth;
-                const uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
-                rem = (uint64_t)fr[0] | ((uint64_t)fr[SOLVE_THREADS] << 32);
-                const uint64_t f = (uint64_t)fr[2 * SOLVE_THREADS] |
-                                   ((uint64_t)fr[3 * SOLVE_THREADS] << 32);
-                const uint32_t pk = fr[4 * SOLVE_THREADS];
+                const uint32_t* fr = my + depth * FIELDS * NM_THREADS;
+                rem = (uint64_t)fr[0] | ((uint64_t)fr[NM_THREADS] << 32);
+                const uint64_t f = (uint64_t)fr[2 * NM_THREADS] |
+                                   ((uint64_t)fr[3 * NM_THREADS] << 32);
+                const uint32_t pk = fr[4 * NM_THREADS];
                 const int sq = pk & 63, keep = (pk >> 6) & 1;
                 const int v = keep ? best : -best;
                 if (!keep) { const uint64_t t = P; P = O; O = t; }
@@ -316,12 +296,12 @@ __device__ __forceinline__ void solve_rows(
                         emit(0, -4, nodes);
                     } else {
                         const int keep = Mo ? 0 : 1;
-                        uint32_t* fr = my + depth * FIELDS * SOLVE_THREADS;
+                        uint32_t* fr = my + depth * FIELDS * NM_THREADS;
                         fr[0] = (uint32_t)rem;
-                        fr[SOLVE_THREADS] = (uint32_t)(rem >> 32);
-                        fr[2 * SOLVE_THREADS] = (uint32_t)f;
-                        fr[3 * SOLVE_THREADS] = (uint32_t)(f >> 32);
-                        fr[4 * SOLVE_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
+                        fr[NM_THREADS] = (uint32_t)(rem >> 32);
+                        fr[2 * NM_THREADS] = (uint32_t)f;
+                        fr[3 * NM_THREADS] = (uint32_t)(f >> 32);
+                        fr[4 * NM_THREADS] = (uint32_t)sq | ((uint32_t)keep << 6) |
                                                 ((uint32_t)(alpha & 0xFF) << 8) |
                                                 ((uint32_t)(beta & 0xFF) << 16) |
                                                 ((uint32_t)(best & 0xFF) << 24);
@@ -342,7 +322,7 @@ __device__ __forceinline__ void solve_rows(
 }
 
 template <int BS>
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
+__global__ __launch_bounds__(NM_THREADS) void k_solve(
     int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
     const int32_t* __restrict__ status, int max_empties, long long node_limit,
     int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
@@ -352,7 +332,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(
 }
 
 template <int BS>
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
+__global__ __launch_bounds__(NM_THREADS) void k_solve_window(
     int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
     const int32_t* __restrict__ status, int max_empties, long long node_limit, int walpha,
     int wbeta, int order_min, int32_t* __restrict__ out_score, int32_t* __restrict__ out_move,
@@ -363,7 +343,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_window(
 
 // tasks = rows * max(1, max_empties) (rvz_solve_moves checks that it fits)
 template <int BS>
-__global__ __launch_bounds__(SOLVE_THREADS) void k_solve_moves(
+__global__ __launch_bounds__(NM_THREADS) void k_solve_moves(
     int tasks, int rows, const uint64_t* __restrict__ black,
     const uint64_t* __restrict__ white, const int32_t* __restrict__ status, int max_empties,
     long long node_limit, int walpha, int wbeta, int order_min, int32_t* __restrict__ out_scores,
@@ -372,11 +352,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve_moves(
                                walpha, wbeta, order_min, out_scores, out_count, out_nodes, slot);
 }
 
-std::atomic<unsigned> g_slot{0};
-
 // What the entry points do before their own launch: the common argument checks (RVZ_EINVAL
-// before any HIP call), then for n > 0 the row-counter slot, the grid and the zeroing launch.
-// per_row: the units of work a row makes (1; rvz_solve_moves: its tasks per row).
+// before any HIP call), then for n > 0 negamax_prepare. per_row: the units of work a row makes
+// (1; rvz_solve_moves: its tasks per row).
 // Returns the grid size, 0 when n == 0 (nothing to launch), or a negative RVZ_E* code.
 int solve_prepare(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
                   const int32_t* status, int32_t max_empties, int64_t node_limit,
@@ -385,17 +363,7 @@ int solve_prepare(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* 
     if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
         node_limit <= 0 || (n > 0 && (!black || !white || !status || !out_score || !out_move)))
         return RVZ_EINVAL;
-    if (n == 0) return 0;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        return RVZ_EHIP;
-    *slot = (int)(g_slot.fetch_add(1u, std::memory_order_relaxed) % SLOTS);
-    hipLaunchKernelGGL(k_solve_zero, dim3(1), dim3(1), 0, s, *slot);
-    const int64_t need = ((int64_t)n * per_row + SOLVE_THREADS - 1) / SOLVE_THREADS;
-    const int wgs = cus * SOLVE_WG_PER_CU;
-    return need < wgs ? (int)need : wgs;
+    return n == 0 ? 0 : negamax_prepare((int64_t)n * per_row, s, slot);
 }
 
 }  // namespace
@@ -408,14 +376,9 @@ extern "C" int rvz_solve(int32_t bs, int32_t n, const uint64_t* black, const uin
     const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_score,
                                   out_move, s, &slot);
     if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
-    dim3 g(wgs), block(SOLVE_THREADS);
-    if (bs == 8)
-        hipLaunchKernelGGL(k_solve<8>, g, block, 0, s, n, black, white, status, max_empties,
-                           (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
-    else
-        hipLaunchKernelGGL(k_solve<6>, g, block, 0, s, n, black, white, status, max_empties,
-                           (long long)node_limit, out_score, out_move, (long long*)out_nodes, slot);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return negamax_launch(bs, k_solve<8>, k_solve<6>, wgs, s, n, black, white, status,
+                          max_empties, (long long)node_limit, out_score, out_move,
+                          (long long*)out_nodes, slot);
 }
 
 extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
@@ -429,16 +392,9 @@ extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
     const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_score,
                                   out_move, s, &slot);
     if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
-    dim3 g(wgs), block(SOLVE_THREADS);
-    if (bs == 8)
-        hipLaunchKernelGGL(k_solve_window<8>, g, block, 0, s, n, black, white, status,
-                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
-                           out_score, out_move, (long long*)out_nodes, slot);
-    else
-        hipLaunchKernelGGL(k_solve_window<6>, g, block, 0, s, n, black, white, status,
-                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
-                           out_score, out_move, (long long*)out_nodes, slot);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return negamax_launch(bs, k_solve_window<8>, k_solve_window<6>, wgs, s, n, black, white,
+                          status, max_empties, (long long)node_limit, alpha, beta,
+                          order_min_empties, out_score, out_move, (long long*)out_nodes, slot);
 }
 
 extern "C" int rvz_solve_moves(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
@@ -454,15 +410,8 @@ extern "C" int rvz_solve_moves(int32_t bs, int32_t n, const uint64_t* black, con
     const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_scores,
                                   out_count, s, &slot, per_row);
     if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
-    dim3 g(wgs), block(SOLVE_THREADS);
     const int tasks = n * per_row;                 // per_row <= 14 < S*S + 1: fits
-    if (bs == 8)
-        hipLaunchKernelGGL(k_solve_moves<8>, g, block, 0, s, tasks, n, black, white, status,
-                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
-                           out_scores, out_count, (long long*)out_nodes, slot);
-    else
-        hipLaunchKernelGGL(k_solve_moves<6>, g, block, 0, s, tasks, n, black, white, status,
-                           max_empties, (long long)node_limit, alpha, beta, order_min_empties,
-                           out_scores, out_count, (long long*)out_nodes, slot);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return negamax_launch(bs, k_solve_moves<8>, k_solve_moves<6>, wgs, s, tasks, n, black, white,
+                          status, max_empties, (long long)node_limit, alpha, beta,
+                          order_min_empties, out_scores, out_count, (long long*)out_nodes, slot);
 }

@@ -806,11 +806,11 @@ def action_probs(visits: torch.Tensor, temperature, u: Optional[torch.Tensor] = 
     return idx, p, drew
 
 
-def _solve_call(name, black, white, status, board_size, max_empties, node_limit, *extra,
-                per_move=False):
-    """solve / solve_window / solve_moves: lib.rvz_<name> on the rows, `extra` the integer
-    arguments the entry point takes between node_limit and the outputs. per_move: the first and
-    third outputs hold S*S + 1 entries per row. Every pointer is null when n == 0."""
+def _rows_call(name, black, white, status, board_size, *mid, per_move=False):
+    """The batched searches (solve, solve_window, solve_moves, alphabeta): lib.rvz_<name> on the
+    rows; `mid` are the arguments the entry point takes between the rows and the outputs, as
+    ctypes takes them. Returns the three outputs, fresh tensors on black's device; per_move: the
+    first and third hold S*S + 1 entries per row. Every pointer is null when n == 0."""
     lib = _lib.load()
     n = black.numel()
     if status.shape != (n, 4) or white.numel() != n:
@@ -826,10 +826,15 @@ def _solve_call(name, black, white, status, board_size, max_empties, node_limit,
     pb, pw, pst, pscore, pmove, pnodes, stream = (
         [ptr(t) for t in (b, w, st, score, move, nodes)] + [_lib.stream_handle(dev)]
         if n else [None] * 7)
-    check(getattr(lib, "rvz_" + name)(int(board_size), n, pb, pw, pst, int(max_empties),
-                                      int(node_limit), *map(int, extra), pscore, pmove, pnodes,
-                                      stream), None, "rvz_" + name)
+    check(getattr(lib, "rvz_" + name)(int(board_size), n, pb, pw, pst, *mid, pscore, pmove,
+                                      pnodes, stream), None, "rvz_" + name)
     return score, move, nodes
+
+
+def _solve_call(name, black, white, status, board_size, *ints, per_move=False):
+    """solve / solve_window / solve_moves: `ints` are max_empties, node_limit and what the entry
+    point takes after them."""
+    return _rows_call(name, black, white, status, board_size, *map(int, ints), per_move=per_move)
 
 
 def solve(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int = 8,
@@ -969,7 +974,6 @@ def alphabeta(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, bo
     the lowest-index best square, S*S for a forced pass, -2 for a root that is over (score
     valid), -4 abandoned at node_limit visited positions, -5 for a malformed row (score 0 for
     -4 / -5); nodes counts the positions visited. 1 <= depth <= RVZ_AB_MAX_DEPTH."""
-    lib = _lib.load()
     nsq = int(board_size) ** 2
     if weights is None:
         weights = alphabeta_weights(board_size)
@@ -979,23 +983,8 @@ def alphabeta(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, bo
     if any(not -2 ** 31 <= x < 2 ** 31 for x in wl):
         raise RvzError("alphabeta: a weight does not fit int32")
     wt = (C.c_int32 * max(len(wl), 1))(*wl)       # host memory: read during the call only
-    n = black.numel()
-    if status.shape != (n, 4) or white.numel() != n:
-        raise RvzError("alphabeta: black and white hold one entry per row, status is [n, 4]")
-    dev = black.device
-    b = black.to(torch.int64).contiguous()
-    w = white.to(dev, torch.int64).contiguous()
-    st = status.to(dev, torch.int32).contiguous()
-    score = torch.empty(n, dtype=torch.int32, device=dev)
-    move = torch.empty(n, dtype=torch.int32, device=dev)
-    nodes = torch.empty(n, dtype=torch.int64, device=dev)
-    pb, pw, pst, pscore, pmove, pnodes, stream = (
-        [ptr(t) for t in (b, w, st, score, move, nodes)] + [_lib.stream_handle(dev)]
-        if n else [None] * 7)
-    check(lib.rvz_alphabeta(int(board_size), n, pb, pw, pst, int(depth),
-                            C.cast(wt, C.c_void_p), int(node_limit), pscore, pmove, pnodes,
-                            stream), None, "rvz_alphabeta")
-    return score, move, nodes
+    return _rows_call("alphabeta", black, white, status, board_size, int(depth),
+                      C.cast(wt, C.c_void_p), int(node_limit))
 
 
 def policy_softmax(logits: torch.Tensor, board_size: int = 8) -> torch.Tensor:

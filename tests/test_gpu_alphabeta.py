@@ -276,6 +276,45 @@ def test_graph_capture_keeps_its_weights():
     assert not torch.equal(want[0], eager[0])
 
 
+def test_solver_and_alphabeta_in_flight_together():
+    """rvz.solve, rvz.solve_moves and rvz.alphabeta issued back to back on three streams with
+    nothing between them give, node counts included, what each gives alone: both translation
+    units take their row counters from csrc/rvz_negamax.hip.h, each a copy of its own. More than
+    128 rows: lanes take further rows and more than one workgroup runs. 32 rounds, all queued
+    before anything is waited for: a round takes two of the solver's 32 counter slots and one of
+    alpha-beta's, so the difference of the two units' slot indices passes through every residue
+    and, were the array one, some round's calls would hold the same counter while the streams'
+    queues keep the three kernels running side by side."""
+    import rvz
+    games = [R.position(s, 8, 8)[0] for s in range(300)] + R.RootCases(8, (12, 25)).mixed
+    arrays = R.to_device(games)
+    wt = list(A.default_table(8))
+    calls = [lambda: rvz.solve(*arrays, 8, 8, BIG),
+             lambda: rvz.solve_moves(*arrays, 8, 8, BIG),
+             lambda: rvz.alphabeta(*arrays, 8, 3, wt, BIG)]
+    alone = []
+    for call in calls:
+        alone.append(call())
+        torch.cuda.synchronize()
+    assert int((alone[0][2] > 1).sum()) > 256 and int((alone[2][2] > 1).sum()) > 256
+    streams = [torch.cuda.Stream() for _ in calls]
+    for s in streams:
+        s.wait_stream(torch.cuda.current_stream())
+    rounds = []
+    for _ in range(32):
+        together = []
+        for s, call in zip(streams, calls):
+            with torch.cuda.stream(s):
+                together.append(call())
+        rounds.append(together)
+    for s in streams:
+        s.synchronize()
+    for i, together in enumerate(rounds):
+        for name, got, want in zip(("solve", "solve_moves", "alphabeta"), together, alone):
+            for a, b in zip(got, want):
+                assert torch.equal(a, b), (i, name)
+
+
 def test_two_streams_two_tables_and_the_engine():
     import rvz
     games = A.playouts(8)
