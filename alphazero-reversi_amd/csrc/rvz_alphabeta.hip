@@ -239,7 +239,7 @@ extern "C" int rvz_alphabeta(int32_t bs, int32_t n, const uint64_t* black, const
                              const int32_t* status, int32_t depth, const int32_t* weights,
                              int64_t node_limit, int32_t* out_score, int32_t* out_move,
                              int64_t* out_nodes, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || depth < 1 || depth > RVZ_AB_MAX_DEPTH ||
+    if (!board_ok(bs) || n < 0 || depth < 1 || depth > RVZ_AB_MAX_DEPTH ||
         node_limit <= 0 || !weights ||
         (n > 0 && (!black || !white || !status || !out_score || !out_move)))
         return RVZ_EINVAL;
@@ -257,7 +257,7 @@ extern "C" int rvz_alphabeta(int32_t bs, int32_t n, const uint64_t* black, const
     int slot = 0;
     const int wgs = negamax_prepare(n, s, &slot);
     if (wgs < 0) return wgs;
-    return negamax_launch(bs, k_alphabeta<8>, k_alphabeta<6>, wgs, s, n, black, white, status,
-                          depth, wt, (long long)node_limit, out_score, out_move,
-                          (long long*)out_nodes, slot);
+    return launch_bs(bs, k_alphabeta<8>, k_alphabeta<6>, dim3(wgs), dim3(NM_THREADS), s, n, black,
+                     white, status, depth, wt, (long long)node_limit, out_score, out_move,
+                     (long long*)out_nodes, slot);
 }

@@ -34,10 +34,12 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rvz.h"
 #include "rvz_h2.hip.h"
+#include "rvz_host.hip.h"
 #include "rvz_pow.hip.h"
 #include "rvz_rules.hip.h"
 #include "rvz_trace.h"
@@ -1336,6 +1338,27 @@ static int launch_check(rvz_engine* e, const char* what) {
 
 static int grid_games(int G) { return (G + WPB - 1) / WPB; }
 
+// The launch of a per-game kernel (one wave per game) for the engine's board on its stream. The
+// unchecked form is for the callers that have work between the launch and its launch_check.
+template <class... P, class... A>
+static void launch_games_unchecked(rvz_engine* e, void (*k8)(P...), void (*k6)(P...), A... args) {
+    launch_bs_unchecked(e->BS, k8, k6, dim3(grid_games(e->v.G)), dim3(WPB * WAVE), e->stream,
+                        args...);
+}
+template <class... P, class... A>
+static int launch_games(rvz_engine* e, const char* what, void (*k8)(P...), void (*k6)(P...),
+                        A... args) {
+    launch_games_unchecked(e, k8, k6, args...);
+    return launch_check(e, what);
+}
+
+// true, with the error text set: a setting that may not change while a search is under way
+static bool in_search(rvz_engine* e, const char* name) {
+    if (!e->pending && !(e->searching && e->next_batch > 0)) return false;
+    e->err = std::string(name) + " inside a search";
+    return true;
+}
+
 // Stream-ordered 32-bit fill as a kernel of our own instead of hipMemsetAsync: inside a captured
 // HIP graph a memset node's replays were seen to leave device words of the filled buffer
 // holding a 64-bit address (tools/diag_stagger.py: rvz_play's queue words after the second replay
@@ -1409,6 +1432,19 @@ static T* dalloc(rvz_engine* e, size_t count) {
     return static_cast<T*>(p);
 }
 
+#ifdef RVZ_WALK_STATS
+// the first n rows of a per-game device counter table copied to the host; the table is then zeroed
+template <class T, int N>
+static int take_rows(T (&table)[WALK_STATS_MAX][N], int n, std::vector<T>& out) {
+    out.assign((size_t)n * N, T(0));
+    if (hipMemcpyFromSymbol(out.data(), HIP_SYMBOL(table), out.size() * sizeof(T)) != hipSuccess)
+        return RVZ_EHIP;
+    const std::vector<T> z((size_t)WALK_STATS_MAX * N, T(0));
+    return hipMemcpyToSymbol(HIP_SYMBOL(table), z.data(), z.size() * sizeof(T)) == hipSuccess
+               ? RVZ_OK : RVZ_EHIP;
+}
+#endif
+
 extern "C" {
 
 int rvz_version(void) { return 1; }
@@ -1421,7 +1457,7 @@ int rvz_create(const rvz_config* cfg, rvz_engine** out) {
     if (!cfg || !out) { g_create_error = "null argument"; return RVZ_EINVAL; }
     *out = nullptr;
     const int bs = cfg->board_size;
-    if (bs != 8 && bs != 6) { g_create_error = "board_size must be 8 or 6"; return RVZ_EINVAL; }
+    if (!board_ok(bs)) { g_create_error = "board_size must be 8 or 6"; return RVZ_EINVAL; }
     if (cfg->n_games <= 0 || cfg->num_simulations <= 0 || cfg->batch_size <= 0) {
         g_create_error = "n_games, num_simulations and batch_size must be positive";
         return RVZ_EINVAL;
@@ -1560,14 +1596,10 @@ int rvz_check(rvz_engine* e, int32_t* host_err) {
     return RVZ_OK;
 }
 
-#define DISPATCH_BS(e, KERNEL8, KERNEL6) ((e)->BS == 8 ? (KERNEL8) : (KERNEL6))
-
 int rvz_env_reset(rvz_engine* e, const uint32_t* seeds, const uint8_t* mask) {
     if (!e || !seeds) return RVZ_EINVAL;
     e->pending = 0;
-    dim3 grid(grid_games(e->v.G)), block(WPB * WAVE);
-    if (e->BS == 8) hipLaunchKernelGGL(k_reset<8>, grid, block, 0, e->stream, e->v, seeds, mask);
-    else hipLaunchKernelGGL(k_reset<6>, grid, block, 0, e->stream, e->v, seeds, mask);
+    launch_games_unchecked(e, k_reset<8>, k_reset<6>, e->v, seeds, mask);
     e->searching = 0;
     return launch_check(e, "k_reset");
 }
@@ -1577,10 +1609,8 @@ int rvz_env_autoreset(rvz_engine* e, const int32_t* idx, int64_t* seeds, int64_t
     const Range trace_range("rvz.env.autoreset");
     if (!e || !idx || !plies || (reset && (!seeds || !done))) return RVZ_EINVAL;
     if (reset) e->pending = 0;
-    dim3 grid(grid_games(e->v.G)), block(WPB * WAVE);
-    if (e->BS == 8) hipLaunchKernelGGL(k_autoreset<8>, grid, block, 0, e->stream, e->v, idx, seeds, stride, plies, done, reset);
-    else hipLaunchKernelGGL(k_autoreset<6>, grid, block, 0, e->stream, e->v, idx, seeds, stride, plies, done, reset);
-    return launch_check(e, "k_autoreset");
+    return launch_games(e, "k_autoreset", k_autoreset<8>, k_autoreset<6>, e->v, idx, seeds, stride,
+                        plies, done, reset);
 }
 
 int rvz_env_get(rvz_engine* e, uint64_t* black, uint64_t* white, int32_t* status) {
@@ -1631,45 +1661,40 @@ int rvz_env_draws(rvz_engine* e, int32_t* out_pos) {
 
 int rvz_board_legal(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
                     const int32_t* status, uint64_t* out, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || (n > 0 && (!black || !white || !status || !out)))
+    if (!board_ok(bs) || n < 0 || (n > 0 && (!black || !white || !status || !out)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid((n + 255) / 256), block(256);
-    if (bs == 8) hipLaunchKernelGGL(k_board_legal<8>, grid, block, 0, (hipStream_t)stream, n, black, white, status, out);
-    else hipLaunchKernelGGL(k_board_legal<6>, grid, block, 0, (hipStream_t)stream, n, black, white, status, out);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const Geometry g = thread_per_row(n);
+    return launch_bs(bs, k_board_legal<8>, k_board_legal<6>, g.grid, g.block, (hipStream_t)stream,
+                     n, black, white, status, out);
 }
 
 int rvz_board_apply(int32_t bs, int32_t n, uint64_t* black, uint64_t* white, int32_t* status,
                     const int32_t* sq, int32_t* ok, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || (n > 0 && (!black || !white || !status || !sq)))
+    if (!board_ok(bs) || n < 0 || (n > 0 && (!black || !white || !status || !sq)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid((n + 255) / 256), block(256);
-    if (bs == 8) hipLaunchKernelGGL(k_board_apply<8>, grid, block, 0, (hipStream_t)stream, n, black, white, status, sq, ok);
-    else hipLaunchKernelGGL(k_board_apply<6>, grid, block, 0, (hipStream_t)stream, n, black, white, status, sq, ok);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const Geometry g = thread_per_row(n);
+    return launch_bs(bs, k_board_apply<8>, k_board_apply<6>, g.grid, g.block, (hipStream_t)stream,
+                     n, black, white, status, sq, ok);
 }
 
 int rvz_board_canonical(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
                         const int32_t* status, float* out, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || (n > 0 && (!black || !white || !status || !out)))
+    if (!board_ok(bs) || n < 0 || (n > 0 && (!black || !white || !status || !out)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    const int total = n * bs * bs;
-    dim3 grid((total + 255) / 256), block(256);
-    if (bs == 8) hipLaunchKernelGGL(k_board_canonical<8>, grid, block, 0, (hipStream_t)stream, n, black, white, status, out);
-    else hipLaunchKernelGGL(k_board_canonical<6>, grid, block, 0, (hipStream_t)stream, n, black, white, status, out);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const Geometry g = thread_per_row(n * bs * bs);   // one thread per square
+    return launch_bs(bs, k_board_canonical<8>, k_board_canonical<6>, g.grid, g.block,
+                     (hipStream_t)stream, n, black, white, status, out);
 }
 
 int rvz_policy_softmax(int32_t bs, int32_t n, const float* logits, float* probs, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || (n > 0 && (!logits || !probs))) return RVZ_EINVAL;
+    if (!board_ok(bs) || n < 0 || (n > 0 && (!logits || !probs))) return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid((n + WPB - 1) / WPB), block(WPB * WAVE);
-    if (bs == 8) hipLaunchKernelGGL(k_policy_softmax<8>, grid, block, 0, (hipStream_t)stream, n, logits, probs);
-    else hipLaunchKernelGGL(k_policy_softmax<6>, grid, block, 0, (hipStream_t)stream, n, logits, probs);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const Geometry g = wave_per_row(n, WPB);
+    return launch_bs(bs, k_policy_softmax<8>, k_policy_softmax<6>, g.grid, g.block,
+                     (hipStream_t)stream, n, logits, probs);
 }
 
 int rvz_env_legal(rvz_engine* e, uint64_t* out) {
@@ -1719,17 +1744,14 @@ int rvz_search_step(rvz_engine* e, void* leaf_x, int32_t* need) {
     const float* pol = e->pend_policy;
     const float* val = e->pend_value;
     const int lg = e->pend_is_logits;
-    dim3 grid(grid_games(e->v.G)), block(WPB * WAVE);
+    const auto step = [&](auto* x) {   // k_step<BS, XT> for the leaf planes' type
+        using XT = std::remove_pointer_t<decltype(x)>;
+        launch_games_unchecked(e, k_step<8, XT>, k_step<6, XT>, e->v, ex, pol, lg, val, first, bsz,
+                               e->next_batch, x, need);
+    };
     timing_begin(e, 0);
-    if (e->cfg.leaf_dtype == RVZ_LEAF_F32) {
-        float* x = (float*)leaf_x;
-        if (e->BS == 8) hipLaunchKernelGGL((k_step<8, float>), grid, block, 0, e->stream, e->v, ex, pol, lg, val, first, bsz, e->next_batch, x, need);
-        else hipLaunchKernelGGL((k_step<6, float>), grid, block, 0, e->stream, e->v, ex, pol, lg, val, first, bsz, e->next_batch, x, need);
-    } else {
-        __hip_bfloat16* x = (__hip_bfloat16*)leaf_x;
-        if (e->BS == 8) hipLaunchKernelGGL((k_step<8, __hip_bfloat16>), grid, block, 0, e->stream, e->v, ex, pol, lg, val, first, bsz, e->next_batch, x, need);
-        else hipLaunchKernelGGL((k_step<6, __hip_bfloat16>), grid, block, 0, e->stream, e->v, ex, pol, lg, val, first, bsz, e->next_batch, x, need);
-    }
+    if (e->cfg.leaf_dtype == RVZ_LEAF_F32) step((float*)leaf_x);
+    else step((__hip_bfloat16*)leaf_x);
     timing_end(e);
     e->pending = 0;
     e->next_batch += 1;
@@ -1757,9 +1779,8 @@ int rvz_search_submit(rvz_engine* e, const float* policy, int32_t is_logits, con
 
 static int flush_pending(rvz_engine* e) {
     if (!e->pending) return RVZ_OK;
-    dim3 grid(grid_games(e->v.G)), block(WPB * WAVE);
-    if (e->BS == 8) hipLaunchKernelGGL(k_expand_backup<8>, grid, block, 0, e->stream, e->v, e->pending, e->pend_policy, e->pend_is_logits, e->pend_value);
-    else hipLaunchKernelGGL(k_expand_backup<6>, grid, block, 0, e->stream, e->v, e->pending, e->pend_policy, e->pend_is_logits, e->pend_value);
+    launch_games_unchecked(e, k_expand_backup<8>, k_expand_backup<6>, e->v, e->pending,
+                           e->pend_policy, e->pend_is_logits, e->pend_value);
     e->pending = 0;
     return launch_check(e, "k_expand_backup");
 }
@@ -1768,18 +1789,12 @@ int rvz_search_visits(rvz_engine* e, int32_t* out) {
     if (!e || !out) return RVZ_EINVAL;
     int r = flush_pending(e);
     if (r != RVZ_OK) return r;
-    dim3 grid(grid_games(e->v.G)), block(WPB * WAVE);
-    if (e->BS == 8) hipLaunchKernelGGL(k_visits<8>, grid, block, 0, e->stream, e->v, out);
-    else hipLaunchKernelGGL(k_visits<6>, grid, block, 0, e->stream, e->v, out);
-    return launch_check(e, "k_visits");
+    return launch_games(e, "k_visits", k_visits<8>, k_visits<6>, e->v, out);
 }
 
 int rvz_search_compact(rvz_engine* e, int32_t on) {
     if (!e) return RVZ_EINVAL;
-    if (e->pending || (e->searching && e->next_batch > 0)) {
-        e->err = "rvz_search_compact inside a search";
-        return RVZ_EINVAL;
-    }
+    if (in_search(e, "rvz_search_compact")) return RVZ_EINVAL;
     if (on && !e->live_buf) {
         // [E] live counts, [G] row map, then the 8-byte running total
         const size_t nlive = (size_t)e->E * e->v.NS * RVZ_LIVE_PITCH;
@@ -1827,10 +1842,7 @@ static int memo_grow(rvz_engine* e) {
 
 int rvz_search_memo(rvz_engine* e, int32_t on) {
     if (!e) return RVZ_EINVAL;
-    if (e->pending || (e->searching && e->next_batch > 0)) {
-        e->err = "rvz_search_memo inside a search";
-        return RVZ_EINVAL;
-    }
+    if (in_search(e, "rvz_search_memo")) return RVZ_EINVAL;
     if (on) {
         const int r = memo_grow(e);
         if (r != RVZ_OK) return r;
@@ -1857,10 +1869,7 @@ int rvz_search_root_noise(rvz_engine* e, double alpha, double epsilon, uint32_t 
                  "0 <= epsilon <= 1";
         return RVZ_EINVAL;
     }
-    if (e->pending || (e->searching && e->next_batch > 0)) {
-        e->err = "rvz_search_root_noise inside a search";
-        return RVZ_EINVAL;
-    }
+    if (in_search(e, "rvz_search_root_noise")) return RVZ_EINVAL;
     // eps and 1 - eps as float32, once, here: the kernels (and a test's restatement) use these
     const float eps = (float)epsilon;
     e->v.noise_eps = eps;
@@ -1873,14 +1882,13 @@ int rvz_search_root_noise(rvz_engine* e, double alpha, double epsilon, uint32_t 
 int rvz_dirichlet_noise(int32_t bs, int32_t n, const uint64_t* legal, const uint32_t* seed32,
                         const int32_t* tag, uint32_t salt, double alpha, float* out,
                         uint32_t* out_bits, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || !noise_alpha_ok(alpha) ||
+    if (!board_ok(bs) || n < 0 || !noise_alpha_ok(alpha) ||
         (n > 0 && (!legal || !seed32 || !tag || !out)) || ((uintptr_t)out_bits & 15) != 0)
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid((n + WPB - 1) / WPB), block(WPB * WAVE);
-    if (bs == 8) hipLaunchKernelGGL(k_dirichlet<8>, grid, block, 0, (hipStream_t)stream, n, legal, seed32, tag, salt, (float)alpha, out, out_bits);
-    else hipLaunchKernelGGL(k_dirichlet<6>, grid, block, 0, (hipStream_t)stream, n, legal, seed32, tag, salt, (float)alpha, out, out_bits);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const Geometry g = wave_per_row(n, WPB);
+    return launch_bs(bs, k_dirichlet<8>, k_dirichlet<6>, g.grid, g.block, (hipStream_t)stream, n,
+                     legal, seed32, tag, salt, (float)alpha, out, out_bits);
 }
 
 int rvz_act_schedule(rvz_engine* e, int32_t from_discs, double late_temperature) {
@@ -1889,10 +1897,7 @@ int rvz_act_schedule(rvz_engine* e, int32_t from_discs, double late_temperature)
         e->err = "rvz_act_schedule: late_temperature must be finite and >= 0";
         return RVZ_EINVAL;
     }
-    if (e->pending || (e->searching && e->next_batch > 0)) {
-        e->err = "rvz_act_schedule inside a search";
-        return RVZ_EINVAL;
-    }
+    if (in_search(e, "rvz_act_schedule")) return RVZ_EINVAL;
     e->v.sched_from = from_discs > 0 ? from_discs : 0;
     e->v.sched_late = from_discs > 0 ? late_temperature : 0.0;
     return RVZ_OK;
@@ -1901,14 +1906,13 @@ int rvz_act_schedule(rvz_engine* e, int32_t from_discs, double late_temperature)
 int rvz_action_probs(int32_t bs, int32_t n, const int32_t* visits, const double* temperature,
                      const double* u, int32_t* out_idx, double* out_p, int32_t* out_drew,
                      void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 ||
+    if (!board_ok(bs) || n < 0 ||
         (n > 0 && (!visits || !temperature || !u || !out_idx || !out_p)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid((n + WPB - 1) / WPB), block(WPB * WAVE);
-    if (bs == 8) hipLaunchKernelGGL(k_action_probs<8>, grid, block, 0, (hipStream_t)stream, n, visits, temperature, u, out_idx, out_p, out_drew);
-    else hipLaunchKernelGGL(k_action_probs<6>, grid, block, 0, (hipStream_t)stream, n, visits, temperature, u, out_idx, out_p, out_drew);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const Geometry g = wave_per_row(n, WPB);
+    return launch_bs(bs, k_action_probs<8>, k_action_probs<6>, g.grid, g.block,
+                     (hipStream_t)stream, n, visits, temperature, u, out_idx, out_p, out_drew);
 }
 
 int rvz_play_gate(rvz_engine* e, double fraction, double timeout_us, double late_us) {
@@ -1978,30 +1982,24 @@ const int32_t* rvz_search_live_count(const rvz_engine* e) {
 #ifdef RVZ_WALK_STATS
 // host int64[10]: sums over games of the 5 walk counters, then their maxima; zeroes them
 int rvz_walk_stats(int32_t n_games, int64_t* out10) {
-    static std::vector<unsigned int> h;
+    std::vector<unsigned int> h;
     const int n = n_games < WALK_STATS_MAX ? n_games : WALK_STATS_MAX;
-    h.assign((size_t)n * 5, 0u);
-    if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_walk), h.size() * 4) != hipSuccess)
-        return RVZ_EHIP;
+    if (take_rows(g_walk, n, h) != RVZ_OK) return RVZ_EHIP;
     for (int i = 0; i < 10; ++i) out10[i] = 0;
     for (int gi = 0; gi < n; ++gi)
         for (int i = 0; i < 5; ++i) {
             out10[i] += h[(size_t)gi * 5 + i];
             if ((int64_t)h[(size_t)gi * 5 + i] > out10[5 + i]) out10[5 + i] = h[(size_t)gi * 5 + i];
         }
-    std::vector<unsigned int> z((size_t)WALK_STATS_MAX * 5, 0u);
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_walk), z.data(), z.size() * 4) == hipSuccess
-               ? RVZ_OK : RVZ_EHIP;
+    return RVZ_OK;
 }
 
 // host int64[11]: the 5 shader-clock categories of the game with the largest total, then the
 // means over games, then that game's index; zeroes them
 int rvz_walk_times(int32_t n_games, int64_t* out11) {
-    static std::vector<unsigned long long> h;
+    std::vector<unsigned long long> h;
     const int n = n_games < WALK_STATS_MAX ? n_games : WALK_STATS_MAX;
-    h.assign((size_t)n * 5, 0ull);
-    if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_wtime), h.size() * 8) != hipSuccess)
-        return RVZ_EHIP;
+    if (take_rows(g_wtime, n, h) != RVZ_OK) return RVZ_EHIP;
     int best = 0;
     unsigned long long bt = 0;
     double mean[5] = {0, 0, 0, 0, 0};
@@ -2018,29 +2016,19 @@ int rvz_walk_times(int32_t n_games, int64_t* out11) {
         out11[5 + i] = (int64_t)mean[i];
     }
     out11[10] = best;
-    std::vector<unsigned long long> z((size_t)WALK_STATS_MAX * 5, 0ull);
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_wtime), z.data(), z.size() * 8) == hipSuccess
-               ? RVZ_OK : RVZ_EHIP;
+    return RVZ_OK;
 }
-#endif
 
-#ifdef RVZ_WALK_STATS
 // tools/exp_play_walks.py: host uint64 [n][9] = g_wtime's 5 columns, then g_ftime's 4; zeroes both
 int rvz_play_walk_read(int32_t n_games, uint64_t* out) {
     const int n = n_games < WALK_STATS_MAX ? n_games : WALK_STATS_MAX;
-    std::vector<unsigned long long> a((size_t)n * 5), b((size_t)n * 4);
-    if (hipMemcpyFromSymbol(a.data(), HIP_SYMBOL(g_wtime), a.size() * 8) != hipSuccess ||
-        hipMemcpyFromSymbol(b.data(), HIP_SYMBOL(g_ftime), b.size() * 8) != hipSuccess)
-        return RVZ_EHIP;
+    std::vector<unsigned long long> a, b;
+    if (take_rows(g_wtime, n, a) != RVZ_OK || take_rows(g_ftime, n, b) != RVZ_OK) return RVZ_EHIP;
     for (int i = 0; i < n; ++i) {
         for (int k = 0; k < 5; ++k) out[(size_t)i * 9 + k] = a[(size_t)i * 5 + k];
         for (int k = 0; k < 4; ++k) out[(size_t)i * 9 + 5 + k] = b[(size_t)i * 4 + k];
     }
-    std::vector<unsigned long long> z((size_t)WALK_STATS_MAX * 5, 0ull);
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_wtime), z.data(), z.size() * 8) != hipSuccess)
-        return RVZ_EHIP;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_ftime), z.data(), (size_t)WALK_STATS_MAX * 4 * 8) ==
-                   hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return RVZ_OK;
 }
 #endif
 
@@ -2066,10 +2054,9 @@ int rvz_act(rvz_engine* e, double temperature, const double* u, int32_t apply, i
     const Range trace_range("rvz.act (expand/backup + action + move)");
     if (!e || !out_idx || !out_p) return RVZ_EINVAL;
     const int ex = e->pending;
-    dim3 grid(grid_games(e->v.G)), block(WPB * WAVE);
     timing_begin(e, 1);
-    if (e->BS == 8) hipLaunchKernelGGL(k_act<8>, grid, block, 0, e->stream, e->v, ex, e->pend_policy, e->pend_is_logits, e->pend_value, temperature, u, apply, out_idx, out_p);
-    else hipLaunchKernelGGL(k_act<6>, grid, block, 0, e->stream, e->v, ex, e->pend_policy, e->pend_is_logits, e->pend_value, temperature, u, apply, out_idx, out_p);
+    launch_games_unchecked(e, k_act<8>, k_act<6>, e->v, ex, e->pend_policy, e->pend_is_logits,
+                           e->pend_value, temperature, u, apply, out_idx, out_p);
     timing_end(e);
     e->pending = 0;
     e->live_dirty = 0;
@@ -2077,19 +2064,34 @@ int rvz_act(rvz_engine* e, double temperature, const double* u, int32_t apply, i
     return launch_check(e, "k_act");
 }
 
-static int64_t play_al4(int64_t n) { return (n + 3) / 4 * 4; }
-
-// scratch (floats): [queue words: q_next + pad, q_done[G] (64-bit {published | claimed} words)]
-// (one 16-B-aligned block at the start, zeroed per launch), leaf planes, need, head-conv rows,
-// logits, value
-// + the pass gate's words (PlayArgs::gate: 8 XCDs x 128 bytes)
-static int64_t play_gwords(int64_t G) { return 2 * play_al4(G); }
-static int64_t play_qwords(int64_t G) { return 4 + play_gwords(G) + 8 * 32; }
+// rvz_play's scratch: the offset of every block and the total, in 4-byte words, each block
+// 16-byte aligned. First the queue words, zeroed per launch as one run of `queue` words: q_next
+// (the task counter, padded to 4), q_done (one 64-bit {published | claimed} word per group, at
+// most G), the pass gate's words (PlayArgs::gate: 8 XCDs x 128 bytes); then the leaf planes, need,
+// the head-conv rows, logits and value.
+struct PlayScratch {
+    int64_t q_next, q_done, gate, queue, x, need, work, logits, value, total;
+};
+static PlayScratch play_scratch(int64_t G, int NSQ, int NPOL) {
+    const auto al4 = [](int64_t n) { return (n + 3) / 4 * 4; };
+    int64_t at = 0;
+    const auto take = [&](int64_t words) { const int64_t o = at; at += al4(words); return o; };
+    PlayScratch s;
+    s.q_next = take(4);
+    s.q_done = take(2 * al4(G));
+    s.gate = take(8 * 32);
+    s.queue = at;
+    s.x = take(G * 3 * NSQ);
+    s.need = take(G);
+    s.work = take(G * 192);
+    s.logits = take(G * NPOL);
+    s.value = take(G);
+    s.total = at;
+    return s;
+}
 int64_t rvz_play_scratch_size(const rvz_engine* e) {
     if (!e) return RVZ_EINVAL;
-    const int64_t G = e->v.G;
-    return play_qwords(G) + play_al4(G * 3 * e->NSQ) + play_al4(G) + play_al4(G * 192) +
-           play_al4(G * e->NPOL) + play_al4(G);
+    return play_scratch(e->v.G, e->NSQ, e->NPOL).total;
 }
 
 #ifndef RVZ_PLAY_GROUP
@@ -2108,21 +2110,25 @@ int64_t rvz_play_scratch_size(const rvz_engine* e) {
 #define RVZ_PLAY_GATE_LATE_US 200.0
 #endif
 extern "C++" {
-template <int F, int NB, int CTW, int PTW, int BS, int OCC>
-static int play_launch(rvz_engine* e, const View& v, const PlayArgs& pa, int slots_per_cu) {
+// T: the (board, filters) pair's H2Tile (rvz_h2.hip.h): k_play runs the evaluator's tile, T::OCC
+// workgroups resident per CU
+template <class T>
+static int play_launch(rvz_engine* e, const View& v, const PlayArgs& pa) {
+    constexpr int F = T::F, BS = T::BS;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->cfg.device) !=
             hipSuccess || cus <= 0)
         cus = 256;
     PlayArgs a = pa;
-    const int slots = cus * slots_per_cu;
+    const int slots = cus * T::OCC;
     dim3 grid;
     if (a.q_next) {     // queue: one persistent workgroup per resident slot, groups of gpw games
         if (a.gpw <= 0) a.gpw = RVZ_PLAY_GROUP;
         if (a.gpw > play_gpw_max<F, BS>()) a.gpw = play_gpw_max<F, BS>();
         a.n_groups = (v.G + a.gpw - 1) / a.gpw;
         grid = dim3(a.n_groups < slots ? a.n_groups : slots);
-        RVZ_HIP(fill32_async(a.q_next, 0u, (size_t)play_qwords(v.G), e->stream), e);
+        RVZ_HIP(fill32_async(a.q_next, 0u, (size_t)play_scratch(v.G, e->NSQ, e->NPOL).queue,
+                             e->stream), e);
     } else {            // static: workgroup w owns group w for every ply
         if (a.gpw <= 0) a.gpw = (v.G + slots - 1) / slots;
         if (a.gpw > play_gpw_max<F, BS>()) a.gpw = play_gpw_max<F, BS>();
@@ -2132,7 +2138,8 @@ static int play_launch(rvz_engine* e, const View& v, const PlayArgs& pa, int slo
     PlayCtx ctx;
     ctx.v = v;
     ctx.a = a;
-    hipLaunchKernelGGL((k_play<F, NB, CTW, PTW, BS, OCC>), grid, dim3(256), 0, e->stream, ctx);
+    hipLaunchKernelGGL((k_play<T::F, T::NB, T::CTW, T::PTW, T::BS, T::OCC>), grid, dim3(256), 0,
+                       e->stream, ctx);
     return launch_check(e, "k_play");
 }
 }  // extern "C++"
@@ -2154,14 +2161,39 @@ int rvz_play_timing_read(uint64_t* host, int n) {
 }
 #endif
 
+// The pass gate's three words for a launch: rvz_play_gate's setting (fraction < 0: the
+// RVZ_PLAY_GATE_* defaults), the environment's RVZ_PLAY_GATE ("fraction,us[,late_us]" or "off")
+// overriding it. frac: Q16, 0 = off (always off without the queue); t, late: 100 MHz ticks.
+struct PlayGate {
+    unsigned frac, t, late;
+};
+static PlayGate play_gate_setting(const rvz_engine* e, bool queue) {
+    double frac = e->gate_frac, us = e->gate_us, late = e->gate_late_us;
+    if (frac < 0.0) {
+        frac = RVZ_PLAY_GATE_FRAC;
+        us = RVZ_PLAY_GATE_US;
+        late = RVZ_PLAY_GATE_LATE_US;
+    }
+    if (const char* gs = getenv("RVZ_PLAY_GATE")) {
+        double f = 0.0, u = 0.0, l = 0.0;
+        const int n = sscanf(gs, "%lf,%lf,%lf", &f, &u, &l);
+        frac = n >= 2 ? f : 0.0;
+        us = u;
+        late = n >= 3 ? l : 0.0;
+    }
+    PlayGate g;
+    g.frac = (queue && frac > 0.0 && us > 0.0) ? (unsigned)(fmin(frac, 1.0) * 65536.0 + 0.5) : 0u;
+    g.t = (unsigned)(us * 100.0);
+    g.late = late > 0.0 ? (unsigned)(late * 100.0) : 0u;
+    return g;
+}
 
 int rvz_play(rvz_engine* e, const rvz_play_args* a) {
     const Range trace_range("rvz.play (fused search + h2 evaluator)");
     if (!e || !a) return RVZ_EINVAL;
     if (!a->params || !a->blob || !a->scratch || !a->seeds || !a->plies_done || !a->out_idx ||
         !a->out_p || (a->reset && !a->games_done) || a->plies < 1 || a->blocks < 0 ||
-        (a->filters != 64 && a->filters != 128 && !(a->filters == 256 && e->BS == 8)) ||
-        a->games_per_workgroup < -PLAY_GPW_MAX ||
+        !h2_tile_ok(e->BS, a->filters) || a->games_per_workgroup < -PLAY_GPW_MAX ||
         e->cfg.leaf_dtype != RVZ_LEAF_F32) {
         e->err = "rvz_play: invalid arguments";
         return RVZ_EINVAL;
@@ -2170,99 +2202,83 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
         e->err = "rvz_play: params, blob and scratch must be 16-byte aligned";
         return RVZ_EINVAL;
     }
-    if (e->pending || (e->searching && e->next_batch > 0)) {
-        e->err = "rvz_play inside a search";
-        return RVZ_EINVAL;
-    }
+    if (in_search(e, "rvz_play")) return RVZ_EINVAL;
     View v = e->v;
     v.live = nullptr;       // the workgroups compact their own rows
     v.row_of = nullptr;
     v.live_total = nullptr;
     v.stats = nullptr;
-    const int64_t G = v.G;
+    if ((a->rec_black || a->rec_white || a->rec_side || a->rec_p) &&
+        !(a->rec_black && a->rec_white && a->rec_side && a->rec_p)) {
+        e->err = "rvz_play: rec_black, rec_white, rec_side and rec_p go together";
+        return RVZ_EINVAL;
+    }
     PlayArgs pa;
+    // the network
     pa.prm = a->params;
     pa.L = make_layout(a->filters, a->blocks, e->BS);
     pa.blob = a->blob;
     pa.n_blocks = a->blocks;
-    float* sc = a->scratch;
-    // games_per_workgroup > 0: static groups of that size; <= 0: the task queue, groups of
-    // -games_per_workgroup games (0: RVZ_PLAY_GROUP)
-    const bool queue = a->games_per_workgroup <= 0;
-    pa.q_next = queue ? reinterpret_cast<unsigned*>(sc) : nullptr;
-    pa.q_done = queue ? reinterpret_cast<unsigned long long*>(sc + 4) : nullptr;
-    pa.n_groups = 0;
-    // the per-XCD pass gate (rvz_play.hip.h play_gate, rvz_play_gate; 8x8 at 128 / 256 filters, queue
-    // schedule only: its words are zeroed with the queue's)
-    pa.gate = queue ? reinterpret_cast<unsigned long long*>(sc + 4 + play_gwords(G)) : nullptr;
-    {   // rvz_play_gate's setting (default: RVZ_PLAY_GATE_DEFAULT), RVZ_PLAY_GATE overriding it
-        double frac = e->gate_frac, us = e->gate_us, late = e->gate_late_us;
-        if (frac < 0.0) {
-            frac = RVZ_PLAY_GATE_FRAC;
-            us = RVZ_PLAY_GATE_US;
-            late = RVZ_PLAY_GATE_LATE_US;
-        }
-        if (const char* gs = getenv("RVZ_PLAY_GATE")) {   // "fraction,us[,late_us]" or "off"
-            double f = 0.0, u = 0.0, l = 0.0;
-            const int n = sscanf(gs, "%lf,%lf,%lf", &f, &u, &l);
-            frac = n >= 2 ? f : 0.0;
-            us = u;
-            late = n >= 3 ? l : 0.0;
-        }
-        pa.gate_frac = (queue && frac > 0.0 && us > 0.0)
-                           ? (unsigned)(fmin(frac, 1.0) * 65536.0 + 0.5) : 0u;
-        pa.gate_t = (unsigned)(us * 100.0);
-        pa.gate_late = late > 0.0 ? (unsigned)(late * 100.0) : 0u;
-    }
-    sc += play_qwords(G);
-    pa.x = sc;
-    sc += play_al4(G * 3 * e->NSQ);
-    pa.need = reinterpret_cast<int32_t*>(sc);
-    sc += play_al4(G);
-    pa.work = sc;
-    sc += play_al4(G * 192);
-    pa.logits = sc;
-    sc += play_al4(G * e->NPOL);
-    pa.value = sc;
     pa.ovf = a->ovf;
+    // the scratch. games_per_workgroup > 0: static groups of that size; <= 0: the task queue,
+    // groups of -games_per_workgroup games (0: RVZ_PLAY_GROUP), with the per-XCD pass gate
+    // (rvz_play.hip.h play_gate; 8x8 at 128 / 256 filters) whose words are zeroed with the queue's
+    const PlayScratch sc = play_scratch(v.G, e->NSQ, e->NPOL);
+    const bool queue = a->games_per_workgroup <= 0;
+    pa.q_next = queue ? reinterpret_cast<unsigned*>(a->scratch + sc.q_next) : nullptr;
+    pa.q_done = queue ? reinterpret_cast<unsigned long long*>(a->scratch + sc.q_done) : nullptr;
+    pa.gate = queue ? reinterpret_cast<unsigned long long*>(a->scratch + sc.gate) : nullptr;
+    pa.x = a->scratch + sc.x;
+    pa.need = reinterpret_cast<int32_t*>(a->scratch + sc.need);
+    pa.work = a->scratch + sc.work;
+    pa.logits = a->scratch + sc.logits;
+    pa.value = a->scratch + sc.value;
+    // the schedule
+    pa.n_groups = 0;
     pa.gpw = queue ? -a->games_per_workgroup : a->games_per_workgroup;
-    pa.plies = a->plies;
-    // a search of one batch (S <= B) evaluates it: its leaf is the root, which the act needs
-    // expanded (the deferred last batch is dead only from the second batch on)
-    pa.skip_last = a->skip_last_eval && e->cfg.num_simulations > e->cfg.batch_size ? 1 : 0;
-    pa.reset = a->reset ? 1 : 0;
+    const PlayGate gate = play_gate_setting(e, queue);
+    pa.gate_frac = gate.frac;
+    pa.gate_t = gate.t;
+    pa.gate_late = gate.late;
+    // the queue's bounded wait (device error 16 when exceeded); RVZ_PLAY_SPIN_LIMIT lowers it to
+    // inject the timeout in tests (tests/test_gpu_play.py)
+    pa.spin_limit = 1u << 26;
+    if (const char* sl = getenv("RVZ_PLAY_SPIN_LIMIT")) pa.spin_limit = (unsigned)strtoul(sl, nullptr, 10);
+    // the search and the plies. A search of one batch (S <= B) evaluates it: its leaf is the
+    // root, which the act needs expanded (the deferred last batch is dead only from the second
+    // batch on). Forced searches go with the deferred last batch (hence E >= 2): the act then
+    // takes the visit counts alone
     pa.S = e->cfg.num_simulations;
     pa.B = e->cfg.batch_size;
+    pa.skip_last = a->skip_last_eval && pa.S > pa.B ? 1 : 0;
+    pa.skip_forced = a->skip_forced_roots && pa.skip_last ? 1 : 0;
+    pa.plies = a->plies;
+    pa.budget = a->ply_budget;
     pa.temperature = a->temperature;
+    pa.reset = a->reset ? 1 : 0;
     pa.seeds = a->seeds;
     pa.stride = a->seed_stride;
+    // outputs: per game, then the launch's counters
     pa.ply_ctr = a->plies_done;
     pa.done = a->games_done;
     pa.out_idx = a->out_idx;
     pa.out_p = a->out_p;
     pa.hist = a->hist;
     pa.rows = reinterpret_cast<unsigned long long*>(a->rows_evaluated);
-    pa.budget = a->ply_budget;
+    pa.unread = reinterpret_cast<unsigned long long*>(a->rows_unread);
+    pa.roots_unread = reinterpret_cast<unsigned long long*>(a->roots_unread);
+    pa.tstats = reinterpret_cast<unsigned long long*>(a->table_stats);
+    // self-play records
+    pa.rec_black = a->rec_black;
+    pa.rec_white = a->rec_white;
+    pa.rec_side = a->rec_side;
+    pa.rec_p = a->rec_p;
+    // the cross-game table (rvz_play_table)
     pa.tab = nullptr;
     pa.tclaim = nullptr;
     pa.tgen = nullptr;
     pa.tmask = 0;
     pa.tmaxd = 0;
-    pa.tstats = reinterpret_cast<unsigned long long*>(a->table_stats);
-    pa.unread = reinterpret_cast<unsigned long long*>(a->rows_unread);
-    // forced searches go with the deferred last batch (hence E >= 2): the act then takes the
-    // visit counts alone
-    pa.skip_forced = a->skip_forced_roots && pa.skip_last ? 1 : 0;
-    pa.roots_unread = reinterpret_cast<unsigned long long*>(a->roots_unread);
-    pa.rec_black = a->rec_black;
-    pa.rec_white = a->rec_white;
-    pa.rec_side = a->rec_side;
-    pa.rec_p = a->rec_p;
-    if ((a->rec_black || a->rec_white || a->rec_side || a->rec_p) &&
-        !(a->rec_black && a->rec_white && a->rec_side && a->rec_p)) {
-        e->err = "rvz_play: rec_black, rec_white, rec_side and rec_p go together";
-        return RVZ_EINVAL;
-    }
     if (e->tab) {
         if (e->tab_blob != a->blob) {   // other weights than the generation's rows came from
             if (e->tab_blob) {
@@ -2286,17 +2302,10 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
         pa.tmask = (unsigned)(e->tslots - 1);
         pa.tmaxd = e->tmaxd;
     }
-    // the queue's bounded wait (device error 16 when exceeded); RVZ_PLAY_SPIN_LIMIT lowers it to
-    // inject the timeout in tests (tests/test_gpu_play.py)
-    pa.spin_limit = 1u << 26;
-    if (const char* sl = getenv("RVZ_PLAY_SPIN_LIMIT")) pa.spin_limit = (unsigned)strtoul(sl, nullptr, 10);
     e->searching = 0;
-    if (e->BS == 8)
-        return a->filters == 64    ? play_launch<64, 2, 2, 4, 8, 2>(e, v, pa, 2)
-               : a->filters == 128 ? play_launch<128, 1, 2, 4, 8, 2>(e, v, pa, 2)
-                                   : play_launch<256, 1, 4, 4, 8, 1>(e, v, pa, 1);
-    return a->filters == 64 ? play_launch<64, 3, 2, 4, 6, 2>(e, v, pa, 2)
-                            : play_launch<128, 1, 2, 3, 6, 2>(e, v, pa, 2);
+    int r = RVZ_EINVAL;
+    h2_tile(e->BS, a->filters, [&](auto t) { r = play_launch<decltype(t)>(e, v, pa); });
+    return r;
 }
 
 // ---- stream-ordered HIP event timer without system fence (bench.py: per-launch kernel

@@ -62,8 +62,41 @@ typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 #ifndef RVZ_H2_ILV
 #define RVZ_H2_ILV 1         // 8x8, 2 boards per workgroup: row-interleaved pixels, edge taps skipped
 #endif                       // (0: board-major pixels, every tap computed)
+#ifndef RVZ_H2_C5NB
+#define RVZ_H2_C5NB 3         // packed 6x6 at F = 64: boards per workgroup (3: 108 of 128 rows, two
+#endif                        // workgroups per CU, the 8x8 pair's tile map; 4: 160 rows, 1 per CU,
+                              // C5 -0.7%; 2: 96 rows, -12%)
 
 constexpr int H2_K = 32, H2_TM = 16, H2_TN = 16;
+
+// The tile table: one workgroup's shape per (board, trunk width) with an h2 instantiation, for
+// the trunk kernel (k_resnet_h2<F, NB, CTW, PTW, BS, OCC>) and the fused self-play kernel (k_play,
+// the same six) alike. F filters; NB boards per pass; a wave's CTW channel tiles x PTW pixel
+// tiles; OCC workgroups per CU. h2_tile calls fn(H2Tile<...>{}) for the pair's tile (host code:
+// fn is a generic lambda that names its kernel from the tile) and returns false, calling
+// nothing, for a pair without one: 256 filters on 6x6, any other width, any other board.
+//   8x8: F = 64 a row-interleaved pair of boards; F = 128 one board; F = 256 the F = 128 map with
+//        4 channel tiles per wave, 144 KB of LDS, one workgroup per CU
+//   6x6, packed: F = 64 RVZ_H2_C5NB boards (3: 108 of 128 pixel rows, 8 tiles); F = 128 one board
+//        (36 of 48 rows)
+template <int F_, int NB_, int CTW_, int PTW_, int BS_, int OCC_>
+struct H2Tile {
+    static constexpr int F = F_, NB = NB_, CTW = CTW_, PTW = PTW_, BS = BS_, OCC = OCC_;
+};
+
+template <class Fn>
+inline bool h2_tile(int bs, int filters, Fn&& fn) {
+    constexpr int C5 = RVZ_H2_C5NB;
+    if (bs == 8 && filters == 64) fn(H2Tile<64, 2, 2, 4, 8, 2>{});
+    else if (bs == 8 && filters == 128) fn(H2Tile<128, 1, 2, 4, 8, 2>{});
+    else if (bs == 8 && filters == 256) fn(H2Tile<256, 1, 4, 4, 8, 1>{});
+    else if (bs == 6 && filters == 64)
+        fn(H2Tile<64, C5, 2, (C5 * 36 + 31) / 32, 6, C5 == 4 ? 1 : 2>{});
+    else if (bs == 6 && filters == 128) fn(H2Tile<128, 1, 2, 3, 6, 2>{});
+    else return false;
+    return true;
+}
+inline bool h2_tile_ok(int bs, int filters) { return h2_tile(bs, filters, [](auto) {}); }
 
 __host__ __device__ inline int64_t h2_layer_elems(int F) { return (int64_t)9 * F * F * 2; }
 __host__ __device__ inline int64_t h2_kstep_elems(int F) { return (int64_t)2 * F * H2_K; }

@@ -30,8 +30,13 @@
 #include <stdlib.h>
 
 #include "../../include/rvz.h"
+#include "rvz_host.hip.h"
 
 namespace {
+
+using rvz::board_ok;
+using rvz::launch_bs;
+using rvz::launch_bs_unchecked;
 
 constexpr int MG_THREADS = 256;
 constexpr int MG_WAVES = MG_THREADS / 64;
@@ -56,7 +61,7 @@ int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
 
 // false: bad arguments
 bool layout(int32_t bs, int32_t n, int32_t table_log2, Layout* L) {
-    if ((bs != 8 && bs != 6) || n < 0) return false;
+    if (!board_ok(bs) || n < 0) return false;
     const int64_t np = bs * bs + 1;
     if ((int64_t)n * np > INT32_MAX) return false;
     int lg = table_log2;
@@ -443,12 +448,8 @@ extern "C" int rvz_merge_positions(int32_t bs, int32_t n, const uint64_t* black,
 
     hipLaunchKernelGGL(k_init, dim3(blocks_for(L.slots > n ? L.slots : n, MG_THREADS)), block, 0,
                        s, n, L.slots, table, first, cnt, hdr);
-    if (bs == 8)
-        hipLaunchKernelGGL(k_validate<8>, per_wave, block, 0, s, n, black, white, status, policy,
-                           value, prov);
-    else
-        hipLaunchKernelGGL(k_validate<6>, per_wave, block, 0, s, n, black, white, status, policy,
-                           value, prov);
+    launch_bs_unchecked(bs, k_validate<8>, k_validate<6>, per_wave, block, s, n, black, white,
+                        status, policy, value, prov);
     hipLaunchKernelGGL(k_insert, per_lane, block, 0, s, n, L.slots, black, white, status, table,
                        prov, first, cnt);
     hipLaunchKernelGGL(k_count, dim3(L.nblk), block, 0, s, n, prov, first, cnt, bsum);
@@ -458,18 +459,9 @@ extern "C" int rvz_merge_positions(int32_t bs, int32_t n, const uint64_t* black,
     hipLaunchKernelGGL(k_zero, dim3(blocks_for((int64_t)(n / 2) * ne, 4 * MG_THREADS)), block, 0,
                        s, hdr, ne, sums);
     const dim3 chunks((n + ACC_ROWS - 1) / ACC_ROWS);
-    if (bs == 8)
-        hipLaunchKernelGGL(k_accumulate<8>, chunks, block, 0, s, n, hot, policy, value, prov, gidx,
-                           sslot, cnt, sums, out_policy, out_value, out_group);
-    else
-        hipLaunchKernelGGL(k_accumulate<6>, chunks, block, 0, s, n, hot, policy, value, prov, gidx,
-                           sslot, cnt, sums, out_policy, out_value, out_group);
-    const dim3 groups(blocks_for(n / 2, MG_WAVES));
-    if (bs == 8)
-        hipLaunchKernelGGL(k_divide<8>, groups, block, 0, s, hdr, mlist, out_count, sums,
-                           out_policy, out_value);
-    else
-        hipLaunchKernelGGL(k_divide<6>, groups, block, 0, s, hdr, mlist, out_count, sums,
-                           out_policy, out_value);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    launch_bs_unchecked(bs, k_accumulate<8>, k_accumulate<6>, chunks, block, s, n, hot, policy,
+                        value, prov, gidx, sslot, cnt, sums, out_policy, out_value, out_group);
+    // the last of the nine launches: its error return answers for all of them
+    return launch_bs(bs, k_divide<8>, k_divide<6>, dim3(blocks_for(n / 2, MG_WAVES)), block, s,
+                     hdr, mlist, out_count, sums, out_policy, out_value);
 }

@@ -1,7 +1,8 @@
 // rvz_negamax.hip.h — what the two negamax lane machines, rvz_solve.hip (solve_rows<BS, MODE>)
 // and rvz_alphabeta.hip (k_alphabeta<BS>), have in common around their loops: the launch
 // geometry, the size of the LDS frame stack and its bound, the per-call row counter with the
-// kernel that zeroes it, and the host side of a launch.
+// kernel that zeroes it, and what the host does before a launch (the launch itself is
+// rvz_host.hip.h's launch_bs on dim3(wgs) x dim3(NM_THREADS)).
 //
 // Shape: one position per LANE. A batch is tens of thousands of small, unequal trees with at
 // most ~12 root moves each, so a wave per position would idle most lanes; here the 64 lanes of a
@@ -39,6 +40,7 @@
 #include <atomic>
 
 #include "../../include/rvz.h"
+#include "rvz_host.hip.h"
 #include "rvz_rules.hip.h"
 
 namespace rvz {
@@ -78,13 +80,6 @@ inline int negamax_prepare(int64_t units, hipStream_t s, int* slot) {
     const int64_t need = (units + NM_THREADS - 1) / NM_THREADS;
     const int wgs = cus * NM_WG_PER_CU;
     return need < wgs ? (int)need : wgs;
-}
-
-// launches k8 (bs == 8) or k6 on wgs workgroups; RVZ_OK or RVZ_EHIP
-template <class... P, class... A>
-int negamax_launch(int bs, void (*k8)(P...), void (*k6)(P...), int wgs, hipStream_t s, A... args) {
-    hipLaunchKernelGGL(bs == 8 ? k8 : k6, dim3(wgs), dim3(NM_THREADS), 0, s, args...);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 // The A/B alternatives (exact f32 MFMA, 3-part bf16 split, VALU heads, the MIOpen epilogue) are
 // built into tools/alt/librvz_alt.so, not into this library.
 #include "rvz_h2.hip.h"
+#include "rvz_host.hip.h"
 #include "rvz_trace.h"
 
 namespace {
@@ -177,63 +178,45 @@ __global__ __launch_bounds__(64) void k_h2_weights(const float* __restrict__ prm
 #ifndef RVZ_H2_DYN
 #define RVZ_H2_DYN 1
 #endif
-#ifndef RVZ_H2_C5NB
-#define RVZ_H2_C5NB 3         // packed 6x6 at F = 64: boards per workgroup (3: 108 of 128 rows, two
-#endif                        // workgroups per CU, the 8x8 pair's tile map; 4: 160 rows, 1 per CU,
-                              // C5 -0.7%; 2: 96 rows, -12%)
 #ifndef RVZ_H2_SPARE
 #define RVZ_H2_SPARE 8        // 1/RVZ_H2_SPARE spare workgroups (a multiple of 8, at least 8)
 #endif
-// board units of one h2 trunk launch, and its grid (RVZ_H2_DYN: + 1/RVZ_H2_SPARE spare workgroups)
+// board units of one h2 trunk launch (the tile's boards per workgroup), and its grid (RVZ_H2_DYN:
+// + 1/RVZ_H2_SPARE spare workgroups)
 static int h2_units(int bs, int filters, int n) {
-    if (bs == 6) return filters == 64 ? (n + RVZ_H2_C5NB - 1) / RVZ_H2_C5NB : n;
-    return filters == 64 ? (n + 1) / 2 : n;
+    int u = n;
+    h2_tile(bs, filters, [&](auto t) { u = (n + decltype(t)::NB - 1) / decltype(t)::NB; });
+    return u;
 }
 static int h2_grid(int bs, int filters, int n) {
     const int u = h2_units(bs, filters, n);
     return RVZ_H2_DYN && u > 0 ? u + ((u + 8 * RVZ_H2_SPARE - 1) / (8 * RVZ_H2_SPARE)) * 8 : u;
 }
 
-template <int BS>
-static void launch_trunk_h2(const float* x, int32_t n, const float* params, const uint16_t* blob,
-                            int32_t filters, int32_t blocks, float* work, hipStream_t s,
-                            const int32_t* n_live, uint64_t* stamps, const uint32_t* stamp_ctr,
-                            int ring) {
-    const Layout L = make_layout(filters, blocks, BS);
-    const dim3 grid(h2_grid(BS, filters, n));
+// the trunk kernel of the pair's tile (rvz_h2.hip.h, h2_tile; the caller checked that it has one)
+static void launch_trunk_h2(int bs, const float* x, int32_t n, const float* params,
+                            const uint16_t* blob, int32_t filters, int32_t blocks, float* work,
+                            hipStream_t s, const int32_t* n_live, uint64_t* stamps,
+                            const uint32_t* stamp_ctr, int ring) {
+    const Layout L = make_layout(filters, blocks, bs);
+    const dim3 grid(h2_grid(bs, filters, n));
     // the unit counter: words n*192 + 2, 3 of the workspace (8-byte aligned)
     unsigned long long* claim =
         RVZ_H2_DYN ? reinterpret_cast<unsigned long long*>(work + (size_t)n * 192 + 2) : nullptr;
-    if (BS == 6) {   // packed 6x6: F=64 3 boards = 128 pixel rows (8 tiles); F=128 1 board = 48
-        if (filters == 64)
-            hipLaunchKernelGGL((k_resnet_h2<64, RVZ_H2_C5NB, 2, (RVZ_H2_C5NB * 36 + 31) / 32,
-                                            6, RVZ_H2_C5NB == 4 ? 1 : 2>), grid, dim3(256), 0, s, x, n,
-                               params, L, blob, blocks, work, n_live, stamps, stamp_ctr, ring,
-                               claim);
-        else
-            hipLaunchKernelGGL((k_resnet_h2<128, 1, 2, 3, 6, 2>), grid, dim3(256), 0, s, x, n,
-                               params, L, blob, blocks, work, n_live, stamps, stamp_ctr, ring,
-                               claim);
-    } else if (filters == 64)
-        hipLaunchKernelGGL((k_resnet_h2<64, 2, 2, 4, 8, 2>), grid, dim3(256), 0, s, x, n,
-                           params, L, blob, blocks, work, n_live, stamps, stamp_ctr, ring,
-                           claim);
-    else if (filters == 128)
-        hipLaunchKernelGGL((k_resnet_h2<128, 1, 2, 4, 8, 2>), grid, dim3(256), 0, s, x, n, params,
-                           L, blob, blocks, work, n_live, stamps, stamp_ctr, ring, claim);
-    else   // F=256: the F=128 tile map with 4 channel tiles per wave; 144 KB of LDS, 1 per CU
-        hipLaunchKernelGGL((k_resnet_h2<256, 1, 4, 4, 8, 1>), grid, dim3(256), 0, s, x, n, params,
-                           L, blob, blocks, work, n_live, stamps, stamp_ctr, ring, claim);
+    h2_tile(bs, filters, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((k_resnet_h2<T::F, T::NB, T::CTW, T::PTW, T::BS, T::OCC>), grid,
+                           dim3(256), 0, s, x, n, params, L, blob, blocks, work, n_live, stamps,
+                           stamp_ctr, ring, claim);
+    });
 }
 
 extern "C" {
 
-static bool board_ok(int32_t bs) { return bs == 8 || bs == 6; }
-// trunk widths with an h2 instantiation: 64 and 128 on both boards, 256 on 8x8
+using rvz::board_ok;
+// trunk widths of the parameter and blob layouts, which do not depend on the board (a trunk
+// launch also needs a tile for its board: h2_tile_ok)
 static bool width_ok(int32_t filters) { return filters == 64 || filters == 128 || filters == 256; }
-static bool trunk_ok(int32_t bs, int32_t filters) {
-    return board_ok(bs) && (filters == 64 || filters == 128 || (filters == 256 && bs == 8));
-}
 
 int64_t rvz_resnet_params_size(int32_t board, int32_t filters, int32_t blocks) {
     if (!width_ok(filters) || blocks < 0 || !board_ok(board)) return RVZ_EINVAL;
@@ -276,14 +259,9 @@ int rvz_resnet_heads_fc_ex(int32_t board, const float* work, int32_t n, const fl
     if (((uintptr_t)params & 15) != 0 || ((uintptr_t)work & 15) != 0) return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
     const Layout L = make_layout(filters, blocks, board);
-    const dim3 grid((n + 15) / 16), block(256);
-    if (board == 8)
-        hipLaunchKernelGGL(k_heads_mfma<8>, grid, block, 0, (hipStream_t)stream, work, n, params,
-                           L, logits, value, n_live, stamp_ctr);
-    else
-        hipLaunchKernelGGL(k_heads_mfma<6>, grid, block, 0, (hipStream_t)stream, work, n, params,
-                           L, logits, value, n_live, stamp_ctr);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return rvz::launch_bs(board, k_heads_mfma<8>, k_heads_mfma<6>, dim3((n + 15) / 16), dim3(256),
+                          (hipStream_t)stream, work, n, params, L, logits, value, n_live,
+                          stamp_ctr);
 }
 
 int rvz_resnet_heads_fc(int32_t board, const float* work, int32_t n, const float* params,
@@ -322,7 +300,7 @@ int rvz_resnet_trunk_h2_ex(int32_t board, const float* x, int32_t n, const float
                            const int32_t* n_live, uint64_t* stamps, const uint32_t* stamp_ctr,
                            int32_t ring, void* stream) {
     const rvz::Range trace_range("rvz.eval.trunk (k_resnet_h2)");
-    if (!x || !params || !blob || !work || n < 0 || blocks < 0 || !trunk_ok(board, filters) ||
+    if (!x || !params || !blob || !work || n < 0 || blocks < 0 || !h2_tile_ok(board, filters) ||
         (stamp_ctr && (!stamps || ring <= 0)))
         return RVZ_EINVAL;
     // work: 16-byte aligned (the 64-bit unit-counter atomic at words n*192 + 2, 3 and the
@@ -331,13 +309,8 @@ int rvz_resnet_trunk_h2_ex(int32_t board, const float* x, int32_t n, const float
         ((uintptr_t)work & 15) != 0)
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (board == 8)
-        launch_trunk_h2<8>(x, n, params, blob, filters, blocks, work, s, n_live,
-                           stamps, stamp_ctr, ring > 0 ? ring : 1);
-    else
-        launch_trunk_h2<6>(x, n, params, blob, filters, blocks, work, s, n_live,
-                           stamps, stamp_ctr, ring > 0 ? ring : 1);
+    launch_trunk_h2(board, x, n, params, blob, filters, blocks, work, (hipStream_t)stream, n_live,
+                    stamps, stamp_ctr, ring > 0 ? ring : 1);
     return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
 }
 
@@ -349,7 +322,7 @@ int rvz_resnet_trunk_h2(int32_t board, const float* x, int32_t n, const float* p
 }
 
 int32_t rvz_resnet_h2_grid(int32_t board, int32_t filters, int32_t n) {
-    if (!trunk_ok(board, filters) || n < 0) return RVZ_EINVAL;
+    if (!h2_tile_ok(board, filters) || n < 0) return RVZ_EINVAL;
     return h2_grid(board, filters, n);
 }
 

@@ -360,7 +360,7 @@ int solve_prepare(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* 
                   const int32_t* status, int32_t max_empties, int64_t node_limit,
                   const int32_t* out_score, const int32_t* out_move, hipStream_t s, int* slot,
                   int per_row = 1) {
-    if ((bs != 8 && bs != 6) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
+    if (!board_ok(bs) || n < 0 || max_empties < 0 || max_empties > RVZ_SOLVE_MAX_EMPTIES ||
         node_limit <= 0 || (n > 0 && (!black || !white || !status || !out_score || !out_move)))
         return RVZ_EINVAL;
     return n == 0 ? 0 : negamax_prepare((int64_t)n * per_row, s, slot);
@@ -376,9 +376,9 @@ extern "C" int rvz_solve(int32_t bs, int32_t n, const uint64_t* black, const uin
     const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_score,
                                   out_move, s, &slot);
     if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
-    return negamax_launch(bs, k_solve<8>, k_solve<6>, wgs, s, n, black, white, status,
-                          max_empties, (long long)node_limit, out_score, out_move,
-                          (long long*)out_nodes, slot);
+    return launch_bs(bs, k_solve<8>, k_solve<6>, dim3(wgs), dim3(NM_THREADS), s, n, black, white,
+                     status, max_empties, (long long)node_limit, out_score, out_move,
+                     (long long*)out_nodes, slot);
 }
 
 extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
@@ -392,9 +392,9 @@ extern "C" int rvz_solve_window(int32_t bs, int32_t n, const uint64_t* black,
     const int wgs = solve_prepare(bs, n, black, white, status, max_empties, node_limit, out_score,
                                   out_move, s, &slot);
     if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
-    return negamax_launch(bs, k_solve_window<8>, k_solve_window<6>, wgs, s, n, black, white,
-                          status, max_empties, (long long)node_limit, alpha, beta,
-                          order_min_empties, out_score, out_move, (long long*)out_nodes, slot);
+    return launch_bs(bs, k_solve_window<8>, k_solve_window<6>, dim3(wgs), dim3(NM_THREADS), s, n,
+                     black, white, status, max_empties, (long long)node_limit, alpha, beta,
+                     order_min_empties, out_score, out_move, (long long*)out_nodes, slot);
 }
 
 extern "C" int rvz_solve_moves(int32_t bs, int32_t n, const uint64_t* black, const uint64_t* white,
@@ -403,7 +403,7 @@ extern "C" int rvz_solve_moves(int32_t bs, int32_t n, const uint64_t* black, con
                                int32_t* out_scores, int32_t* out_count, int64_t* out_nodes,
                                void* stream) {
     if (alpha < -64 || alpha >= beta || beta > 64 || order_min_empties < 0) return RVZ_EINVAL;
-    if ((bs == 8 || bs == 6) && n > 0 && (int64_t)n * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
+    if (board_ok(bs) && n > 0 && (int64_t)n * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int per_row = max_empties > 1 ? max_empties : 1;
     int slot = 0;
@@ -411,7 +411,7 @@ extern "C" int rvz_solve_moves(int32_t bs, int32_t n, const uint64_t* black, con
                                   out_count, s, &slot, per_row);
     if (wgs <= 0) return wgs;                      // an error code, or RVZ_OK for n == 0
     const int tasks = n * per_row;                 // per_row <= 14 < S*S + 1: fits
-    return negamax_launch(bs, k_solve_moves<8>, k_solve_moves<6>, wgs, s, tasks, n, black, white,
-                          status, max_empties, (long long)node_limit, alpha, beta,
-                          order_min_empties, out_scores, out_count, (long long*)out_nodes, slot);
+    return launch_bs(bs, k_solve_moves<8>, k_solve_moves<6>, dim3(wgs), dim3(NM_THREADS), s, tasks,
+                     n, black, white, status, max_empties, (long long)node_limit, alpha, beta,
+                     order_min_empties, out_scores, out_count, (long long*)out_nodes, slot);
 }

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/rvz.h"
+#include "rvz_host.hip.h"
 #include "rvz_rules.hip.h"
 
 namespace {
@@ -164,40 +165,30 @@ int blocks_for(int64_t units, int per_block) {
 extern "C" int rvz_board_symmetry(int32_t bs, int32_t n, const uint64_t* black,
                                   const uint64_t* white, const int32_t* sym, uint64_t* out_black,
                                   uint64_t* out_white, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 ||
+    if (!board_ok(bs) || n < 0 ||
         (n > 0 && (!black || !white || !sym || !out_black || !out_white)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid(blocks_for(n, SYM_THREADS)), block(SYM_THREADS);
-    if (bs == 8)
-        hipLaunchKernelGGL(k_board_symmetry<8>, grid, block, 0, (hipStream_t)stream, n, black,
-                           white, sym, out_black, out_white);
-    else
-        hipLaunchKernelGGL(k_board_symmetry<6>, grid, block, 0, (hipStream_t)stream, n, black,
-                           white, sym, out_black, out_white);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return launch_bs(bs, k_board_symmetry<8>, k_board_symmetry<6>,
+                     dim3(blocks_for(n, SYM_THREADS)), dim3(SYM_THREADS), (hipStream_t)stream, n,
+                     black, white, sym, out_black, out_white);
 }
 
 extern "C" int rvz_training_rows(int32_t bs, int32_t n, const uint64_t* black,
                                  const uint64_t* white, const int32_t* status, const float* policy,
                                  const int32_t* sym, int32_t fan, float* out_states,
                                  float* out_policy, int32_t* out_quirk, void* stream) {
-    if ((bs != 8 && bs != 6) || n < 0 || (fan != 1 && fan != 8)) return RVZ_EINVAL;
+    if (!board_ok(bs) || n < 0 || (fan != 1 && fan != 8)) return RVZ_EINVAL;
     if ((int64_t)n * fan * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
     if (n > 0 && (!black || !white || !status || !policy || !out_states || !out_policy ||
                   (fan == 1 && !sym) || ((uintptr_t)out_states & 15u) != 0))   // float4 stores
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    dim3 grid(blocks_for(n, SYM_WAVES)), block(SYM_THREADS);
-    hipStream_t s = (hipStream_t)stream;
-#define RVZ_SYM_LAUNCH(BS, FAN)                                                                  \
-    hipLaunchKernelGGL((k_training_rows<BS, FAN>), grid, block, 0, s, n, black, white, status,   \
-                       policy, sym, out_states, out_policy, out_quirk)
-    if (bs == 8) {
-        if (fan == 1) RVZ_SYM_LAUNCH(8, 1); else RVZ_SYM_LAUNCH(8, 8);
-    } else {
-        if (fan == 1) RVZ_SYM_LAUNCH(6, 1); else RVZ_SYM_LAUNCH(6, 8);
-    }
-#undef RVZ_SYM_LAUNCH
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    const auto launch = [&](auto k8, auto k6) {
+        return launch_bs(bs, k8, k6, dim3(blocks_for(n, SYM_WAVES)), dim3(SYM_THREADS),
+                         (hipStream_t)stream, n, black, white, status, policy, sym, out_states,
+                         out_policy, out_quirk);
+    };
+    return fan == 1 ? launch(k_training_rows<8, 1>, k_training_rows<6, 1>)
+                    : launch(k_training_rows<8, 8>, k_training_rows<6, 8>);
 }

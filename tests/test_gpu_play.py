@@ -104,6 +104,30 @@ def test_fused_other_geometries(board, blocks, filters, gpw):
     _same(a, _plain(net, G, S, plies, True, True))
 
 
+@pytest.mark.parametrize("board,G,words", [(8, 5, 2540), (6, 5, 1980), (8, 203, 92224)])
+def test_play_scratch_size(board, G, words):
+    """rvz_play's scratch in 4-byte words: the queue head (4), q_done (2 al4(G)), the gate (256),
+    then x (3 G S^2), need (G), work (192 G), logits (G (S^2 + 1)) and value (G), each rounded up
+    to a multiple of 4 (al4). G = 5: 276 + 960 + 8 + 960 + 328 + 8 on 8x8, 276 + 540 + 8 + 960 +
+    188 + 8 on 6x6; G = 203 on 8x8: 668 + 38976 + 204 + 38976 + 13196 + 204."""
+    import rvz
+    eng = rvz.Engine(G, 64, 64, board_size=board)
+    assert eng.lib.rvz_play_scratch_size(eng._h) == words
+
+
+@pytest.mark.parametrize("blocks,filters", [(2, 64), (1, 128)])
+@pytest.mark.parametrize("gpw", [0, 5], ids=["queue", "static5"])
+def test_fused_6x6_with_a_padded_scratch_layout(blocks, filters, gpw):
+    """6x6 with a game count that is no multiple of 4 (G = 37: 3 G S^2 = 3996 is one, G = 37 and
+    G (S^2 + 1) = 1369 are not, so need, logits and value each end in padding, and the queue's
+    q_done rounds 37 up to 40): the task queue and static groups of 5 play the runner's games."""
+    net = _net(6, blocks, filters, seed=1)
+    G, S, plies = 37, 200, 8
+    a = _fused(net, G, S, plies, True, True, gpw=gpw)
+    assert len(set(a[1][3].tolist())) > 1                  # distinct games by the fourth ply
+    _same(a, _plain(net, G, S, plies, True, True))
+
+
 def test_fused_headline_configuration_at_full_size():
     """bench.py's C2 workload at full size: 4,096 games x 800 sims, the 6x64 net, memo and the
     last batch left to it, 64 plies (a whole game and its restarts): identical to the runner."""
