@@ -2145,15 +2145,15 @@ static int play_launch(rvz_engine* e, const View& v, const PlayArgs& pa) {
 }  // extern "C++"
 
 #ifdef RVZ_PLAY_TIMING
-// tools/exp_play_phases.py: host copy of g_play_t (n workgroups x 12) and g_pass_t (n x 6), then
-// zeroed
+// tools/exp_play_phases.py: host copy of g_play_t (n workgroups x PLAY_T_SLOTS = 14) and g_pass_t
+// (n x 6), then zeroed
 int rvz_play_timing_read(uint64_t* host, int n) {
-    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_play_t), (size_t)n * 12 * 8) != hipSuccess)
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_play_t), (size_t)n * PLAY_T_SLOTS * 8) != hipSuccess)
         return RVZ_EHIP;
-    if (hipMemcpyFromSymbol(host + (size_t)n * 12, HIP_SYMBOL(g_pass_t), (size_t)n * 6 * 8) !=
-        hipSuccess)
+    if (hipMemcpyFromSymbol(host + (size_t)n * PLAY_T_SLOTS, HIP_SYMBOL(g_pass_t),
+                            (size_t)n * 6 * 8) != hipSuccess)
         return RVZ_EHIP;
-    std::vector<unsigned long long> z((size_t)16384 * 12, 0ull);
+    std::vector<unsigned long long> z((size_t)16384 * PLAY_T_SLOTS, 0ull);
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_pass_t), z.data(), (size_t)16384 * 6 * 8) != hipSuccess)
         return RVZ_EHIP;
     return hipMemcpyToSymbol(HIP_SYMBOL(g_play_t), z.data(), z.size() * 8) == hipSuccess
@@ -2244,6 +2244,10 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
     // inject the timeout in tests (tests/test_gpu_play.py)
     pa.spin_limit = 1u << 26;
     if (const char* sl = getenv("RVZ_PLAY_SPIN_LIMIT")) pa.spin_limit = (unsigned)strtoul(sl, nullptr, 10);
+    // the one-board shape for the C2 pair's passes with one live board (on; RVZ_PLAY_SINGLE_PASS=0
+    // runs the pair shape everywhere: the tests' and same-library A/Bs' switch, the same games)
+    pa.single_pass = 1;
+    if (const char* sp = getenv("RVZ_PLAY_SINGLE_PASS")) pa.single_pass = atoi(sp) != 0;
     // the search and the plies. A search of one batch (S <= B) evaluates it: its leaf is the
     // root, which the act needs expanded (the deferred last batch is dead only from the second
     // batch on). Forced searches go with the deferred last batch (hence E >= 2): the act then

@@ -97,6 +97,13 @@ inline bool h2_tile(int bs, int filters, Fn&& fn) {
     return true;
 }
 inline bool h2_tile_ok(int bs, int filters) { return h2_tile(bs, filters, [](auto) {}); }
+// The channel groups of the 1x1 head convs (head_convs_cg) of a net: the table tile's four waves
+// over its boards, whatever board count a pass runs at, so that a one-board pass of the 64-filter
+// net (h2_pass_single) sums its head convs in the pair's order and gives the pair's bits.
+template <int F, int BS>
+__host__ __device__ constexpr int h2_head_cg() {
+    return F == 64 ? 4 / (BS == 8 ? 2 : RVZ_H2_C5NB) : 4;
+}
 
 __host__ __device__ inline int64_t h2_layer_elems(int F) { return (int64_t)9 * F * F * 2; }
 __host__ __device__ inline int64_t h2_kstep_elems(int F) { return (int64_t)2 * F * H2_K; }
@@ -1065,8 +1072,8 @@ __device__ __forceinline__ void h2_pass(char* smem, const float* __restrict__ x,
     PASS_ADD(1, tp2 - tp0);   // stem + tower
     // the 1x1 head convs -> work (the FC heads are the next launch, k_heads_mfma)
     const ActH2<F, G::NPIX> act{actA, simg.pk};
-    head_convs<F, NBOARD, NTHR, BS, true, ILV>(act, reinterpret_cast<float*>(actB), prm, L, hout,
-                                              tid, bar);
+    head_convs_cg<F, NBOARD, NTHR, h2_head_cg<F, BS>(), BS, true, ILV>(
+        act, reinterpret_cast<float*>(actB), prm, L, hout, tid, bar);
 #ifdef RVZ_PLAY_TIMING
     {
         PASS_NOW(tp3);
@@ -1074,6 +1081,61 @@ __device__ __forceinline__ void h2_pass(char* smem, const float* __restrict__ x,
         PASS_ADD(3, 1);
     }
 #endif
+}
+
+// A pointer every lane holds the same value of, as scalar registers, with its address space
+// kept: a global pointer (wave_uniform) or an LDS pointer (wave_uniform_lds: its 32-bit offset).
+// Rebuilt from a plain integer it would be a flat pointer: 64-bit addresses per lane and flat
+// loads in place of ds_read / global_load.
+template <class T>
+__device__ __forceinline__ T* wave_uniform(T* p) {
+    typedef __attribute__((address_space(1))) T GT;
+    const uint64_t v = (uint64_t)(GT*)p;
+    const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+    return (T*)(GT*)u;
+}
+template <class T>
+__device__ __forceinline__ T* wave_uniform_lds(T* p) {
+    typedef __attribute__((address_space(3))) T LT;
+    const uint32_t v = (uint32_t)(uintptr_t)(LT*)p;
+    return (T*)(LT*)(uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+// A pass of the fused kernel over ONE board at the one-board tile shape (PTW pixel tiles per
+// wave, half the pair's; not interleaved), for a pass of the pair shape whose second board does
+// not exist: the stem from the board's bitboards, the tower, its own ranged re-run and the head
+// convs into column `slot` of the FC heads' LDS rows (HeadsInLds). Per output the products are
+// those of the pair shape in the same order (tap-major, k-step planes, mma3's parts; the taps
+// the interleaved shape skips are exact-zero products here) and the head convs keep the pair's
+// channel groups (h2_head_cg), so the row's outputs are bitwise the pair shape's. smem: the head
+// of the caller's LDS (CfgH of the one-board shape is the smaller); its zero rows, range maxima
+// and overflow words are pass-local. A call like h2_trunk_ranged, for the same reason: inlined
+// beside the pair shape its registers would push the hot path into spills. Everything crosses
+// by value, the parameter layout is recomputed from the net's shape, and the sticky overflow
+// flag is the result.
+template <int F, int CTW, int PTW, int BS>
+__device__ __attribute__((noinline)) int h2_pass_single(char* smem, const uint64_t* bits,
+                                                        const float* prm, const uint16_t* blob,
+                                                        int n_blocks, float* hin, int slot,
+                                                        int nslots, int tid, int lane, int wave) {
+    // a function's arguments arrive in vector registers: without these the weight loads' buffer
+    // descriptor and scalar offsets count as divergent and every load becomes a waterfall loop
+    smem = wave_uniform_lds(smem);
+    bits = wave_uniform_lds(bits);
+    prm = wave_uniform(prm);
+    blob = wave_uniform(blob);
+    hin = wave_uniform_lds(hin);
+    n_blocks = __builtin_amdgcn_readfirstlane(n_blocks);
+    slot = __builtin_amdgcn_readfirstlane(slot);
+    nslots = __builtin_amdgcn_readfirstlane(nslots);
+    wave = __builtin_amdgcn_readfirstlane(wave);
+    const Layout L = make_layout(F, n_blocks, BS);
+    const int gb[1] = {0};          // (a row of x: not read, the input is the bitboards)
+    bool ovf = false;
+    h2_pass<F, 1, CTW, PTW, BS>(smem, nullptr, gb, bits, prm, L, blob, n_blocks,
+                                HeadsInLds<BS>{hin, slot, nslots}, tid, lane, wave, ovf);
+    return ovf ? 1 : 0;
 }
 
 // bits 52-55 of a workgroup's end stamp: the XCD it ran on (HW_REG_XCC_ID; bench.py --stamps-dump)

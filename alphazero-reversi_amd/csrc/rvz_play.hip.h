@@ -11,7 +11,9 @@
 //    batch's selection, or, after the last batch, act + autoreset, until the game has queued its
 //    next NN row or has committed `plies` plies in this launch;
 //  * an evaluation phase: the queued rows in NBOARD-board passes of the h2 trunk (h2_pass, the
-//    code of k_resnet_h2) and 16-board passes of the FC heads (heads_fc16, as k_heads_mfma).
+//    code of k_resnet_h2) and 16-board passes of the FC heads (heads_fc16, as k_heads_mfma); a
+//    pass of the 8x8 pair with one live board runs that board at the one-board shape
+//    (h2_pass_single: the same bits for half the MFMAs).
 // Each per-game computation is the one the unfused launches make, and an h2 row's outputs depend
 // only on its position (test_h2_live_rows), so the games are bit-identical to SelfPlayRunner's
 // (tests/test_gpu_play.py). One exception changes rows, not games: with skip_last a search whose
@@ -42,6 +44,8 @@ struct PlayArgs {
     unsigned long long* rows;   // += the rows this launch evaluated, or null
     const int32_t* budget;      // [G] plies game g commits in this launch (<= plies), or null
     unsigned spin_limit;        // queue waits give up (ERR_SCHED) after this many sleeps
+    int single_pass;            // C2: a pass with one live board runs the one-board shape (the
+                                // same bits; 0, RVZ_PLAY_SINGLE_PASS=0: the pair shape everywhere)
     // the cross-game NN-output table (rvz_play_table; tab null: off)
     unsigned long long* tab;    // [slots][TabGeo<BS>::STRIDE] granules {value, tag = generation}
     unsigned* tclaim;           // [slots] the generation that claimed the slot
@@ -340,9 +344,11 @@ __device__ __forceinline__ const PlayCtx& play_ctx() {
 // [2] the FC heads, [3] the whole launch; [4] cycles of the loop, [5] trunk passes, [6] rows,
 // [7] the workgroup's XCC / CU (HW_ID); [8] cycles drawing tasks (queue: the scans of the group
 // words and the waits when nothing was ready), [9] tasks, [10] the launch clock at the
-// workgroup's end (s_memrealtime, 100 MHz), [11] empty scans (nothing ready, plies left)
+// workgroup's end (s_memrealtime, 100 MHz), [11] empty scans (nothing ready, plies left), [12] the
+// trunk passes with fewer live boards than NBOARD and [13] their cycles (part of [5] and [1])
 #ifdef RVZ_PLAY_TIMING
-__device__ unsigned long long g_play_t[16384][12];
+constexpr int PLAY_T_SLOTS = 14;
+__device__ unsigned long long g_play_t[16384][PLAY_T_SLOTS];
 #define PT_NOW(t) const unsigned long long t = __builtin_amdgcn_s_memtime()
 #define PT_ADD(i, v) if (tid == 0 && blockIdx.x < 16384) g_play_t[blockIdx.x][i] += (v)
 #else
@@ -364,6 +370,8 @@ void k_play(PlayCtx ctx0) {
     constexpr int NPOL = Geo<BS>::NPOL;
     constexpr bool HLDS = play_heads_lds<F, BS>();
     constexpr int GMAX = play_gpw_max<F, BS>();
+    // the 8x8 / 64-filter pair (C2): a pass with one live board runs at the one-board tile shape
+    constexpr bool PLAY_SINGLE = F == 64 && NBOARD == 2 && BS == 8 && (PTW & 1) == 0 && HLDS;
     constexpr int HROW = heads_in_floats(BS) / 16;
     // LDS: the trunk's activation image; between passes its head holds the search phase's act /
     // reset scratch (per wave) or (not HLDS) the FC heads' input rows
@@ -660,6 +668,8 @@ void k_play(PlayCtx ctx0) {
                 // rows that would leave the last pass partly empty wait one cycle (their games
                 // sit out one search phase: a game's computation is the same whichever cycle
                 // evaluates its row), unless they waited last cycle or there is no full pass
+                // (never holding, now that an odd row's own pass is a one-board pass, measured
+                // 1.0-1.8% behind holding on the 60-ply line: tools/patches/play_no_hold.patch)
                 int hold = n > NBOARD ? n % NBOARD : 0;
                 for (int j = ng - 1; j >= 0; --j) {
                     const int fj = st_f[j];
@@ -701,21 +711,45 @@ void k_play(PlayCtx ctx0) {
                     }
                 }
                 const PlayArgs& a = play_ctx().a;
-                int gb[NBOARD];
+                PT_NOW(t_p0);
+                // the pair shape with one live board (its second row does not exist): that board
+                // alone at the one-board tile shape, 216 MFMAs per wave and conv instead of 396,
+                // with the pair shape's bits (h2_pass_single). Workgroup-uniform.
+                bool single = false;
+                if constexpr (PLAY_SINGLE)
+                    single = a.single_pass &&
+                             __builtin_amdgcn_readfirstlane(q_rows[p0 + 1]) < 0;
+                if (single) {
+                    if constexpr (PLAY_SINGLE) {
+                        const int t = opaque_tid();
+                        ovf |= h2_pass_single<F, CTW, PTW / 2, BS>(
+                                   smem, q_bits + 3 * p0, a.prm, a.blob, a.n_blocks, hin, p0, nq,
+                                   t, t & 63, __builtin_amdgcn_readfirstlane(t >> 6)) != 0;
+                    }
+                } else {
+                    int gb[NBOARD];
 #pragma unroll
-                for (int k = 0; k < NBOARD; ++k) gb[k] = q_rows[p0 + k];
-                const int t = opaque_tid();
-                if constexpr (HLDS)
-                    h2_pass<F, NBOARD, CTW, PTW, BS>(
-                        smem, a.x, gb, q_bits + 3 * p0, a.prm, a.L, a.blob, a.n_blocks,
-                        HeadsInLds<BS>{hin, p0, nq}, t, t & 63,
-                        __builtin_amdgcn_readfirstlane(t >> 6), ovf);
-                else
-                    h2_pass<F, NBOARD, CTW, PTW, BS>(
-                        smem, a.x, gb, q_bits + 3 * p0, a.prm, a.L, a.blob, a.n_blocks,
-                        HeadsGlobalIdx<NBOARD>(a.work, gb), t, t & 63,
-                        __builtin_amdgcn_readfirstlane(t >> 6), ovf);
+                    for (int k = 0; k < NBOARD; ++k) gb[k] = q_rows[p0 + k];
+                    const int t = opaque_tid();
+                    if constexpr (HLDS)
+                        h2_pass<F, NBOARD, CTW, PTW, BS>(
+                            smem, a.x, gb, q_bits + 3 * p0, a.prm, a.L, a.blob, a.n_blocks,
+                            HeadsInLds<BS>{hin, p0, nq}, t, t & 63,
+                            __builtin_amdgcn_readfirstlane(t >> 6), ovf);
+                    else
+                        h2_pass<F, NBOARD, CTW, PTW, BS>(
+                            smem, a.x, gb, q_bits + 3 * p0, a.prm, a.L, a.blob, a.n_blocks,
+                            HeadsGlobalIdx<NBOARD>(a.work, gb), t, t & 63,
+                            __builtin_amdgcn_readfirstlane(t >> 6), ovf);
+                }
                 __syncthreads();
+#ifdef RVZ_PLAY_TIMING
+                if (p0 + NBOARD > nq) {   // a pass with fewer live boards than NBOARD
+                    PT_NOW(t_p1);
+                    PT_ADD(12, 1);
+                    PT_ADD(13, t_p1 - t_p0);
+                }
+#endif
             }
             PT_NOW(t_c3);
             PT_ADD(1, t_c3 - t_c2);

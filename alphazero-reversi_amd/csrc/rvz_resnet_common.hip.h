@@ -60,15 +60,20 @@ __host__ __device__ inline Layout make_layout(int F, int NB, int BS = 8) {
 struct BarWG {
     __device__ __forceinline__ void operator()() const { __syncthreads(); }
 };
-template <int F, int NBOARD, int NTHR, int BS = 8, bool PACKED = false, bool ILV = false, class Act,
-          class Out, class Bar = BarWG>
-__device__ __forceinline__ void head_convs(const Act& act, float* part,
-                                           const float* __restrict__ prm, const Layout& L,
-                                           const Out& hpv, int tid, const Bar& bar = Bar{}) {
-    constexpr int NW = NTHR / 64, CG = NW / NBOARD, CPG = F / CG;
+// CG: the channel groups a board's channels are split into, one wave per (board, group); each
+// group's sum is one fma chain and the groups are added in order, so CG fixes the bits of the
+// result. head_convs takes every wave (CG = waves / boards); head_convs_cg names CG, for a pass
+// shape that must give the bits of another shape's split (waves past NBOARD * CG only sum).
+template <int F, int NBOARD, int NTHR, int CG, int BS = 8, bool PACKED = false, bool ILV = false,
+          class Act, class Out, class Bar = BarWG>
+__device__ __forceinline__ void head_convs_cg(const Act& act, float* part,
+                                              const float* __restrict__ prm, const Layout& L,
+                                              const Out& hpv, int tid, const Bar& bar = Bar{}) {
+    constexpr int NW = NTHR / 64, CPG = F / CG;
     static_assert(CPG % 8 == 0, "8-channel reads");
+    static_assert(CG >= 1 && NBOARD * CG <= NW, "one wave per (board, channel group)");
     const int lane = tid & 63;
-    {
+    if (NBOARD * CG == NW || __builtin_amdgcn_readfirstlane(tid >> 6) < NBOARD * CG) {
         const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
         // PACKED: board b's cells are act rows b * BS^2 + cell (h2); else the 8x8 grid
         const int b = wave % NBOARD, cg = wave / NBOARD, row = b * 64 + lane;
@@ -110,6 +115,14 @@ __device__ __forceinline__ void head_convs(const Act& act, float* part,
         const float bias = c2 < 2 ? prm[L.pol_b + c2] : prm[L.val_b];
         hpv.store(b, c2 * CELLS + cell, fmaxf(acc + bias, 0.0f));
     }
+}
+template <int F, int NBOARD, int NTHR, int BS = 8, bool PACKED = false, bool ILV = false, class Act,
+          class Out, class Bar = BarWG>
+__device__ __forceinline__ void head_convs(const Act& act, float* part,
+                                           const float* __restrict__ prm, const Layout& L,
+                                           const Out& hpv, int tid, const Bar& bar = Bar{}) {
+    head_convs_cg<F, NBOARD, NTHR, NTHR / 64 / NBOARD, BS, PACKED, ILV>(act, part, prm, L, hpv, tid,
+                                                                        bar);
 }
 struct HeadsLds {        // hpv rows in LDS
     float* p;

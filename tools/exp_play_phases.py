@@ -1,7 +1,9 @@
 """Phase split of the fused self-play kernel (k_play) from an instrumented build
 (tools/ab_lib_build.sh ptime -DRVZ_PLAY_TIMING; RVZ_LIB=tools/_ab/librvz_ptime.so): per workgroup
 the shader clocks of the search phase (to its barrier), the trunk passes and the FC heads, the
-loop cycles, passes and rows; summarised over the workgroups of PLIES plies of the C2 workload.
+loop cycles, passes and rows, and the passes with fewer live boards than the tile's (partial_*)
+against the full ones; summarised over the workgroups of PLIES plies of the C2 workload.
+RVZ_PLAY_SINGLE_PASS=0 (the library's switch) runs those passes at the pair shape.
 GAMES (4096), SIMS (800), PLIES (20), NET (6x64), WARM (3); FORCED (1): the timed launch and the
 warm-up plies play forced searches whole (skip_forced_roots), 0: batch by batch."""
 import ctypes as C
@@ -41,7 +43,8 @@ if int(os.environ.get("STAGGER", 1)):      # bench.py's phase stagger (--stagger
 lib = rvz.load()
 lib.rvz_play_timing_read.argtypes = [C.c_void_p, C.c_int]
 n_wg = 16384
-buf = np.zeros((n_wg, 18), dtype=np.uint64)   # [n][12] phases, then [n][6] pass / heads parts
+NS = 14                                       # PLAY_T_SLOTS (csrc/rvz_play.hip.h)
+buf = np.zeros((n_wg, NS + 6), dtype=np.uint64)   # [n][NS] phases, then [n][6] pass / heads parts
 for _ in range(WARM):
     run.ply()
 torch.cuda.synchronize()
@@ -57,13 +60,16 @@ torch.cuda.synchronize()
 ms = t0.elapsed_time(t1)
 lib.rvz_play_timing_read(buf.ctypes.data, n_wg)
 flat = buf.reshape(-1)
-pt = flat[n_wg * 12:n_wg * 18].reshape(n_wg, 6).astype(np.float64)
-buf = flat[:n_wg * 12].reshape(n_wg, 12)
+pt = flat[n_wg * NS:n_wg * (NS + 6)].reshape(n_wg, 6).astype(np.float64)
+buf = flat[:n_wg * NS].reshape(n_wg, NS)
 used = buf[:, 3] > 0
 b = buf[used].astype(np.float64)
 end_us = (b[:, 10] - b[:, 10].max()) / 100.0   # s_memrealtime ticks (100 MHz) before the last end
 pt = pt[used]
 tot = b[:, 3]
+# passes with fewer live boards than the tile's (C2: one of the pair) and the full ones
+n_part, c_part = b[:, 12].sum(), b[:, 13].sum()
+n_full, c_full = b[:, 5].sum() - n_part, b[:, 1].sum() - c_part
 out = {"workgroups": int(used.sum()), "launch_ms": round(ms, 3), "plies": PLIES,
        "forced": FORCED, "rows": int(b[:, 6].sum()),
        "clock_GHz_est": round(float(np.median(tot)) / (ms * 1e6), 3),
@@ -74,6 +80,11 @@ out = {"workgroups": int(used.sum()), "launch_ms": round(ms, 3), "plies": PLIES,
        "passes_per_cycle": round(float(b[:, 5].sum() / b[:, 4].sum()), 3),
        "rows_per_pass": round(float(b[:, 6].sum() / b[:, 5].sum()), 4),
        "trunk_kcycles_per_pass": round(float(b[:, 1].sum() / b[:, 5].sum()) / 1e3, 2),
+       "single_pass": os.environ.get("RVZ_PLAY_SINGLE_PASS", "1") != "0",
+       "partial_pass_frac": round(float(n_part / b[:, 5].sum()), 4),
+       "partial_pass_cycle_frac_of_trunk": round(float(c_part / b[:, 1].sum()), 4),
+       "partial_pass_kcycles": round(float(c_part / max(n_part, 1.0)) / 1e3, 2),
+       "full_pass_kcycles": round(float(c_full / max(n_full, 1.0)) / 1e3, 2),
        "search_kcycles_per_cycle": round(float(b[:, 0].sum() / b[:, 4].sum()) / 1e3, 2),
        "heads_kcycles_per_cycle": round(float(b[:, 2].sum() / b[:, 4].sum()) / 1e3, 2),
        "pass_stem_kcycles": round(float(pt[:, 0].sum() / pt[:, 3].sum()) / 1e3, 2),
