@@ -6,7 +6,8 @@
 // one wave per game, as a pure function of (seed32, salt, tag, alpha, legal mask): a counter-based
 // generator, so no state is carried and the values do not depend on the launch geometry, the
 // schedule or which kernel asks.
-//  * Philox4x32-10 (Salmon et al., SC'11), key (seed32, salt), counter (attempt, square, tag, 0).
+//  * Philox4x32-10 (Salmon et al., SC'11; rvz_philox.hip.h, included by the translation unit
+//    before this file), key (seed32, salt), counter (attempt, square, tag, 0).
 //  * Gamma(alpha) per legal square by Marsaglia-Tsang rejection (ACM TOMS 26(3), 2000): the normal
 //    by Box-Muller from words 0 and 1 of the attempt's block, the acceptance uniform from word 2;
 //    every attempt is a new block (the attempt index is a counter word). alpha < 1 samples
@@ -22,22 +23,6 @@
 
 constexpr int32_t ERR_NOISE = 32;   // a Gamma rejection loop ran out of attempts (device error word)
 constexpr int NOISE_ATTEMPTS = 64;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1,
-                                               uint32_t c2, uint32_t c3) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return make_uint4(c0, c1, c2, c3);
-}
 
 // the top 23 bits of a word as a uniform of the open interval (0, 1)
 __device__ __forceinline__ float noise_u01(uint32_t w) {

@@ -40,6 +40,7 @@
 #include "../../include/rvz.h"
 #include "rvz_h2.hip.h"
 #include "rvz_host.hip.h"
+#include "rvz_philox.hip.h"
 #include "rvz_pow.hip.h"
 #include "rvz_rules.hip.h"
 #include "rvz_trace.h"

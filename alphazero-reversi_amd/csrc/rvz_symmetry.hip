@@ -16,32 +16,19 @@
 // three ballots, and the policy row moves through one cross-lane read, so nothing is recomputed
 // and no table lives in memory. Per image the wave stores the 3*S*S plane floats as float4 (48
 // lanes on 8x8, 27 on 6x6), the S*S+1 policy floats as dwords and one quirk word: 1028 B on 8x8
-// (1032 B with the quirk), 580 B (584 B) on 6x6, each byte written once.
+// (1032 B with the quirk), 580 B (584 B) on 6x6, each byte written once. The wave's part
+// (sym_src, write_image) is in rvz_symmetry.hip.h, shared with the replay buffer's k_replay_batch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/rvz.h"
 #include "rvz_host.hip.h"
 #include "rvz_rules.hip.h"
+#include "rvz_symmetry.hip.h"
 
 namespace {
 
 using namespace rvz;
-
-constexpr int SYM_THREADS = 256;                 // 4 waves, one input row each per step
-constexpr int SYM_WAVES = SYM_THREADS / 64;
-constexpr int SYM_MAX_BLOCKS = 2048;             // grid-stride beyond that
-
-// the source square of output square s under T_k (k in [0, 8))
-template <int BS>
-__device__ __forceinline__ int sym_src(int s, int k) {
-    const int i = s / BS, j0 = s % BS;
-    const int j = (k & 4) ? BS - 1 - j0 : j0;
-    const int r = k & 3;
-    const int si = r == 0 ? i : (r == 1 ? j : (r == 2 ? BS - 1 - i : BS - 1 - j));
-    const int sj = r == 0 ? j : (r == 1 ? BS - 1 - i : (r == 2 ? BS - 1 - j : i));
-    return si * BS + sj;
-}
 
 __device__ __forceinline__ uint64_t delta_swap(uint64_t x, uint64_t mask, int shift) {
     const uint64_t t = mask & (x ^ (x << shift));
@@ -89,42 +76,6 @@ __global__ __launch_bounds__(SYM_THREADS) void k_board_symmetry(
     }
 }
 
-// One image of one row, by the whole wave. P, O, V (mover, opponent, legal mask of the original),
-// pass and k are wave-uniform; pv is the lane's own policy entry (lane = square). k outside
-// [0, 8): an all-zero row and quirk -1.
-template <int BS>
-__device__ __forceinline__ void write_image(int lane, uint64_t P, uint64_t O, uint64_t V, float pv,
-                                            float pass, int k, size_t row,
-                                            float* __restrict__ out_states,
-                                            float* __restrict__ out_policy,
-                                            int32_t* __restrict__ out_quirk) {
-    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
-    const bool ok = k >= 0 && k < 8;
-    const bool sq = lane < NSQ;
-    const int src = sq ? sym_src<BS>(lane, k & 7) : lane;
-    const bool take = ok && sq;
-    const uint64_t TP = __ballot(take && ((P >> src) & 1ull));
-    const uint64_t TO = __ballot(take && ((O >> src) & 1ull));
-    const uint64_t TV = __ballot(take && ((V >> src) & 1ull));
-    const float moved = __shfl(pv, src, 64);
-
-    if (lane < 3 * NSQ / 4) {                    // NSQ % 4 == 0: a float4 stays within one plane
-        const int e = 4 * lane, plane = e / NSQ, s = e % NSQ;
-        const uint64_t B = plane == 0 ? TP : (plane == 1 ? TO : TV);
-        const uint32_t nib = (uint32_t)(B >> s) & 0xFu;
-        reinterpret_cast<float4*>(out_states + row * (3 * NSQ))[lane] =
-            make_float4((float)(nib & 1u), (float)((nib >> 1) & 1u), (float)((nib >> 2) & 1u),
-                        (float)(nib >> 3));
-    }
-    float* prow = out_policy + row * NPOL;
-    if (lane < NPOL) prow[lane] = ok ? (sq ? moved : pass) : 0.0f;
-    if (NPOL > 64 && lane == 0) prow[NSQ] = ok ? pass : 0.0f;
-    if (out_quirk) {             // wave-uniform; the image position's own mask, a direction per lane
-        const uint64_t own = legal_wave<BS>(TP, TO, lane);
-        if (lane == 0) out_quirk[row] = ok ? (int32_t)(own != TV) : -1;
-    }
-}
-
 template <int BS, int FAN>
 __global__ __launch_bounds__(SYM_THREADS) void k_training_rows(
     int n, const uint64_t* __restrict__ black, const uint64_t* __restrict__ white,
@@ -155,11 +106,6 @@ __global__ __launch_bounds__(SYM_THREADS) void k_training_rows(
     }
 }
 
-int blocks_for(int64_t units, int per_block) {
-    const int64_t need = (units + per_block - 1) / per_block;
-    return (int)(need < SYM_MAX_BLOCKS ? need : SYM_MAX_BLOCKS);
-}
-
 }  // namespace
 
 extern "C" int rvz_board_symmetry(int32_t bs, int32_t n, const uint64_t* black,
@@ -170,8 +116,8 @@ extern "C" int rvz_board_symmetry(int32_t bs, int32_t n, const uint64_t* black,
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
     return launch_bs(bs, k_board_symmetry<8>, k_board_symmetry<6>,
-                     dim3(blocks_for(n, SYM_THREADS)), dim3(SYM_THREADS), (hipStream_t)stream, n,
-                     black, white, sym, out_black, out_white);
+                     dim3(sym_blocks_for(n, SYM_THREADS)), dim3(SYM_THREADS),
+                     (hipStream_t)stream, n, black, white, sym, out_black, out_white);
 }
 
 extern "C" int rvz_training_rows(int32_t bs, int32_t n, const uint64_t* black,
@@ -185,7 +131,7 @@ extern "C" int rvz_training_rows(int32_t bs, int32_t n, const uint64_t* black,
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
     const auto launch = [&](auto k8, auto k6) {
-        return launch_bs(bs, k8, k6, dim3(blocks_for(n, SYM_WAVES)), dim3(SYM_THREADS),
+        return launch_bs(bs, k8, k6, dim3(sym_blocks_for(n, SYM_WAVES)), dim3(SYM_THREADS),
                          (hipStream_t)stream, n, black, white, status, policy, sym, out_states,
                          out_policy, out_quirk);
     };

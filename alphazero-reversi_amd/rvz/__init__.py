@@ -21,18 +21,22 @@ Batched core:
                             symmetry_compose / symmetry_inverse give the group table
     merge_positions         one training row per distinct position, the mean of the targets of
                             all its occurrences (rvz_merge_positions)
+    ReplayBuffer, replay_batch   a ring of compact training records on the device across
+                            iterations, and a minibatch drawn from it under random board
+                            symmetries in one launch (rvz_replay_batch)
 """
 from ._lib import RvzError, load  # noqa: F401
 from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa: F401
                      SOLVE_NOT_A_MOVE, Engine, action_probs, alphabeta, alphabeta_weights,
                      best_moves, board_apply, board_canonical, board_legal, board_symmetry,
-                     dirichlet_noise, merge_positions, policy_softmax, solve, solve_moves,
-                     solve_moves_wld, solve_window, solve_wld, symmetry_compose, symmetry_inverse,
-                     training_rows)
+                     dirichlet_noise, merge_positions, policy_softmax, replay_batch, solve,
+                     solve_moves, solve_moves_wld, solve_window, solve_wld, symmetry_compose,
+                     symmetry_inverse, training_rows)
 from .game import Board, ReversiGame  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)
+from .replay import ReplayBuffer  # noqa: F401
 from .selfplay import LaneRunner, SelfPlay, SelfPlayRunner  # noqa: F401
 
 __version__ = "0.1.0"

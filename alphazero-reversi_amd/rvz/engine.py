@@ -745,6 +745,68 @@ def merge_positions(black: torch.Tensor, white: torch.Tensor, status: torch.Tens
             "group": group}
 
 
+def replay_batch(mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
+                 value: torch.Tensor, start: int, live: int, nb: int, seed: int, step: int,
+                 random_sym: bool = True, idx: Optional[torch.Tensor] = None,
+                 sym: Optional[torch.Tensor] = None, board_size: int = 8):
+    """rvz_replay_batch: nb training rows drawn from a ring of compact records (include/rvz.h has
+    the draw). mover / opponent int64 [capacity] (bit patterns), policy float32 [capacity, S*S+1],
+    value float32 [capacity] or [capacity, 1], device tensors; the ring's `live` rows start at
+    slot `start`, oldest first, and wrap. seed and step are integers taken mod 2^64: row r's record
+    and symmetry are a pure function of (seed, step, r). idx [nb] integers: the logical rows to
+    take instead of the draw; sym [nb] integers: the symmetries instead of the draw
+    (random_sym=False: the identity). Returns (states float32 [nb, 3, S, S], policy float32
+    [nb, S*S+1], value float32 [nb, 1], slot int32 [nb], sym int32 [nb]); a row whose given idx is
+    outside [0, live) or whose given sym is outside [0, 8) is all zero with sym -1 (and slot -1
+    for the idx)."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    npol = board_size * board_size + 1
+    lib = _lib.load()
+    for name, x in (("start", start), ("live", live), ("nb", nb), ("seed", seed), ("step", step)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            raise RvzError(f"replay_batch: {name} is an int, not {x!r}")
+    cap = mover.numel()
+    if mover.dim() != 1 or opponent.shape != (cap,):
+        raise RvzError("replay_batch: mover and opponent hold one entry per slot")
+    if mover.dtype != torch.int64 or opponent.dtype != torch.int64:
+        raise RvzError("replay_batch: mover and opponent are int64 bit patterns")
+    if policy.shape != (cap, npol) or policy.dtype != torch.float32:
+        raise RvzError(f"replay_batch: policy must be float32 [capacity, {npol}]")
+    if value.shape not in ((cap,), (cap, 1)) or value.dtype != torch.float32:
+        raise RvzError("replay_batch: value must be float32 [capacity] or [capacity, 1]")
+    if cap < 1 or cap >= 2 ** 31:
+        raise RvzError("replay_batch: the ring holds between 1 and 2^31 - 1 slots")
+    if not 1 <= live <= cap or not 0 <= start < cap:
+        raise RvzError(f"replay_batch: live = {live} must be in [1, {cap}] and start = {start} "
+                       f"in [0, {cap})")
+    if nb < 0 or nb * npol >= 2 ** 31:
+        raise RvzError("replay_batch: nb must be >= 0 and nb * (S*S + 1) fit int32")
+    dev = mover.device
+    given = []
+    for name, x in (("idx", idx), ("sym", sym)):
+        if x is not None and (x.shape != (nb,) or x.dtype.is_floating_point or
+                              x.dtype == torch.bool):
+            raise RvzError(f"replay_batch: {name} holds one integer per output row")
+        given.append(None if x is None else x.to(dev, torch.int32).contiguous())
+    m, o = mover.contiguous(), opponent.to(dev).contiguous()
+    pol = policy.to(dev).contiguous()
+    val = value.to(dev).reshape(cap).contiguous()
+    states = torch.empty(nb, 3, board_size, board_size, dtype=torch.float32, device=dev)
+    out_p = torch.empty(nb, npol, dtype=torch.float32, device=dev)
+    out_v = torch.empty(nb, 1, dtype=torch.float32, device=dev)
+    slot = torch.empty(nb, dtype=torch.int32, device=dev)
+    out_k = torch.empty(nb, dtype=torch.int32, device=dev)
+    if nb:
+        check(lib.rvz_replay_batch(board_size, cap, ptr(m), ptr(o), ptr(pol), ptr(val), int(start),
+                                   int(live), int(nb), ptr(given[0]), ptr(given[1]),
+                                   int(bool(random_sym)), int(seed) & (2 ** 64 - 1),
+                                   int(step) & (2 ** 64 - 1), ptr(states), ptr(out_p), ptr(out_v),
+                                   ptr(slot), ptr(out_k), _lib.stream_handle(dev)),
+              None, "rvz_replay_batch")
+    return states, out_p, out_v, slot, out_k
+
+
 def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor, salt: int,
                     alpha: float, board_size: int = 8, bits: bool = False):
     """rvz_dirichlet_noise: the eta rows Engine.root_noise mixes into the roots' priors, by the

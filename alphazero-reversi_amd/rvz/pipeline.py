@@ -9,6 +9,8 @@ them (``_train_epoch``, :272-366), repeat. One process per GPU:
   global game g of iteration i is seeded ``seed + i * games * world + g`` (games sharded by rank,
   no collective);
 * records -> training arrays on the device (``records_to_training``; no host round trip);
+  with ``replay_iterations`` they are compact rows appended to a ``ReplayBuffer`` on the device,
+  and every training step samples its minibatch from the last iterations' rows;
 * training: ``DDPTrainer`` steps; DDP's bucketed gradient all-reduce over RCCL (backend "nccl"
   on ROCm) during backward is the only collective of the loop; then rank 0's BN statistics are
   broadcast and the evaluator re-reads the weights in place (``LeafEvaluator.refresh``), so the
@@ -26,6 +28,7 @@ import torch.distributed as dist
 
 from .engine import SOLVE_MAX_EMPTIES, Engine
 from .network import LeafEvaluator, leaf_evaluator
+from .replay import ReplayBuffer
 from .selfplay import SelfPlayRunner
 from .trainer import DDPTrainer, adjudicate, records_to_training
 
@@ -42,7 +45,9 @@ class SelfPlayTrainer:
                  exact_node_limit: int = 2 ** 24, exact_wld: bool = False,
                  adjudicate_empties: int = 0, adjudicate_node_limit: int = 2 ** 24,
                  exact_policy: int = 0, symmetries: Optional[str] = None,
-                 symmetry_seed: Optional[int] = None, merge_positions: bool = False):
+                 symmetry_seed: Optional[int] = None, merge_positions: bool = False,
+                 replay_iterations: int = 0, replay_capacity: Optional[int] = None,
+                 replay_steps: Optional[int] = None, replay_symmetries: bool = True):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -82,6 +87,19 @@ class SelfPlayTrainer:
         `symmetries`, in generate() and with adjudication on alike. train_epoch walks the merged
         rows unweighted, so every distinct position is seen once per pass. run_iteration reports
         merge_rows and merge_input_rows (0 when off).
+        replay_iterations: 0 (off: every iteration trains on its own games alone) or K: a replay
+        buffer on the device (rvz.ReplayBuffer) holds the rows of the last K iterations, this
+        rank's own, as compact records of 280 B on 8x8 (bitboards, policy, value; generate() then
+        returns "mover" and "opponent" in place of "states"), and every training step draws its
+        minibatch from all of them (DDPTrainer.train_replay seeded seed + iteration; the
+        rvz_replay_batch HIP kernel): a uniform row, under a fresh board symmetry at every draw
+        unless replay_symmetries is False. `symmetries` must then be None (ValueError otherwise);
+        exact targets, adjudication and merge_positions apply as before. replay_capacity: the
+        buffer's rows, default K x games x max_plies (no iteration yields more than games x
+        max_plies). replay_steps: the optimizer steps of an iteration, default ceil(the
+        iteration's new rows / train_batch), the steps of a pass over them; train_steps caps
+        either. run_iteration reports replay_rows (the rows held after the iteration's append)
+        and replay_iterations_held (0 when off).
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
@@ -102,6 +120,14 @@ class SelfPlayTrainer:
         self.symmetries = symmetries
         self.symmetry_seed = None if symmetry_seed is None else int(symmetry_seed)
         self.merge_positions = bool(merge_positions)
+        self.replay_iterations = int(replay_iterations)
+        if self.replay_iterations < 0:
+            raise ValueError("replay_iterations must be >= 0")
+        if self.replay_iterations and symmetries is not None:
+            raise ValueError("replay_iterations > 0 draws a symmetry with every sampled row "
+                             f"(replay_symmetries): symmetries must be None, not {symmetries!r}")
+        self.replay_steps = None if replay_steps is None else int(replay_steps)
+        self.replay_symmetries = bool(replay_symmetries)
         self.adjudicate_empties = int(adjudicate_empties)
         self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
@@ -138,6 +164,12 @@ class SelfPlayTrainer:
                                      seed_base=self.seed + self.rank * self.games,
                                      fused=self.fused, skip_last_eval=self.fused and memo)
         self.graph = bool(graph) and h2
+        self.buffer = None
+        if self.replay_iterations:
+            if replay_capacity is None:
+                replay_capacity = self.replay_iterations * self.games * self.max_plies
+            self.buffer = ReplayBuffer(int(replay_capacity), bs, self.device,
+                                       window_iterations=self.replay_iterations)
         self.iteration = 0
 
     def _seeds(self):
@@ -153,6 +185,9 @@ class SelfPlayTrainer:
 
     def _merge_args(self) -> dict:
         return {"merge_positions": True} if self.merge_positions else {}
+
+    def _compact_args(self) -> dict:
+        return {"compact": True} if self.replay_iterations else {}
 
     def generate(self) -> Dict[str, torch.Tensor]:
         """One iteration's self-play: every game of this rank from the start to its end.
@@ -178,7 +213,8 @@ class SelfPlayTrainer:
                                    exact_endgame=self.exact_endgame,
                                    exact_node_limit=self.exact_node_limit,
                                    exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                   **self._symmetry_args(), **self._merge_args())
+                                   **self._symmetry_args(), **self._merge_args(),
+                                   **self._compact_args())
 
     def _adjudicated(self, plies: int) -> Dict[str, torch.Tensor]:
         """generate()'s tail with adjudication on: the games stand after `plies` plies."""
@@ -199,15 +235,28 @@ class SelfPlayTrainer:
                                   eng.board_size, exact_endgame=self.exact_endgame,
                                   exact_node_limit=self.exact_node_limit,
                                   exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                  **self._symmetry_args(), **self._merge_args())
+                                  **self._symmetry_args(), **self._merge_args(),
+                                  **self._compact_args())
         out.update(stats)
         return out
 
     def train(self, data: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """_train_epoch over this iteration's data (each rank walks its own games; DDP averages
-        the gradients), then the evaluator picks up the new weights."""
-        out = self.trainer.train_epoch(data, seed=self.seed + self.iteration,
-                                       max_steps=self.train_steps, local_data=True)
+        the gradients), then the evaluator picks up the new weights. With a replay buffer the
+        iteration's rows are appended to it first and the steps draw from the whole window."""
+        if self.buffer is not None:
+            self.buffer.append(data["mover"], data["opponent"], data["policy_targets"],
+                               data["value_targets"], self.iteration)
+            steps = self.replay_steps
+            if steps is None:
+                steps = -(-data["mover"].shape[0] // self.trainer.batch_size)
+            if self.train_steps is not None:
+                steps = min(steps, self.train_steps)
+            out = self.trainer.train_replay(self.buffer, steps, seed=self.seed + self.iteration,
+                                            symmetries=self.replay_symmetries)
+        else:
+            out = self.trainer.train_epoch(data, seed=self.seed + self.iteration,
+                                           max_steps=self.train_steps, local_data=True)
         self.trainer.sync_buffers()
         self.trainer.scheduler_step()          # pipeline.py:131, once per iteration
         self.model.eval()
@@ -229,7 +278,7 @@ class SelfPlayTrainer:
         t2 = time.perf_counter()
         self.iteration += 1
         out.update({"selfplay_s": t1 - t0, "train_s": t2 - t1, "board_steps": plies,
-                    "samples": int(data["states"].shape[0]),
+                    "samples": int(data["policy_targets"].shape[0]),
                     "exact_rows": int(data.get("exact_rows", 0)),
                     "exact_unsolved": int(data.get("exact_unsolved", 0)),
                     "exact_policy_rows": int(data.get("exact_policy_rows", 0)),
@@ -240,5 +289,8 @@ class SelfPlayTrainer:
                     "symmetry_rows": int(data.get("symmetry_rows", 0)),
                     "symmetry_quirk_rows": int(data.get("symmetry_quirk_rows", 0)),
                     "merge_rows": int(data.get("merge_rows", 0)),
-                    "merge_input_rows": int(data.get("merge_input_rows", 0))})
+                    "merge_input_rows": int(data.get("merge_input_rows", 0)),
+                    "replay_rows": len(self.buffer) if self.buffer is not None else 0,
+                    "replay_iterations_held": (len(self.buffer.rows_by_iteration())
+                                               if self.buffer is not None else 0)})
         return out

@@ -34,7 +34,7 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
                         exact_wld: bool = False, exact_policy: int = 0,
                         moves_solver=None, symmetries: Optional[str] = None,
                         symmetry_seed: int = 0, augment=None, merge_positions: bool = False,
-                        merger=None) -> Dict[str, torch.Tensor]:
+                        merger=None, compact: bool = False) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -96,9 +96,21 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     number of rows is this option's one host synchronisation.
     merger(black, white, status, policy, value, board_size) -> dict with "m", "first", "count",
     "policy", "value": default rvz.merge_positions (the rvz_merge_positions HIP kernels).
+    compact = True (the default False is off: the keys and bytes of before): the rows a
+    rvz.ReplayBuffer holds. In place of "states" the result carries "mover" and "opponent", int64
+    [n]: each kept record's bitboards from the side of the player to move (mover = black where
+    the side is 1, else white, as rvz_board_canonical), from which rvz_replay_batch writes the
+    planes when a row is drawn; `canonical` is not called. policy_targets, value_targets and every
+    counter key are those of compact=False, after exact_endgame, exact_policy and merge_positions
+    alike (with merging, the bitboards are those of each group's first record). compact=True
+    together with `symmetries` raises ValueError: a compact row's symmetry is drawn every time it
+    is sampled.
     """
     if symmetries not in (None, "all", "random"):
         raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
+    if compact and symmetries is not None:
+        raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
+                         f"symmetries must be None, not {symmetries!r}")
     if canonical is None:
         canonical = board_canonical
     P, G = rec_idx.shape
@@ -109,14 +121,16 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
                       torch.zeros_like(side)], dim=1).to(torch.int32).contiguous()
     states = (canonical(black, white, st, board_size)
-              if symmetries is None and not merge_positions else None)
+              if symmetries is None and not merge_positions and not compact else None)
     policy = rec_p.permute(1, 0, 2).reshape(P * G, -1)[live].to(torch.float32)
     winner = final_status[:, 2].to(torch.int32).unsqueeze(0).expand(P, G).t().reshape(-1)[live]
     over = final_status[:, 1].unsqueeze(0).expand(P, G).t().reshape(-1)[live]
     v = torch.where(winner == side.to(torch.int32), 1.0, -1.0)
     v = torch.where(winner == 0, torch.zeros_like(v), v)
     v = torch.where(over != 0, v, -torch.ones_like(v))      # winner None -> -1 (self_play.py:121-126)
-    out = {"states": states, "policy_targets": policy, "value_targets": v.reshape(-1, 1).float()}
+    # compact: the two bitboards are filled in below, once merging has chosen the rows
+    out = {"mover": None, "opponent": None} if compact else {"states": states}
+    out.update({"policy_targets": policy, "value_targets": v.reshape(-1, 1).float()})
     if exact_endgame:
         if solver is None:
             def solver(b, w, s, bs, me):
@@ -148,13 +162,17 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
         m = int(merged["m"])
         first = merged["first"][:m].to(black.device, torch.int64)
         black, white, st = (t[first].contiguous() for t in (black, white, st))
-        if symmetries is None:
+        if symmetries is None and not compact:
             out["states"] = canonical(black, white, st, board_size)
         out["policy_targets"] = merged["policy"][:m]
         out["value_targets"] = merged["value"][:m].reshape(-1, 1)
         out["position_counts"] = merged["count"][:m]
         out["merge_rows"] = torch.tensor(m, dtype=torch.int64, device=black.device)
         out["merge_input_rows"] = torch.tensor(rows_in, dtype=torch.int64, device=black.device)
+    if compact:
+        mine = st[:, 0] == 1
+        out["mover"] = torch.where(mine, black, white)
+        out["opponent"] = torch.where(mine, white, black)
     if symmetries is not None:
         if augment is None:
             def augment(b, w, s, p, sym, bs, all_images):
@@ -323,6 +341,37 @@ class DDPTrainer:
             t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t)
             tot = t / ranks
+        return {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
+                "train/value_loss": float(tot[2]), "train/lr": self.opt.param_groups[0]["lr"],
+                "steps": steps}
+
+    def train_replay(self, buffer, steps: int, seed: int = 0, symmetries: bool = True
+                     ) -> Dict[str, float]:
+        """`steps` optimizer steps on minibatches drawn from a rvz.ReplayBuffer: step s trains
+        on buffer.sample(batch_size, seed * world + rank, s, symmetries), a uniform draw with
+        replacement over the rows held, each under a fresh board symmetry. The buffer is this
+        rank's own (its own self-play games), and the seed is spread over the ranks as
+        train_epoch(local_data=True) spreads it; each step's global batch is world x batch_size,
+        and every rank runs the same number of steps (the minimum over ranks). Returns
+        train_epoch's loss dict, averaged over ranks too."""
+        rank, world = self.rank_world()
+        steps = int(steps)
+        if self.distributed:          # every rank must run the same number of DDP steps
+            t = torch.tensor([steps], dtype=torch.int64,
+                             device=self.device if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            steps = int(t.item())
+        tot = torch.zeros(3, dtype=torch.float64, device=self.device)
+        for s in range(steps):
+            states, policy, value = buffer.sample(self.batch_size, seed * world + rank, s,
+                                                  symmetries)[:3]
+            losses = self.train_step(states, policy, value)
+            tot += torch.stack([x.double() for x in losses])
+        tot /= max(1, steps)
+        if self.distributed and world > 1:   # the job's loss: the mean over ranks
+            t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t)
+            tot = t / world
         return {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
                 "train/value_loss": float(tot[2]), "train/lr": self.opt.param_groups[0]["lr"],
                 "steps": steps}

@@ -522,6 +522,55 @@ int rvz_merge_positions(int32_t board_size, int32_t n, const uint64_t *black,
                         float *out_policy /* [n][S*S+1] */, float *out_value /* [n] */,
                         int32_t *out_group /* [n] */, void *hip_stream);
 
+/* ---- replay buffer: a minibatch drawn from a ring of compact records ----------------------
+ * A sliding window over the last iterations' records, held compactly: a record is its mover
+ * bitboard, its opponent bitboard (P = side == 1 ? black : white, as rvz_board_canonical), its
+ * policy row and its value, 16 + 4 * (S*S + 1) + 4 bytes (280 B on 8x8, 168 B on 6x6) against the
+ * 1028 B (580 B) of its expanded planes and policy. rvz_replay_batch (csrc/rvz_replay.hip) draws
+ * nb training rows from such a ring in one launch: a uniform record, a random board symmetry,
+ * and the row rvz_training_rows writes for that record under that symmetry. Stateless, on caller
+ * arrays (device pointers), asynchronous on hip_stream and graph-capturable: no allocation, no
+ * copy, no synchronisation, no table in memory, no host randomness.
+ * The ring: mover / opponent uint64 [capacity], policy float32 [capacity][S*S+1], value float32
+ * [capacity]. It holds `live` rows (1 <= live <= capacity); logical row i, oldest first, sits in
+ * slot (start + i) % capacity. Slots outside the live rows are never read.
+ * Output row r, one wavefront per row, lane = output square:
+ *   x = Philox4x32-10(key (seed & 0xffffffff, seed >> 32),
+ *                     counter (r, step & 0xffffffff, step >> 32, 0))      (Salmon et al., SC'11)
+ *   i = idx[r] if idx is given, else (uint32) (((uint64) x.0 * (uint32) live) >> 32): the
+ *       multiply-high draw. Every i gets floor(2^32 / live) or one more of the 2^32 words, so its
+ *       probability is within 2^-32 of 1 / live: a relative bias of at most live / 2^32.
+ *   k = sym[r] if sym is given, else x.1 & 7 if random_sym != 0, else 0.
+ * With P, O, the policy row and v read from slot (start + i) % capacity, the row is exactly what
+ * rvz_training_rows (fan 1) writes for that record (black = P, white = O, side 1) under T_k:
+ * out_states float32 [nb][3][S][S], 16-byte aligned, the images of the three planes of the
+ * original position, the third being the image of the original's legal mask; out_policy float32
+ * [nb][S*S+1] the permuted policy row, values moved and never recomputed; out_value float32 [nb]
+ * = v bit for bit; out_slot int32 [nb] the slot read and out_sym int32 [nb] = k, so that a caller
+ * can see which record and which image a drawn row is. There is no quirk output.
+ * A given idx[r] outside [0, live) (checked in the kernel, no host synchronisation): that row's
+ * states and policy are all zero, out_value[r] = 0, out_slot[r] = -1 and out_sym[r] = -1. A given
+ * sym[r] outside [0, 8): the same zero row with out_value[r] = 0 and out_sym[r] = -1; out_slot[r]
+ * still reports the slot.
+ * Every output element of all nb rows is written by exactly one lane (no pre-fill needed). A
+ * row's outputs depend on (the ring's contents, start, live, capacity, seed, step, r, idx[r],
+ * sym[r]) alone, not on nb or the launch geometry. Offsets into the ring are 64-bit, so
+ * capacity * (S*S + 1) may pass 2^31. The outputs must not overlap the ring or each other.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, capacity < 1, live outside
+ * [1, capacity], start outside [0, capacity), nb < 0, nb * (S*S + 1) not fitting in int32, and
+ * with nb > 0 a null mover / opponent / policy / value / out_states / out_policy / out_value /
+ * out_slot / out_sym or an out_states that is not 16-byte aligned. nb = 0 returns RVZ_OK without
+ * a launch. */
+int rvz_replay_batch(int32_t board_size, int32_t capacity, const uint64_t *mover,
+                     const uint64_t *opponent /* [capacity] */,
+                     const float *policy /* [capacity][S*S+1] */,
+                     const float *value /* [capacity] */, int32_t start, int32_t live, int32_t nb,
+                     const int32_t *idx /* [nb], nullable */,
+                     const int32_t *sym /* [nb], nullable */, int32_t random_sym, uint64_t seed,
+                     uint64_t step, float *out_states /* [nb][3][S][S], 16-byte aligned */,
+                     float *out_policy /* [nb][S*S+1] */, float *out_value /* [nb] */,
+                     int32_t *out_slot /* [nb] */, int32_t *out_sym /* [nb] */, void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
