@@ -24,6 +24,9 @@ Batched core:
     ReplayBuffer, replay_batch   a ring of compact training records on the device across
                             iterations, and a minibatch drawn from it under random board
                             symmetries in one launch (rvz_replay_batch)
+    policy_value_loss, full_policy_loss   the loss on the full policy target, weighted per row,
+                            with its gradients in one deterministic float64 call
+                            (rvz_policy_value_loss), and its differentiable torch form
 """
 from ._lib import RvzError, load  # noqa: F401
 from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa: F401
@@ -33,6 +36,7 @@ from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa
                      solve_moves, solve_moves_wld, solve_window, solve_wld, symmetry_compose,
                      symmetry_inverse, training_rows)
 from .game import Board, ReversiGame  # noqa: F401
+from .loss import full_policy_loss, policy_value_loss  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)

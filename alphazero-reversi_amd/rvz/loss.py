@@ -1,0 +1,162 @@
+"""The policy/value loss on the full policy target: AlphaZero's own -pi . log p + (y - t)^2.
+
+``merge_positions`` gives the mean search policy of every record of a position and the number of
+records behind it, ``exact_policy`` the uniform distribution over the proven-optimal moves, MCTS
+a visit distribution: ``policy_value_loss`` (rvz_policy_value_loss, include/rvz.h has the
+definition) trains on the whole distribution, weighted per row, where the reference's criterion
+keeps only its argmax. One deterministic HIP call computes the loss, its statistics and both
+gradients in float64; ``full_policy_loss`` makes it a differentiable torch function, which
+``DDPTrainer(policy_target="full")`` uses.
+"""
+from __future__ import annotations
+
+import math
+import numbers
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib
+from ._lib import RvzError, check, ptr
+
+OUT_LOSS = ("loss", "policy_loss", "value_loss", "target_entropy", "weight_sum", "agreement",
+            "malformed")        # out_loss[0 .. 7); out_loss[7] is 0
+
+
+def _addr(t: Optional[torch.Tensor]):
+    """Device address of a contiguous device tensor (the loss kernels read and write single
+    dwords, so only the scratch needs ptr()'s 16-byte alignment)."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RvzError("rvz buffers must be device tensors (no host fallback)")
+    return t.data_ptr()
+
+
+def check_loss_args(logits, value, policy_targets, value_targets, weights, policy_weight,
+                    value_weight, board_size) -> int:
+    """The shape, dtype and weight rules of policy_value_loss, checked before any device call;
+    returns n."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    npol = board_size * board_size + 1
+    for name, t in (("logits", logits), ("value", value), ("policy_targets", policy_targets),
+                    ("value_targets", value_targets)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise RvzError(f"policy_value_loss: {name} must be a float32 tensor")
+    if logits.dim() != 2 or logits.shape[1] != npol:
+        raise RvzError(f"policy_value_loss: logits must be [n, {npol}]")
+    n = logits.shape[0]
+    if policy_targets.shape != (n, npol):
+        raise RvzError(f"policy_value_loss: policy_targets must be [n, {npol}]")
+    for name, t in (("value", value), ("value_targets", value_targets)):
+        if t.shape not in ((n,), (n, 1)):
+            raise RvzError(f"policy_value_loss: {name} must be [n] or [n, 1]")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or
+                                weights.dtype != torch.float32 or weights.shape != (n,)):
+        raise RvzError("policy_value_loss: weights must be None or float32 [n]")
+    if n * npol >= 2 ** 31:
+        raise RvzError("policy_value_loss: n * (S*S + 1) does not fit int32")
+    for name, x in (("policy_weight", policy_weight), ("value_weight", value_weight)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Real) or \
+                not 0.0 <= float(x) < math.inf:
+            raise RvzError(f"policy_value_loss: {name} must be a finite number >= 0, not {x!r}")
+    return n
+
+
+def policy_value_loss(logits: torch.Tensor, value: torch.Tensor, policy_targets: torch.Tensor,
+                      value_targets: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                      policy_weight: float = 1.0, value_weight: float = 1.0, board_size: int = 8,
+                      rows: bool = False, grads: bool = True) -> Dict[str, torch.Tensor]:
+    """rvz_policy_value_loss: the weighted loss of a batch on its full policy targets, with its
+    gradients, in float64 (include/rvz.h has the definition). logits and policy_targets float32
+    [n, S*S+1], value (the net's tanh output) and value_targets float32 [n] or [n, 1], weights
+    None (every row 1) or float32 [n], device tensors. Returns a dict of device tensors: "out_loss"
+    float64 [8] and 0-d views of its entries "loss" (policy_weight * P + value_weight * V),
+    "policy_loss" P, "value_loss" V, "target_entropy", "weight_sum" W, "agreement" and
+    "malformed" (the rows dropped with weight 0: a non-finite logit or value, a target out of
+    range, a negative or non-finite weight); with rows=True "rows" float64 [n, 3], each row's
+    {Lp, Lv, H}; with grads=True "grad_logits" float32 [n, S*S+1] and "grad_value" float32 in
+    value's shape, the derivatives of "loss". The call runs on the current stream, allocates its
+    scratch and outputs, and never synchronises with the host; n = 0 launches nothing and
+    returns zeros."""
+    n = check_loss_args(logits, value, policy_targets, value_targets, weights, policy_weight,
+                        value_weight, board_size)
+    lib = _lib.load()
+    dev = logits.device
+    z = logits.detach().contiguous()
+    y = value.detach().reshape(n).contiguous()
+    pi = policy_targets.detach().to(dev).contiguous()
+    t = value_targets.detach().to(dev).reshape(n).contiguous()
+    w = None if weights is None else weights.detach().to(dev).contiguous()
+    f64 = {"dtype": torch.float64, "device": dev}
+    out_loss = torch.empty(8, **f64) if n else torch.zeros(8, **f64)
+    out = {"out_loss": out_loss}
+    out.update({name: out_loss[i] for i, name in enumerate(OUT_LOSS)})
+    if rows:
+        out["rows"] = torch.empty(n, 3, **f64)
+    if grads:
+        out["grad_logits"] = torch.empty(n, logits.shape[1], dtype=torch.float32, device=dev)
+        out["grad_value"] = torch.empty(value.shape, dtype=torch.float32, device=dev)
+    if n:
+        size = lib.rvz_loss_scratch_size(board_size, n)
+        if size < 0:
+            raise RvzError(f"policy_value_loss: no scratch for n = {n}")
+        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
+        check(lib.rvz_policy_value_loss(board_size, n, _addr(z), _addr(y), _addr(pi), _addr(t),
+                                        _addr(w), float(policy_weight), float(value_weight),
+                                        ptr(scratch), _addr(out_loss), _addr(out.get("rows")),
+                                        _addr(out.get("grad_logits")), _addr(out.get("grad_value")),
+                                        _lib.stream_handle(dev)), None, "rvz_policy_value_loss")
+    return out
+
+
+class _Loss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, value, kernel, args):
+        out = kernel(logits.detach(), value.detach(), *args, rows=False, grads=True)
+        ctx.save_for_backward(out["grad_logits"], out["grad_value"])
+        ctx.shapes = (logits.shape, value.shape)
+        return out["loss"].to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gl, gv = ctx.saved_tensors
+        g = grad_output.to(gl.dtype)
+        return (g * gl).reshape(ctx.shapes[0]), (g * gv).reshape(ctx.shapes[1]), None, None
+
+
+def differentiable(kernel):
+    """A function of full_policy_loss's signature around any `kernel` of policy_value_loss's
+    signature and results (tests on a host without a GPU wrap the NumPy reference)."""
+    def loss_fn(logits, value, policy_targets, value_targets, weights=None, policy_weight=1.0,
+                value_weight=1.0, board_size=8):
+        holder = {}
+
+        def call(*a, **k):
+            holder["out"] = kernel(*a, **k)
+            return holder["out"]
+        loss = _Loss.apply(logits, value, call,
+                           (policy_targets, value_targets, weights, policy_weight, value_weight,
+                            board_size))
+        out = holder["out"]
+        stats = {k: out[k] for k in ("target_entropy", "agreement", "weight_sum", "malformed")}
+        return loss, out["policy_loss"], out["value_loss"], stats
+    return loss_fn
+
+
+_full = differentiable(policy_value_loss)
+
+
+def full_policy_loss(logits: torch.Tensor, value: torch.Tensor, policy_targets: torch.Tensor,
+                     value_targets: torch.Tensor, weights: Optional[torch.Tensor] = None,
+                     policy_weight: float = 1.0, value_weight: float = 1.0, board_size: int = 8):
+    """policy_value_loss as a differentiable torch function (one rvz_policy_value_loss call in
+    the forward, which also computes the gradients; the backward multiplies the saved gradients
+    by the upstream factor). Returns (loss, policy_loss, value_loss, stats): loss a 0-d tensor of
+    logits' dtype, differentiable with respect to logits and value; policy_loss and value_loss
+    the weighted means P and V, 0-d float64; stats the 0-d float64 device tensors
+    "target_entropy", "agreement", "weight_sum" and "malformed". Nothing synchronises with the
+    host."""
+    return _full(logits, value, policy_targets, value_targets, weights, policy_weight,
+                 value_weight, board_size)

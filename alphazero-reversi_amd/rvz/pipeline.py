@@ -47,7 +47,8 @@ class SelfPlayTrainer:
                  exact_policy: int = 0, symmetries: Optional[str] = None,
                  symmetry_seed: Optional[int] = None, merge_positions: bool = False,
                  replay_iterations: int = 0, replay_capacity: Optional[int] = None,
-                 replay_steps: Optional[int] = None, replay_symmetries: bool = True):
+                 replay_steps: Optional[int] = None, replay_symmetries: bool = True,
+                 policy_target: str = "argmax", count_weights: bool = False):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -85,7 +86,8 @@ class SelfPlayTrainer:
         search policy and the mean outcome of all its occurrences and, under "position_counts",
         their number: the start position is one row, not one per game. It runs before
         `symmetries`, in generate() and with adjudication on alike. train_epoch walks the merged
-        rows unweighted, so every distinct position is seen once per pass. run_iteration reports
+        rows unweighted, so every distinct position is seen once per pass (count_weights weights
+        them by their counts). run_iteration reports
         merge_rows and merge_input_rows (0 when off).
         replay_iterations: 0 (off: every iteration trains on its own games alone) or K: a replay
         buffer on the device (rvz.ReplayBuffer) holds the rows of the last K iterations, this
@@ -100,10 +102,30 @@ class SelfPlayTrainer:
         iteration's new rows / train_batch), the steps of a pass over them; train_steps caps
         either. run_iteration reports replay_rows (the rows held after the iteration's append)
         and replay_iterations_held (0 when off).
+        policy_target: "argmax" (the default: the reference's criterion) or "full": the trainer's
+        loss is AlphaZero's own -pi . log p on the whole policy target (DDPTrainer;
+        rvz.full_policy_loss, the rvz_policy_value_loss HIP kernels), so a merged row's mean
+        search policy and every proven-optimal move of an exact_policy row are trained on, not
+        their argmax alone; train() then also reports train/policy_kl and
+        train/policy_agreement. count_weights: True weights each merged row by its
+        position_counts, the records it stands for; it needs policy_target="full",
+        merge_positions=True and no replay buffer (the ring stores no counts), ValueError
+        otherwise.
         table_slots: slots of the fused launch's cross-game NN-output table (0: no table;
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
         on 6x6): 2^20 slots = 608 MB, 2^12 = 2.4 MB."""
+        if policy_target not in ("argmax", "full"):
+            raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
+        if count_weights and policy_target != "full":
+            raise ValueError("count_weights=True weights the rows of the full policy loss: "
+                             "policy_target must be 'full'")
+        if count_weights and not merge_positions:
+            raise ValueError("count_weights=True needs merge_positions=True (the counts are "
+                             "the merged rows' position_counts)")
+        if count_weights and replay_iterations:
+            raise ValueError("count_weights=True needs replay_iterations=0: the replay ring "
+                             "stores no position counts")
         self.model = model.eval()
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -133,7 +155,9 @@ class SelfPlayTrainer:
         self.train_steps = train_steps
         self.trainer = DDPTrainer(model, lr=lr, weight_decay=weight_decay,
                                   gradient_clip=gradient_clip, batch_size=train_batch,
-                                  lr_milestones=lr_milestones, lr_gamma=lr_gamma)
+                                  lr_milestones=lr_milestones, lr_gamma=lr_gamma,
+                                  policy_target=policy_target,
+                                  count_weights=bool(count_weights))
         # the h2 kernels when they cover the net, else the module itself on the GPU
         # (ModuleEvaluator: pull-style, eager plies; it reads the live module, so refresh() only
         # drops the memo)

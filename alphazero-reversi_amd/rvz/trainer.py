@@ -11,7 +11,9 @@ optimizer step. Differences by design:
 * every rank trains on its own shard of the global sample order, drawn from one seeded
   permutation, so the global batch of a step is world_size x batch_size;
 * the training arrays come straight from the engine's device-side records
-  (``records_to_training``): no host round trip, no per-state Python lists.
+  (``records_to_training``): no host round trip, no per-state Python lists;
+* ``policy_target="full"`` (off by default) trains on the whole policy target, weighted per row,
+  instead of its argmax (``rvz.full_policy_loss``; the rvz_policy_value_loss HIP kernels).
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch.nn.functional as F
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
                      solve_moves, solve_moves_wld, solve_wld, training_rows)
 from .engine import merge_positions as _merge_positions
+from .loss import full_policy_loss
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
@@ -57,8 +60,8 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     exact_policy = N > 0 (independent of exact_endgame): every kept record with at most N empty
     squares whose every move the per-move solver decides (rvz.best_moves' `complete`) gets the
     policy target mask / mask.sum(), float32: uniform over the proven-optimal moves (the pass
-    index for a root that can only pass), so its argmax, which DDPTrainer trains on, is the
-    lowest-index optimal move. Rows above N, and rows with an abandoned move, keep their MCTS
+    index for a root that can only pass), so its argmax, which DDPTrainer trains on by default, is
+    the lowest-index optimal move (DDPTrainer(policy_target="full") trains on the whole row). Rows above N, and rows with an abandoned move, keep their MCTS
     target bit for bit; states and value targets are untouched. Two more keys then, 0-d int64
     (no host synchronisation): "exact_policy_rows", the rows replaced, and
     "exact_policy_unsolved", the rows within N with an abandoned move. N = 0 (the default) is
@@ -241,10 +244,31 @@ class DDPTrainer:
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 1e-4,
                  gradient_clip: float = 1.0, policy_loss_weight: float = 1.0,
                  value_loss_weight: float = 1.0, batch_size: int = 64, bucket_cap_mb: int = 25,
-                 lr_milestones=(), lr_gamma: float = 0.1):
+                 lr_milestones=(), lr_gamma: float = 0.1, policy_target: str = "argmax",
+                 count_weights: bool = False, loss_fn=None):
         """Defaults = the reference's TrainingConfig (config.py:46-60): AdamW(lr 1e-3, weight decay
         1e-4), clip 1.0, loss weights 1, batch 64, MultiStepLR(milestones [], gamma 0.1)
-        (pipeline.py:91-105), stepped once per iteration (scheduler_step, pipeline.py:131)."""
+        (pipeline.py:91-105), stepped once per iteration (scheduler_step, pipeline.py:131).
+        policy_target: "argmax" (the default: the reference's criterion, cross-entropy against
+        the argmax of the policy target) or "full": AlphaZero's own loss -pi . log p on the whole
+        target distribution plus the squared value error, a weighted mean over the batch's rows
+        (rvz.full_policy_loss; the rvz_policy_value_loss HIP kernels, float64, deterministic).
+        The loss dict then gains "train/policy_kl" (the policy loss minus the mean target
+        entropy: the divergence of the net's policy from the target) and
+        "train/policy_agreement" (the weighted share of rows whose argmax the net matches).
+        count_weights (needs "full"): train_epoch weights every row by data["position_counts"],
+        the records a merged row stands for (records_to_training(merge_positions=True)).
+        loss_fn(logits, value, policy_targets, value_targets, weights, policy_weight,
+        value_weight, board_size) -> (loss, policy_loss, value_loss, stats): default
+        rvz.full_policy_loss (tests on a host without a GPU pass the NumPy reference)."""
+        if policy_target not in ("argmax", "full"):
+            raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
+        if count_weights and policy_target != "full":
+            raise ValueError("count_weights=True weights the rows of the full policy loss: "
+                             "policy_target must be 'full'")
+        self.policy_target, self.count_weights = policy_target, bool(count_weights)
+        self.loss_fn = full_policy_loss if loss_fn is None else loss_fn
+        self.last_stats = None      # "full": the stats of the last train_step (0-d tensors)
         self.model = model
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -279,20 +303,49 @@ class DDPTrainer:
     def rank_world(self):
         return (dist.get_rank(), dist.get_world_size()) if self.distributed else (0, 1)
 
-    def train_step(self, states, policy_targets, value_targets):
-        """One optimizer step (pipeline.py:297-340); returns (loss, policy_loss, value_loss)."""
+    def train_step(self, states, policy_targets, value_targets, weights=None):
+        """One optimizer step (pipeline.py:297-340); returns (loss, policy_loss, value_loss).
+        weights (policy_target="full" only): float32 [n], each row's weight in the batch's mean;
+        None weights every row 1. In "full" mode last_stats holds the step's loss_fn stats."""
+        if weights is not None and self.policy_target != "full":
+            raise ValueError("train_step: weights need policy_target='full'")
         self.net.train()
         self.opt.zero_grad()
         logits, value = self.net(states)
-        policy_loss = F.cross_entropy(logits.view(-1, logits.size(-1)),
-                                      policy_targets.argmax(dim=1))
-        value_loss = F.mse_loss(value.squeeze(-1), value_targets.reshape(-1))
-        loss = self.wp * policy_loss + self.wv * value_loss
+        if self.policy_target == "full":
+            board = int(getattr(self.model, "board_size", 8))
+            loss, policy_loss, value_loss, self.last_stats = self.loss_fn(
+                logits.view(-1, logits.size(-1)), value.squeeze(-1), policy_targets,
+                value_targets.reshape(-1), weights, self.wp, self.wv, board)
+        else:
+            policy_loss = F.cross_entropy(logits.view(-1, logits.size(-1)),
+                                          policy_targets.argmax(dim=1))
+            value_loss = F.mse_loss(value.squeeze(-1), value_targets.reshape(-1))
+            loss = self.wp * policy_loss + self.wv * value_loss
         loss.backward()                      # DDP: bucketed RCCL all-reduce during backward
         if self.clip > 0:
             torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
         self.opt.step()
         return loss.detach(), policy_loss.detach(), value_loss.detach()
+
+    def _step_totals(self, losses):
+        """The per-step summands of the loss dict: the three losses, and in "full" mode the
+        policy KL and the agreement."""
+        vals = [x.double() for x in losses]
+        if self.policy_target == "full":
+            st = self.last_stats
+            vals += [losses[1].double() - st["target_entropy"].double(),
+                     st["agreement"].double()]
+        return torch.stack(vals)
+
+    def _loss_dict(self, tot, steps):
+        out = {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
+               "train/value_loss": float(tot[2]), "train/lr": self.opt.param_groups[0]["lr"],
+               "steps": steps}
+        if self.policy_target == "full":
+            out["train/policy_kl"] = float(tot[3])
+            out["train/policy_agreement"] = float(tot[4])
+        return out
 
     def train_epoch(self, data: Dict[str, torch.Tensor], seed: int = 0,
                     max_steps: Optional[int] = None, local_data: bool = False
@@ -306,7 +359,12 @@ class DDPTrainer:
         Order: the permutation the reference's DataLoader(shuffle=True) draws when handed a
         generator seeded with `seed` (its base-seed draw, then randperm(n)). On one
         process the last partial batch is trained too, as the reference's DataLoader (no
-        drop_last) does; across ranks every step is a full world x batch_size batch."""
+        drop_last) does; across ranks every step is a full world x batch_size batch.
+        With count_weights every row is weighted by data["position_counts"] (ValueError when the
+        key is missing)."""
+        if self.count_weights and "position_counts" not in data:
+            raise ValueError("train_epoch: count_weights=True needs data['position_counts'] "
+                             "(records_to_training(merge_positions=True))")
         rank, world = self.rank_world()
         ranks = world
         n = data["states"].shape[0]
@@ -329,21 +387,25 @@ class DDPTrainer:
                              device=self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             steps = int(t.item())
-        tot = torch.zeros(3, dtype=torch.float64, device=self.device)
+        tot = torch.zeros(5 if self.policy_target == "full" else 3, dtype=torch.float64,
+                          device=self.device)
         for s in range(steps):
             idx = order[s * per_step + rank * self.batch_size:
                         s * per_step + (rank + 1) * self.batch_size].to(self.device)
-            losses = self.train_step(data["states"][idx], data["policy_targets"][idx],
-                                     data["value_targets"][idx])
-            tot += torch.stack([x.double() for x in losses])
+            if self.count_weights:
+                losses = self.train_step(data["states"][idx], data["policy_targets"][idx],
+                                         data["value_targets"][idx],
+                                         data["position_counts"][idx].to(torch.float32))
+            else:
+                losses = self.train_step(data["states"][idx], data["policy_targets"][idx],
+                                         data["value_targets"][idx])
+            tot += self._step_totals(losses)
         tot /= max(1, steps)
         if self.distributed and ranks > 1:   # the job's loss: the mean over ranks
             t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t)
             tot = t / ranks
-        return {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
-                "train/value_loss": float(tot[2]), "train/lr": self.opt.param_groups[0]["lr"],
-                "steps": steps}
+        return self._loss_dict(tot, steps)
 
     def train_replay(self, buffer, steps: int, seed: int = 0, symmetries: bool = True
                      ) -> Dict[str, float]:
@@ -353,7 +415,8 @@ class DDPTrainer:
         rank's own (its own self-play games), and the seed is spread over the ranks as
         train_epoch(local_data=True) spreads it; each step's global batch is world x batch_size,
         and every rank runs the same number of steps (the minimum over ranks). Returns
-        train_epoch's loss dict, averaged over ranks too."""
+        train_epoch's loss dict, averaged over ranks too. The ring stores no record counts, so
+        in "full" mode every drawn row weighs 1."""
         rank, world = self.rank_world()
         steps = int(steps)
         if self.distributed:          # every rank must run the same number of DDP steps
@@ -361,17 +424,16 @@ class DDPTrainer:
                              device=self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             steps = int(t.item())
-        tot = torch.zeros(3, dtype=torch.float64, device=self.device)
+        tot = torch.zeros(5 if self.policy_target == "full" else 3, dtype=torch.float64,
+                          device=self.device)
         for s in range(steps):
             states, policy, value = buffer.sample(self.batch_size, seed * world + rank, s,
                                                   symmetries)[:3]
             losses = self.train_step(states, policy, value)
-            tot += torch.stack([x.double() for x in losses])
+            tot += self._step_totals(losses)
         tot /= max(1, steps)
         if self.distributed and world > 1:   # the job's loss: the mean over ranks
             t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t)
             tot = t / world
-        return {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
-                "train/value_loss": float(tot[2]), "train/lr": self.opt.param_groups[0]["lr"],
-                "steps": steps}
+        return self._loss_dict(tot, steps)

@@ -571,6 +571,60 @@ int rvz_replay_batch(int32_t board_size, int32_t capacity, const uint64_t *mover
                      float *out_policy /* [nb][S*S+1] */, float *out_value /* [nb] */,
                      int32_t *out_slot /* [nb] */, int32_t *out_sym /* [nb] */, void *hip_stream);
 
+/* ---- policy/value loss on the full policy target -------------------------------------------
+ * AlphaZero's own loss, -pi . log p + (y - t)^2, on the whole target distribution (a merged
+ * position's mean search policy, the uniform distribution over the proven-optimal moves, a visit
+ * distribution) and weighted per row, forward and backward in one call. rvz_policy_value_loss
+ * (csrc/rvz_loss.hip) is stateless, on caller arrays (device pointers), asynchronous on
+ * hip_stream and graph-capturable: no allocation, no copy, no memset, no synchronisation; the
+ * scratch needs no preparation.
+ * All arithmetic is float64 (IEEE, no contraction) on the float32 inputs. With z = logits,
+ * pi = policy_target, y = value (the net's tanh output), t = value_target, A = S*S + 1, per row r:
+ *   m = max_a z[a]                     lse = m + log sum_a exp(z[a] - m)
+ *   logp[a] = z[a] - lse               p[a] = exp(logp[a])
+ *   S  = sum_a pi[a]
+ *   Lp = -sum_{a: pi[a] > 0} pi[a] * logp[a]
+ *   H  = -sum_{a: pi[a] > 0} pi[a] * log pi[a]
+ *   Lv = (y - t)^2
+ *   agree = 1 if the first maximum of z and the first maximum of pi are the same index, else 0
+ *   w = weight[r], or 1 with a null weight
+ * A row is malformed if a logit or y is not finite, a pi entry is outside [0, 1], t is outside
+ * [-1, 1], or its weight is negative or not finite (NaN fails each test): it gets w = 0, a zero
+ * out_row, zero gradients, and is counted. Rows are checked in the kernel, no host
+ * synchronisation.
+ *   W = sum_r w        P = sum_r w Lp / W        V = sum_r w Lv / W
+ *   out_loss = { policy_weight * P + value_weight * V, P, V, sum_r w H / W, W,
+ *                sum_r w agree / W, malformed rows, 0 }
+ *   out_row[r] = { Lp, Lv, H }
+ *   grad_logits[r][a] = (float) ((policy_weight * w / W) * (S * p[a] - pi[a]))
+ *   grad_value[r]     = (float) ((value_weight * w / W) * 2 * (y - t))
+ * the derivatives of out_loss[0] with respect to z and y. With W == 0 every mean and every
+ * gradient is 0; no NaN is written anywhere.
+ * Sums: a row's sums over a are a fixed float64 butterfly over the wavefront that holds the row
+ * (lane = a; on 8x8 lane 0 also carries the pass entry), so out_row[r] depends on row r alone,
+ * not on n, r or the neighbours. The cross-row sums are float64 in a fixed tree whose shape
+ * depends on n alone: 4096 consecutive rows per node (a thread adds items t, t + 1024, t + 2048,
+ * t + 3072, the 64 lanes of a wave by the butterfly, the 16 waves in order), level on level to one
+ * node. No floating-point atomics: the same inputs give the same bytes on every call. Every
+ * output element is written exactly once; out_row, and the two gradients together, may be null
+ * and are then not computed.
+ * rvz_loss_scratch_size: the scratch's bytes (64 + 64 per row + the tree's upper levels),
+ * non-decreasing in n; negative for bad arguments.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, n * A >= 2^31, a loss weight
+ * that is negative or not finite, and with n > 0 a null logits / value / policy_target /
+ * value_target / scratch / out_loss, exactly one of the two gradients, or a scratch that is not
+ * 16-byte aligned. n = 0 returns RVZ_OK without a launch, and then nothing is written. */
+int64_t rvz_loss_scratch_size(int32_t board_size, int32_t n);
+int rvz_policy_value_loss(int32_t board_size, int32_t n, const float *logits /* [n][A] */,
+                          const float *value /* [n] */, const float *policy_target /* [n][A] */,
+                          const float *value_target /* [n] */,
+                          const float *weight /* [n], nullable: every row 1 */,
+                          double policy_weight, double value_weight,
+                          void *scratch /* 16-byte aligned */, double *out_loss /* [8] */,
+                          double *out_row /* [n][3], nullable */,
+                          float *grad_logits /* [n][A] */, float *grad_value /* [n] */,
+                          void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
