@@ -12,6 +12,16 @@
 // The draw of the logical row: i = mulhi(x.0, live), the multiply-high of a uniform 32-bit word.
 // Of the 2^32 words, floor(2^32 / live) or one more map to each i, so a row's probability is
 // within 2^-32 of 1 / live: a relative bias of at most live / 2^32 (0.05% at 2^21 rows).
+//
+// The weighted draw (rvz_replay_cdf, rvz_replay_batch_weighted): a per-slot float32 weight becomes
+// the fixed-point integer q = rint(w * 2^16), and a table holds the inclusive prefix sums C of q
+// over the live rows in logical order. k_cdf_scan / k_cdf_add build it as a tiled scan in
+// consecutive launches on one stream (a tile's local scan and its total, the totals scanned the
+// same way, the offsets added back), so no workgroup ever waits on another; every sum is an
+// integer, so the table's bytes depend on neither the tile nor the order of the adds.
+// k_replay_batch_weighted is k_replay_batch with another draw: t = mulhi64(u, total) of a uniform
+// 64-bit word u, and the row is the first i with C[i] > t, found 64 pivots at a time (a load per
+// lane and one ballot per round, 4 rounds at 2^21 rows).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -66,6 +76,185 @@ __global__ __launch_bounds__(SYM_THREADS) void k_replay_batch(
     }
 }
 
+// ---------------------------------------------------------------- the weighted draw
+constexpr int CDF_THREADS = 256;                 // 4 waves a tile
+constexpr int CDF_WAVES = CDF_THREADS / 64;
+constexpr int CDF_HEAD = 4;                      // total, invalid weights, start, live
+constexpr int CDF_TILE_LOG2 = 11;                // the default tile: 2,048 rows a workgroup
+constexpr int CDF_MAX_LEVELS = 8;                // 2^31 rows at the 64-row tile need 6
+constexpr int CDF_ADD_MAX_BLOCKS = 1 << 16;      // grid-stride beyond that
+
+inline bool tile_ok(int t) { return t == 0 || (t >= 6 && t <= 12); }
+
+// the scan's levels for n rows at tile 2^tl: cnt[0] = n, cnt[k + 1] = ceil(cnt[k] / tile), down to
+// cnt[L] == 1; returns L >= 1
+inline int cdf_levels(int64_t n, int tl, int64_t* cnt) {
+    int L = 0;
+    cnt[0] = n;
+    do {
+        cnt[L + 1] = (cnt[L] + ((int64_t)1 << tl) - 1) >> tl;
+        ++L;
+    } while (cnt[L] > 1);
+    return L;
+}
+
+// One tile of one level: the local inclusive scan of the tile's items into vals, the tile's total
+// into tot_out[tile] and its invalid weights into inv_out[tile]. LEAF: item i is q of the weight
+// of logical row i (slot (start + i) % capacity) and vals is C; else item i is vals[i] (the totals
+// of the level below, scanned in place) and its invalid count is inv_in[i]. A chunk of blockDim.x
+// items per step: a shuffle scan of the 64-bit items within each wave, the waves' totals through
+// LDS (two buffers, so one barrier a chunk), a running carry from chunk to chunk.
+template <bool LEAF>
+__global__ __launch_bounds__(CDF_THREADS) void k_cdf_scan(
+    const float* __restrict__ weight, int capacity, int start, uint64_t* vals,
+    const uint64_t* __restrict__ inv_in, int64_t n, int tile, uint64_t* __restrict__ tot_out,
+    uint64_t* __restrict__ inv_out) {
+    __shared__ uint64_t part[2][CDF_WAVES];
+    __shared__ uint64_t bad[CDF_WAVES];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int waves = blockDim.x >> 6;
+    const int64_t base = (int64_t)blockIdx.x * tile;
+    const int64_t end = base + tile < n ? base + tile : n;
+    uint64_t carry = 0ull, nbad = 0ull;
+    int c = 0;
+    for (int64_t at = base; at < end; at += blockDim.x, c ^= 1) {      // block-uniform trip count
+        const int64_t i = at + threadIdx.x;
+        uint64_t v = 0ull;
+        if (i < end) {
+            if (LEAF) {
+                const int64_t s = (int64_t)start + i;                   // below 2 * capacity
+                const float w = weight[s >= capacity ? s - capacity : s];
+                const bool valid = w >= 0.0f && w <= 65536.0f;          // NaN fails both
+                v = valid ? (uint64_t)rint((double)w * 65536.0) : 0ull;
+                nbad += valid ? 0ull : 1ull;
+            } else {
+                v = vals[i];
+                nbad += inv_in[i];
+            }
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint64_t up = __shfl_up((unsigned long long)v, d, 64);
+            if (lane >= d) v += up;
+        }
+        if (lane == 63) part[c][wave] = v;
+        __syncthreads();
+        uint64_t before = carry;
+        for (int w = 0; w < waves; ++w) {
+            const uint64_t p = part[c][w];
+            if (w < wave) before += p;
+            carry += p;
+        }
+        if (i < end) vals[i] = v + before;
+    }
+#pragma unroll
+    for (int d = 32; d; d >>= 1) nbad += __shfl_xor((unsigned long long)nbad, d, 64);
+    if (lane == 0) bad[wave] = nbad;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t all = 0ull;
+        for (int w = 0; w < waves; ++w) all += bad[w];
+        tot_out[blockIdx.x] = carry;
+        inv_out[blockIdx.x] = all;
+    }
+}
+
+// The offsets added back: vals[i] += prefix[i / tile - 1] for every item past the first tile
+// (prefix: the scanned totals of the level above). head (the level of C only): the table's four
+// header words, from the top level's one total and one count.
+__global__ __launch_bounds__(CDF_THREADS) void k_cdf_add(
+    uint64_t* __restrict__ vals, int64_t n, int tile_log2, const uint64_t* __restrict__ prefix,
+    uint64_t* __restrict__ head, const uint64_t* __restrict__ top_tot,
+    const uint64_t* __restrict__ top_inv, int start, int live) {
+    const int64_t stride = (int64_t)gridDim.x * CDF_THREADS;
+    for (int64_t i = ((int64_t)1 << tile_log2) + (int64_t)blockIdx.x * CDF_THREADS + threadIdx.x;
+         i < n; i += stride)
+        vals[i] += prefix[(i >> tile_log2) - 1];
+    if (head && blockIdx.x == 0 && threadIdx.x == 0) {
+        head[0] = *top_tot;
+        head[1] = *top_inv;
+        head[2] = (uint64_t)start;
+        head[3] = (uint64_t)live;
+    }
+}
+
+// k_replay_batch with the weighted draw. The search keeps [lo, hi] with C[hi] > t and C[lo - 1]
+// <= t: each round lane j reads pivot lo + (j + 1) * step - 1 (step = ceil(size / 64), clamped to
+// hi, which is known to be above t), and the first lane whose pivot is above t names the next
+// range.
+template <int BS>
+__global__ __launch_bounds__(SYM_THREADS) void k_replay_batch_weighted(
+    int capacity, const uint64_t* __restrict__ mover, const uint64_t* __restrict__ opponent,
+    const float* __restrict__ policy, const float* __restrict__ value,
+    const uint64_t* __restrict__ cdf, int start, int live, int nb,
+    const int32_t* __restrict__ idx, const int32_t* __restrict__ sym,
+    const uint64_t* __restrict__ word, int random_sym, uint32_t key0, uint32_t key1,
+    uint32_t step0, uint32_t step1, float* __restrict__ out_states,
+    float* __restrict__ out_policy, float* __restrict__ out_value, int32_t* __restrict__ out_slot,
+    int32_t* __restrict__ out_sym, float* __restrict__ out_prob) {
+    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int stride = gridDim.x * SYM_WAVES;       // nb * NPOL fits int32, so r + stride does too
+    const uint64_t total = cdf[0];
+    const bool fresh = cdf[2] == (uint64_t)start && cdf[3] == (uint64_t)live;
+    const uint64_t* __restrict__ C = cdf + CDF_HEAD;
+    for (int r = blockIdx.x * SYM_WAVES + wave; r < nb; r += stride) {  // wave-uniform trip count
+        const uint4 x = philox4x32_10(key0, key1, (uint32_t)r, step0, step1, 0u);
+        const int k = sym ? sym[r] : (random_sym ? (int)(x.y & 7u) : 0);
+        int i = -1;
+        if (idx) {
+            i = idx[r];
+        } else if (fresh && total) {                                    // wave-uniform
+            const uint64_t u = word ? word[r] : (((uint64_t)x.z << 32) | x.w);
+            const uint64_t t = __umul64hi(u, total);                    // < total = C[live - 1]
+            int64_t lo = 0, hi = live - 1;
+            while (hi - lo >= 64) {
+                const int64_t step = (hi - lo + 64) >> 6;               // ceil((hi - lo + 1) / 64)
+                const int64_t mine = lo + (int64_t)(lane + 1) * step - 1;
+                const bool above = mine >= hi || C[mine] > t;
+                const int f = __ffsll((unsigned long long)__ballot(above)) - 1;  // lane 63 is
+                const int64_t top = lo + (int64_t)(f + 1) * step - 1;
+                lo += (int64_t)f * step;
+                hi = top < hi ? top : hi;
+            }
+            const bool above = lo + lane >= hi || C[lo + lane] > t;
+            i = (int)(lo + __ffsll((unsigned long long)__ballot(above)) - 1);
+        }
+        const bool in = fresh && i >= 0 && i < live;
+        const int64_t at = (int64_t)start + (in ? i : 0);              // below 2 * capacity
+        const int slot = (int)(at >= capacity ? at - capacity : at);
+        const bool ok = in && k >= 0 && k < 8;
+        uint64_t P = 0ull, O = 0ull;
+        float pv = 0.0f, pass = 0.0f, v = 0.0f;
+        if (ok) {                                                       // wave-uniform
+            P = mover[slot];
+            O = opponent[slot];
+            const float* prow = policy + (size_t)slot * NPOL;           // capacity * NPOL: 64-bit
+            pv = lane < NSQ ? prow[lane] : 0.0f;
+            pass = prow[NSQ];
+            v = value[slot];
+        }
+        const uint64_t V = legal<BS>(P, O);
+        write_image<BS>(lane, P, O, V, pv, pass, ok ? k : -1, (size_t)r, out_states, out_policy,
+                        nullptr);
+        if (lane == 0) {
+            out_value[r] = v;
+            out_slot[r] = in ? slot : -1;
+            out_sym[r] = ok ? k : -1;
+            if (out_prob) {
+                float p = 0.0f;
+                if (in && total) {
+                    const uint64_t q = C[i] - (i ? C[i - 1] : 0ull);
+                    p = (float)((double)q / (double)total);
+                }
+                out_prob[r] = p;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int rvz_replay_batch(int32_t bs, int32_t capacity, const uint64_t* mover,
@@ -89,4 +278,85 @@ extern "C" int rvz_replay_batch(int32_t bs, int32_t capacity, const uint64_t* mo
                      capacity, mover, opponent, policy, value, start, live, nb, idx, sym,
                      random_sym, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step,
                      (uint32_t)(step >> 32), out_states, out_policy, out_value, out_slot, out_sym);
+}
+
+extern "C" int64_t rvz_replay_cdf_size(int32_t capacity, int32_t tile_log2) {
+    if (capacity < 1 || !tile_ok(tile_log2)) return -1;
+    int64_t cnt[CDF_MAX_LEVELS + 1];
+    const int L = cdf_levels(capacity, tile_log2 ? tile_log2 : CDF_TILE_LOG2, cnt);
+    int64_t words = CDF_HEAD + cnt[0];
+    for (int k = 1; k <= L; ++k) words += 2 * cnt[k];                  // totals and counts
+    return 8 * ((words + 1) & ~(int64_t)1);
+}
+
+extern "C" int rvz_replay_cdf(int32_t capacity, const float* weight, int32_t start, int32_t live,
+                              int32_t tile_log2, void* cdf, void* stream) {
+    if (capacity < 1 || live < 0 || live > capacity || start < 0 || start >= capacity ||
+        !tile_ok(tile_log2))
+        return RVZ_EINVAL;
+    if (live == 0) return RVZ_OK;
+    if (!weight || !cdf || ((uintptr_t)cdf & 15u) != 0) return RVZ_EINVAL;
+    const int tl = tile_log2 ? tile_log2 : CDF_TILE_LOG2;
+    const int tile = 1 << tl;
+    const int threads = tile < CDF_THREADS ? tile : CDF_THREADS;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t cnt[CDF_MAX_LEVELS + 1];
+    const int L = cdf_levels(live, tl, cnt);
+    // level k's totals tot[k] and counts inv[k], cnt[k] words each, behind C (level 0's values)
+    uint64_t* head = (uint64_t*)cdf;
+    uint64_t *tot[CDF_MAX_LEVELS + 1], *inv[CDF_MAX_LEVELS + 1];
+    tot[0] = head + CDF_HEAD;
+    inv[0] = nullptr;
+    uint64_t* next = tot[0] + cnt[0];
+    for (int k = 1; k <= L; ++k) {
+        tot[k] = next;
+        inv[k] = next + cnt[k];
+        next += 2 * cnt[k];
+    }
+    hipLaunchKernelGGL(k_cdf_scan<true>, dim3((unsigned)cnt[1]), dim3(threads), 0, s, weight,
+                       capacity, start, tot[0], (const uint64_t*)nullptr, cnt[0], tile, tot[1],
+                       inv[1]);
+    for (int k = 1; k < L; ++k)
+        hipLaunchKernelGGL(k_cdf_scan<false>, dim3((unsigned)cnt[k + 1]), dim3(threads), 0, s,
+                           (const float*)nullptr, 0, 0, tot[k], (const uint64_t*)inv[k], cnt[k],
+                           tile, tot[k + 1], inv[k + 1]);
+    for (int k = L - 2; k >= 0; --k) {                                  // tot[L - 1] is complete
+        const int64_t rest = cnt[k] - tile;                             // the items past tile 0
+        int64_t blocks = rest > 0 ? (rest + CDF_THREADS - 1) / CDF_THREADS : 1;
+        if (blocks > CDF_ADD_MAX_BLOCKS) blocks = CDF_ADD_MAX_BLOCKS;
+        hipLaunchKernelGGL(k_cdf_add, dim3((unsigned)blocks), dim3(CDF_THREADS), 0, s, tot[k],
+                           cnt[k], tl, (const uint64_t*)tot[k + 1], k ? nullptr : head,
+                           (const uint64_t*)tot[L], (const uint64_t*)inv[L], start, live);
+    }
+    if (L == 1)                                                         // one tile: the header
+        hipLaunchKernelGGL(k_cdf_add, dim3(1), dim3(CDF_THREADS), 0, s, tot[0], cnt[0], tl,
+                           (const uint64_t*)tot[1], head, (const uint64_t*)tot[1],
+                           (const uint64_t*)inv[1], start, live);
+    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+}
+
+extern "C" int rvz_replay_batch_weighted(int32_t bs, int32_t capacity, const uint64_t* mover,
+                                         const uint64_t* opponent, const float* policy,
+                                         const float* value, const void* cdf, int32_t start,
+                                         int32_t live, int32_t nb, const int32_t* idx,
+                                         const int32_t* sym, const uint64_t* word,
+                                         int32_t random_sym, uint64_t seed, uint64_t step,
+                                         float* out_states, float* out_policy, float* out_value,
+                                         int32_t* out_slot, int32_t* out_sym, float* out_prob,
+                                         void* stream) {
+    if (!board_ok(bs) || capacity < 1 || live < 1 || live > capacity || start < 0 ||
+        start >= capacity || nb < 0)
+        return RVZ_EINVAL;
+    if ((int64_t)nb * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
+    if (nb > 0 && (!mover || !opponent || !policy || !value || !cdf || !out_states ||
+                   !out_policy || !out_value || !out_slot || !out_sym ||
+                   ((uintptr_t)out_states & 15u) != 0 || ((uintptr_t)cdf & 15u) != 0))
+        return RVZ_EINVAL;
+    if (nb == 0) return RVZ_OK;
+    return launch_bs(bs, k_replay_batch_weighted<8>, k_replay_batch_weighted<6>,
+                     dim3(sym_blocks_for(nb, SYM_WAVES)), dim3(SYM_THREADS), (hipStream_t)stream,
+                     capacity, mover, opponent, policy, value, (const uint64_t*)cdf, start, live,
+                     nb, idx, sym, word, random_sym, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (uint32_t)step, (uint32_t)(step >> 32), out_states, out_policy, out_value,
+                     out_slot, out_sym, out_prob);
 }

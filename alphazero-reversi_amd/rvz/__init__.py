@@ -24,6 +24,10 @@ Batched core:
     ReplayBuffer, replay_batch   a ring of compact training records on the device across
                             iterations, and a minibatch drawn from it under random board
                             symmetries in one launch (rvz_replay_batch)
+    replay_cdf, replay_batch_weighted   the same draw in proportion to a per-row weight:
+                            ReplayBuffer(weighted=True), a table of integer prefix sums
+                            (rvz_replay_cdf) and the search through it
+                            (rvz_replay_batch_weighted)
     policy_value_loss, full_policy_loss   the loss on the full policy target, weighted per row,
                             with its gradients in one deterministic float64 call
                             (rvz_policy_value_loss), and its differentiable torch form
@@ -32,9 +36,9 @@ from ._lib import RvzError, load  # noqa: F401
 from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa: F401
                      SOLVE_NOT_A_MOVE, Engine, action_probs, alphabeta, alphabeta_weights,
                      best_moves, board_apply, board_canonical, board_legal, board_symmetry,
-                     dirichlet_noise, merge_positions, policy_softmax, replay_batch, solve,
-                     solve_moves, solve_moves_wld, solve_window, solve_wld, symmetry_compose,
-                     symmetry_inverse, training_rows)
+                     dirichlet_noise, merge_positions, policy_softmax, replay_batch,
+                     replay_batch_weighted, replay_cdf, solve, solve_moves, solve_moves_wld,
+                     solve_window, solve_wld, symmetry_compose, symmetry_inverse, training_rows)
 from .game import Board, ReversiGame  # noqa: F401
 from .loss import full_policy_loss, policy_value_loss  # noqa: F401
 from .mcts import MCTS  # noqa: F401

@@ -807,6 +807,116 @@ def replay_batch(mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tens
     return states, out_p, out_v, slot, out_k
 
 
+def replay_cdf(weight: torch.Tensor, start: int, live: int, tile_log2: int = 0,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rvz_replay_cdf: the table rvz.replay_batch_weighted draws from (include/rvz.h has the
+    layout). weight float32 [capacity], the ring's per-slot sampling weights, a device tensor; the
+    ring's `live` rows start at slot `start`. A weight w counts as rint(w * 2^16); one that is not
+    finite or outside [0, 65536] counts as 0 and is reported in word 1. Returns the table, int64
+    (the uint64 words' bit patterns, all below 2^63): word 0 the total, 1 the invalid weights,
+    2 start, 3 live, 4 + i the inclusive prefix sum up to logical row i; the words behind 4 + live
+    are scratch. out: an int64 device tensor of at least rvz_replay_cdf_size(capacity, tile_log2)
+    bytes to build into (a buffer kept across calls); None allocates one. tile_log2: 0, or the
+    scan's tile as a power of two in [6, 12]; the table does not depend on it. live = 0 writes
+    nothing. Asynchronous on the current stream."""
+    lib = _lib.load()
+    for name, x in (("start", start), ("live", live), ("tile_log2", tile_log2)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            raise RvzError(f"replay_cdf: {name} is an int, not {x!r}")
+    cap = weight.numel()
+    if weight.dim() != 1 or weight.dtype != torch.float32:
+        raise RvzError("replay_cdf: weight must be float32 [capacity]")
+    if cap < 1 or cap >= 2 ** 31:
+        raise RvzError("replay_cdf: the ring holds between 1 and 2^31 - 1 slots")
+    if not 0 <= live <= cap or not 0 <= start < cap:
+        raise RvzError(f"replay_cdf: live = {live} must be in [0, {cap}] and start = {start} in "
+                       f"[0, {cap})")
+    size = lib.rvz_replay_cdf_size(cap, int(tile_log2))
+    if size < 0:
+        raise RvzError(f"replay_cdf: tile_log2 = {tile_log2} must be 0 or in [6, 12]")
+    dev = weight.device
+    if out is None:
+        out = torch.empty(size // 8, dtype=torch.int64, device=dev)
+    elif out.dtype != torch.int64 or out.dim() != 1 or out.numel() * 8 < size or \
+            out.device != dev or not out.is_contiguous():
+        raise RvzError(f"replay_cdf: out must be a contiguous int64 tensor of at least {size // 8} "
+                       "words on the weights' device")
+    w = weight.contiguous()
+    check(lib.rvz_replay_cdf(cap, ptr(w), int(start), int(live), int(tile_log2), ptr(out),
+                             _lib.stream_handle(dev)), None, "rvz_replay_cdf")
+    return out
+
+
+def replay_batch_weighted(mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
+                          value: torch.Tensor, cdf: torch.Tensor, start: int, live: int, nb: int,
+                          seed: int, step: int, random_sym: bool = True,
+                          idx: Optional[torch.Tensor] = None, sym: Optional[torch.Tensor] = None,
+                          word: Optional[torch.Tensor] = None, board_size: int = 8):
+    """rvz_replay_batch_weighted: rvz.replay_batch with every row drawn in proportion to its
+    sampling weight, through the table `cdf` that rvz.replay_cdf built for the same (start, live).
+    word [nb] int64 (uint64 bit patterns): the uniform 64-bit words to draw with instead of the
+    generator's. The other arguments are replay_batch's. Returns replay_batch's five outputs and
+    prob float32 [nb], the probability q_i / total of each row taken. Row r's symmetry is
+    replay_batch's for the same (seed, step, r); its record is not, not even for equal weights.
+    Every row is a zero row (slot -1, sym -1, prob 0) when the table was built for another start
+    or live, and every drawn one when the weights' total is 0."""
+    if board_size not in (8, 6):
+        raise RvzError("board_size must be 8 or 6")
+    npol = board_size * board_size + 1
+    lib = _lib.load()
+    for name, x in (("start", start), ("live", live), ("nb", nb), ("seed", seed), ("step", step)):
+        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            raise RvzError(f"replay_batch_weighted: {name} is an int, not {x!r}")
+    cap = mover.numel()
+    if mover.dim() != 1 or opponent.shape != (cap,):
+        raise RvzError("replay_batch_weighted: mover and opponent hold one entry per slot")
+    if mover.dtype != torch.int64 or opponent.dtype != torch.int64:
+        raise RvzError("replay_batch_weighted: mover and opponent are int64 bit patterns")
+    if policy.shape != (cap, npol) or policy.dtype != torch.float32:
+        raise RvzError(f"replay_batch_weighted: policy must be float32 [capacity, {npol}]")
+    if value.shape not in ((cap,), (cap, 1)) or value.dtype != torch.float32:
+        raise RvzError("replay_batch_weighted: value must be float32 [capacity] or [capacity, 1]")
+    if cap < 1 or cap >= 2 ** 31:
+        raise RvzError("replay_batch_weighted: the ring holds between 1 and 2^31 - 1 slots")
+    if not 1 <= live <= cap or not 0 <= start < cap:
+        raise RvzError(f"replay_batch_weighted: live = {live} must be in [1, {cap}] and start = "
+                       f"{start} in [0, {cap})")
+    if nb < 0 or nb * npol >= 2 ** 31:
+        raise RvzError("replay_batch_weighted: nb must be >= 0 and nb * (S*S + 1) fit int32")
+    dev = mover.device
+    if cdf.dtype != torch.int64 or cdf.dim() != 1 or cdf.numel() < 4 + live or \
+            cdf.device != dev or not cdf.is_contiguous():
+        raise RvzError("replay_batch_weighted: cdf is rvz.replay_cdf's table (contiguous int64, at "
+                       "least 4 + live words, on the ring's device)")
+    given = []
+    for name, x in (("idx", idx), ("sym", sym)):
+        if x is not None and (x.shape != (nb,) or x.dtype.is_floating_point or
+                              x.dtype == torch.bool):
+            raise RvzError(f"replay_batch_weighted: {name} holds one integer per output row")
+        given.append(None if x is None else x.to(dev, torch.int32).contiguous())
+    if word is not None and (word.shape != (nb,) or word.dtype != torch.int64):
+        raise RvzError("replay_batch_weighted: word holds one int64 (a uint64 bit pattern) per "
+                       "output row")
+    wd = None if word is None else word.to(dev).contiguous()
+    m, o = mover.contiguous(), opponent.to(dev).contiguous()
+    pol = policy.to(dev).contiguous()
+    val = value.to(dev).reshape(cap).contiguous()
+    states = torch.empty(nb, 3, board_size, board_size, dtype=torch.float32, device=dev)
+    out_p = torch.empty(nb, npol, dtype=torch.float32, device=dev)
+    out_v = torch.empty(nb, 1, dtype=torch.float32, device=dev)
+    slot = torch.empty(nb, dtype=torch.int32, device=dev)
+    out_k = torch.empty(nb, dtype=torch.int32, device=dev)
+    prob = torch.empty(nb, dtype=torch.float32, device=dev)
+    if nb:
+        check(lib.rvz_replay_batch_weighted(
+            board_size, cap, ptr(m), ptr(o), ptr(pol), ptr(val), ptr(cdf), int(start), int(live),
+            int(nb), ptr(given[0]), ptr(given[1]), ptr(wd), int(bool(random_sym)),
+            int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), ptr(states), ptr(out_p),
+            ptr(out_v), ptr(slot), ptr(out_k), ptr(prob), _lib.stream_handle(dev)),
+            None, "rvz_replay_batch_weighted")
+    return states, out_p, out_v, slot, out_k, prob
+
+
 def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor, salt: int,
                     alpha: float, board_size: int = 8, bits: bool = False):
     """rvz_dirichlet_noise: the eta rows Engine.root_noise mixes into the roots' priors, by the

@@ -20,6 +20,7 @@ The reference's evaluation tournament and checkpointing (:128-140) are out of sc
 """
 from __future__ import annotations
 
+import numbers
 import time
 from typing import Dict, Optional
 
@@ -48,7 +49,8 @@ class SelfPlayTrainer:
                  symmetry_seed: Optional[int] = None, merge_positions: bool = False,
                  replay_iterations: int = 0, replay_capacity: Optional[int] = None,
                  replay_steps: Optional[int] = None, replay_symmetries: bool = True,
-                 policy_target: str = "argmax", count_weights: bool = False):
+                 policy_target: str = "argmax", count_weights: bool = False,
+                 replay_sampling: str = "uniform", replay_recency_decay: float = 1.0):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -102,6 +104,15 @@ class SelfPlayTrainer:
         iteration's new rows / train_batch), the steps of a pass over them; train_steps caps
         either. run_iteration reports replay_rows (the rows held after the iteration's append)
         and replay_iterations_held (0 when off).
+        replay_sampling: "uniform" (the default: every held row is as likely as any other) or
+        "counts": every merged row is appended with its position_counts as its sampling weight
+        (ReplayBuffer(weighted=True); the rvz_replay_cdf / rvz_replay_batch_weighted HIP
+        kernels), so a position is drawn in proportion to the records it stands for: the start
+        position as often as if it had not been merged. It needs replay_iterations > 0 and
+        merge_positions=True, ValueError otherwise. The sampling then carries the counts, so
+        with policy_target="full" every drawn row weighs 1 in the loss. replay_recency_decay: d in
+        (0, 1]: a held row's sampling weight is multiplied by d with every newer iteration
+        appended, under either replay_sampling; a d other than 1 needs replay_iterations > 0.
         policy_target: "argmax" (the default: the reference's criterion) or "full": the trainer's
         loss is AlphaZero's own -pi . log p on the whole policy target (DDPTrainer;
         rvz.full_policy_loss, the rvz_policy_value_loss HIP kernels), so a merged row's mean
@@ -126,6 +137,23 @@ class SelfPlayTrainer:
         if count_weights and replay_iterations:
             raise ValueError("count_weights=True needs replay_iterations=0: the replay ring "
                              "stores no position counts")
+        if replay_sampling not in ("uniform", "counts"):
+            raise ValueError("replay_sampling must be 'uniform' or 'counts', not "
+                             f"{replay_sampling!r}")
+        if replay_sampling == "counts" and not replay_iterations:
+            raise ValueError("replay_sampling='counts' needs replay_iterations > 0: it is the "
+                             "replay buffer's draw")
+        if replay_sampling == "counts" and not merge_positions:
+            raise ValueError("replay_sampling='counts' needs merge_positions=True (the weights "
+                             "are the merged rows' position_counts)")
+        if isinstance(replay_recency_decay, bool) or \
+                not isinstance(replay_recency_decay, numbers.Real) or \
+                not 0.0 < replay_recency_decay <= 1.0:
+            raise ValueError("replay_recency_decay must be in (0, 1], not "
+                             f"{replay_recency_decay!r}")
+        if replay_recency_decay != 1.0 and not replay_iterations:
+            raise ValueError("replay_recency_decay != 1 needs replay_iterations > 0: it ages "
+                             "the replay buffer's rows")
         self.model = model.eval()
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -150,6 +178,8 @@ class SelfPlayTrainer:
                              f"(replay_symmetries): symmetries must be None, not {symmetries!r}")
         self.replay_steps = None if replay_steps is None else int(replay_steps)
         self.replay_symmetries = bool(replay_symmetries)
+        self.replay_sampling = replay_sampling
+        self.replay_recency_decay = float(replay_recency_decay)
         self.adjudicate_empties = int(adjudicate_empties)
         self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
@@ -192,8 +222,12 @@ class SelfPlayTrainer:
         if self.replay_iterations:
             if replay_capacity is None:
                 replay_capacity = self.replay_iterations * self.games * self.max_plies
+            weighted = self.replay_sampling == "counts" or self.replay_recency_decay != 1.0
             self.buffer = ReplayBuffer(int(replay_capacity), bs, self.device,
-                                       window_iterations=self.replay_iterations)
+                                       window_iterations=self.replay_iterations,
+                                       **({"weighted": True,
+                                           "recency_decay": self.replay_recency_decay}
+                                          if weighted else {}))
         self.iteration = 0
 
     def _seeds(self):
@@ -264,13 +298,20 @@ class SelfPlayTrainer:
         out.update(stats)
         return out
 
+    def _append(self, data: Dict[str, torch.Tensor]) -> None:
+        """The iteration's compact rows into the replay buffer; with replay_sampling="counts" each
+        merged row's position_counts is its sampling weight."""
+        counts = ({"weight": data["position_counts"].to(torch.float32)}
+                  if self.replay_sampling == "counts" else {})
+        self.buffer.append(data["mover"], data["opponent"], data["policy_targets"],
+                           data["value_targets"], self.iteration, **counts)
+
     def train(self, data: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """_train_epoch over this iteration's data (each rank walks its own games; DDP averages
         the gradients), then the evaluator picks up the new weights. With a replay buffer the
         iteration's rows are appended to it first and the steps draw from the whole window."""
         if self.buffer is not None:
-            self.buffer.append(data["mover"], data["opponent"], data["policy_targets"],
-                               data["value_targets"], self.iteration)
+            self._append(data)
             steps = self.replay_steps
             if steps is None:
                 steps = -(-data["mover"].shape[0] // self.trainer.batch_size)

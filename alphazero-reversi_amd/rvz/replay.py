@@ -7,6 +7,11 @@ records (mover bitboard, opponent bitboard, policy row, value: 280 B a row on 8x
 and one HIP kernel samples (``rvz.replay_batch`` / rvz_replay_batch, include/rvz.h): a uniform
 record and a fresh board symmetry per drawn row, the planes and the permuted policy written
 straight from the bitboards, no host randomness.
+
+``ReplayBuffer(weighted=True)`` adds a sampling weight per row (a merged position's record count,
+a priority) and a recency decay, and draws rows in proportion to their weights: a table of integer
+prefix sums built on the device after each append (``rvz.replay_cdf`` / rvz_replay_cdf) and one
+kernel that draws through it (``rvz.replay_batch_weighted`` / rvz_replay_batch_weighted).
 """
 from __future__ import annotations
 
@@ -15,12 +20,14 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .engine import replay_batch
+from . import _lib
+from .engine import replay_batch, replay_batch_weighted, replay_cdf
 
 
 class ReplayBuffer:
     def __init__(self, capacity: int, board_size: int = 8, device=None,
-                 window_iterations: int = 0, batcher=None):
+                 window_iterations: int = 0, batcher=None, weighted: bool = False,
+                 recency_decay: float = 1.0, weighted_batcher=None, cdf_builder=None):
         """capacity: the ring's rows. window_iterations = K > 0: an append of iteration t also
         drops every row of an iteration before t - K + 1 (0: rows leave only when overwritten).
         batcher(mover, opponent, policy, value, start, live, nb, seed, step, random_sym, idx, sym,
@@ -28,7 +35,21 @@ class ReplayBuffer:
         rvz_replay_batch HIP kernel; the ring must then be on the GPU). Tests on a host without
         a GPU pass a NumPy restatement.
         The ledger of (iteration, rows) is kept on the host and row counts are tensor shapes, so
-        neither append nor sample synchronises with the device."""
+        neither append nor sample synchronises with the device.
+        weighted=True: the ring also holds `weight` float32 [capacity], a sampling weight per row
+        (append's `weight`, 1.0 by default), and sample draws a row with probability weight /
+        the sum of the weights held. A weight counts in fixed point, rint(w * 2^16); one that is
+        not finite or outside [0, 65536] counts as 0, so the row is never drawn
+        (invalid_weights() counts them). recency_decay = d in (0, 1]: an append of an iteration t
+        newer than the newest held iteration t0 first multiplies every held weight in place by
+        float32(d ** (t - t0)), one float32 multiply per row, so a row's weight falls by d with
+        every iteration it ages. The table of prefix sums the draw reads lives in a buffer
+        allocated here once; append marks it stale and the next sample rebuilds it.
+        cdf_builder(weight, start, live, tile_log2, out) -> the table built into `out`: default
+        rvz.replay_cdf. weighted_batcher(mover, opponent, policy, value, cdf, start, live, nb,
+        seed, step, random_sym, idx, sym, word, board_size) -> batcher's five outputs and prob
+        [nb]: default rvz.replay_batch_weighted. total_weight() and invalid_weights() read the
+        table's first two words: the only host synchronisations."""
         for name, x in (("capacity", capacity), ("window_iterations", window_iterations)):
             if isinstance(x, bool) or not isinstance(x, numbers.Integral):
                 raise ValueError(f"ReplayBuffer: {name} is an int, not {x!r}")
@@ -42,6 +63,15 @@ class ReplayBuffer:
         self.window_iterations = int(window_iterations)
         self.device = torch.device("cuda" if device is None else device)
         self.batcher = replay_batch if batcher is None else batcher
+        self.weighted = bool(weighted)
+        if not self.weighted and (recency_decay != 1.0 or weighted_batcher is not None or
+                                  cdf_builder is not None):
+            raise ValueError("ReplayBuffer: recency_decay, weighted_batcher and cdf_builder need "
+                             "weighted=True")
+        if isinstance(recency_decay, bool) or not isinstance(recency_decay, numbers.Real) or \
+                not 0.0 < recency_decay <= 1.0:
+            raise ValueError(f"ReplayBuffer: recency_decay must be in (0, 1], not "
+                             f"{recency_decay!r}")
         npol = self.board_size ** 2 + 1
         self.mover = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
         self.opponent = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
@@ -50,6 +80,16 @@ class ReplayBuffer:
         self.start = 0                  # the slot of the oldest row
         self._live = 0
         self._ledger: List[List[int]] = []      # [iteration, rows], oldest first
+        if self.weighted:
+            self.recency_decay = float(recency_decay)
+            self.weighted_batcher = (replay_batch_weighted if weighted_batcher is None
+                                     else weighted_batcher)
+            self.cdf_builder = replay_cdf if cdf_builder is None else cdf_builder
+            self.weight = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+            # the table at this capacity: 4 words of header, one per row, the scan's upper levels
+            words = _lib.load().rvz_replay_cdf_size(self.capacity, 0) // 8
+            self._cdf = torch.zeros(words, dtype=torch.int64, device=self.device)
+            self._dirty = True
 
     def __len__(self) -> int:
         return self._live
@@ -69,11 +109,13 @@ class ReplayBuffer:
                 self._ledger.pop(0)
 
     def append(self, mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
-               value: torch.Tensor, iteration: int) -> None:
+               value: torch.Tensor, iteration: int,
+               weight: Optional[torch.Tensor] = None) -> None:
         """n <= capacity rows of `iteration` at the head of the ring (at most two slice copies per
         tensor), over the oldest rows once the ring is full. mover / opponent int64 [n], policy
         float32 [n, S*S+1], value float32 [n] or [n, 1]. Iterations are appended in
-        non-decreasing order."""
+        non-decreasing order. weight (weighted=True only): float32 [n], the rows' sampling
+        weights; None: 1.0 each."""
         if isinstance(iteration, bool) or not isinstance(iteration, numbers.Integral):
             raise ValueError(f"ReplayBuffer.append: iteration is an int, not {iteration!r}")
         n = mover.numel()
@@ -86,6 +128,11 @@ class ReplayBuffer:
                 policy.dtype != torch.float32 or value.dtype != torch.float32:
             raise ValueError("ReplayBuffer.append: mover and opponent are int64, policy and value "
                              "float32")
+        if weight is not None:
+            if not self.weighted:
+                raise ValueError("ReplayBuffer.append: weight needs ReplayBuffer(weighted=True)")
+            if weight.shape != (n,) or weight.dtype != torch.float32:
+                raise ValueError("ReplayBuffer.append: weight is float32 [n]")
         if n > self.capacity:
             raise ValueError(f"ReplayBuffer.append: {n} rows do not fit a ring of {self.capacity}")
         if self._ledger and iteration < self._ledger[-1][0]:
@@ -94,8 +141,19 @@ class ReplayBuffer:
         if n:
             head = (self.start + self._live) % self.capacity
             first = min(n, self.capacity - head)
-            for ring, rows in ((self.mover, mover), (self.opponent, opponent),
-                               (self.policy, policy), (self.value, value.reshape(n))):
+            fields = [(self.mover, mover), (self.opponent, opponent), (self.policy, policy),
+                      (self.value, value.reshape(n))]
+            if self.weighted:
+                if self._ledger and iteration > self._ledger[-1][0] and self.recency_decay != 1.0:
+                    # the held rows age by the iterations that passed (slots that hold no row too:
+                    # they are never read)
+                    factor = self.recency_decay ** (int(iteration) - self._ledger[-1][0])
+                    self.weight.mul_(torch.tensor(factor, dtype=torch.float32).item())
+                if weight is None:
+                    weight = torch.ones(n, dtype=torch.float32, device=self.device)
+                fields.append((self.weight, weight))
+                self._dirty = True
+            for ring, rows in fields:
                 ring[head:head + first].copy_(rows[:first])
                 if first < n:
                     ring[:n - first].copy_(rows[first:])
@@ -111,16 +169,52 @@ class ReplayBuffer:
                       if it < iteration - self.window_iterations + 1)
             if old:
                 self._drop_oldest(old)
+                if self.weighted:
+                    self._dirty = True
 
     def sample(self, nb: int, seed: int, step: int, symmetries: bool = True,
-               idx: Optional[torch.Tensor] = None, sym: Optional[torch.Tensor] = None):
+               idx: Optional[torch.Tensor] = None, sym: Optional[torch.Tensor] = None,
+               word: Optional[torch.Tensor] = None, with_prob: bool = False):
         """A batch of nb rows: (states [nb, 3, S, S], policy [nb, S*S+1], value [nb, 1], slot
         [nb], sym [nb]), a pure function of (the ring, seed, step). Every row is drawn uniformly
         from the rows held, under a uniformly drawn board symmetry (symmetries=False: the
         identity). idx / sym [nb]: the logical rows (0 the oldest) and the symmetries to take
-        instead of the draws."""
+        instead of the draws.
+        weighted=True: every row is drawn with probability weight / total weight instead (the
+        symmetries are the same draws). word [nb] int64 (uint64 bit patterns): the uniform 64-bit
+        words to draw with in place of the generator's. with_prob=True: a sixth output, prob
+        float32 [nb], each taken row's probability. With every weight 0 or invalid all drawn rows
+        are zero rows with slot -1 and sym -1."""
         if not self._live:
             raise ValueError("ReplayBuffer.sample: the buffer is empty")
+        if self.weighted:
+            out = self.weighted_batcher(self.mover, self.opponent, self.policy, self.value,
+                                        self._table(), self.start, self._live, nb, seed, step,
+                                        bool(symmetries), idx, sym, word, self.board_size)
+            return out if with_prob else out[:5]
+        if word is not None or with_prob:
+            raise ValueError("ReplayBuffer.sample: word and with_prob need "
+                             "ReplayBuffer(weighted=True)")
         return self.batcher(self.mover, self.opponent, self.policy, self.value, self.start,
                             self._live, nb, seed, step, bool(symmetries), idx, sym,
                             self.board_size)
+
+    def _table(self) -> torch.Tensor:
+        """The table of the rows held now, rebuilt if an append changed them."""
+        if self._dirty:
+            self._cdf = self.cdf_builder(self.weight, self.start, self._live, 0, self._cdf)
+            self._dirty = False
+        return self._cdf
+
+    def total_weight(self) -> float:
+        """The sum of the valid weights held, as sampled: fixed point / 2^16. Synchronises."""
+        if not self.weighted:
+            raise ValueError("ReplayBuffer.total_weight needs ReplayBuffer(weighted=True)")
+        return int(self._table()[0].item()) / 65536.0 if self._live else 0.0
+
+    def invalid_weights(self) -> int:
+        """The rows held whose weight is not finite or outside [0, 65536]: they are never drawn.
+        Synchronises."""
+        if not self.weighted:
+            raise ValueError("ReplayBuffer.invalid_weights needs ReplayBuffer(weighted=True)")
+        return int(self._table()[1].item()) if self._live else 0

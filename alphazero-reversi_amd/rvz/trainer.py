@@ -416,7 +416,10 @@ class DDPTrainer:
         train_epoch(local_data=True) spreads it; each step's global batch is world x batch_size,
         and every rank runs the same number of steps (the minimum over ranks). Returns
         train_epoch's loss dict, averaged over ranks too. The ring stores no record counts, so
-        in "full" mode every drawn row weighs 1."""
+        in "full" mode every drawn row weighs 1. With a ReplayBuffer(weighted=True) the draw is in
+        proportion to the rows' sampling weights instead; where those are record counts
+        (SelfPlayTrainer(replay_sampling="counts")) the sampling carries the counts, and every
+        drawn row still weighs 1 in the loss."""
         rank, world = self.rank_world()
         steps = int(steps)
         if self.distributed:          # every rank must run the same number of DDP steps

@@ -571,6 +571,82 @@ int rvz_replay_batch(int32_t board_size, int32_t capacity, const uint64_t *mover
                      float *out_policy /* [nb][S*S+1] */, float *out_value /* [nb] */,
                      int32_t *out_slot /* [nb] */, int32_t *out_sym /* [nb] */, void *hip_stream);
 
+/* ---- weighted replay sampling: rows drawn in proportion to a per-row weight ----------------
+ * The ring gains weight float32 [capacity], one sampling weight per slot (a merged position's
+ * record count, a recency factor, a priority). rvz_replay_cdf turns the live rows' weights into a
+ * table of integer prefix sums, and rvz_replay_batch_weighted is rvz_replay_batch drawing logical
+ * row i with probability q_i / total from that table. Both are stateless, on caller arrays
+ * (device pointers), asynchronous on hip_stream and graph-capturable: no allocation, no copy, no
+ * memset, no synchronisation, no host randomness; the table needs no preparation.
+ * Fixed point: q(w) = (uint64) rint((double) w * 2^16) (round half to even). A weight is valid
+ * iff it is finite and 0 <= w <= 65536 (-0 is 0); then q <= 2^32, and with live < 2^31 the total
+ * stays below 2^63. An invalid weight (NaN, negative, above 65536, infinite) has q = 0: the row is
+ * never drawn, and it is counted. Every sum is an integer, so the table's bytes depend neither on
+ * the tile nor on the order of the adds.
+ * The table, uint64 words, 16-byte aligned, rvz_replay_cdf_size(capacity, tile_log2) bytes
+ * (non-decreasing in capacity; negative for capacity < 1 or a bad tile_log2):
+ *   [0] total = C[live - 1]      [1] the invalid weights among the live rows
+ *   [2] start                    [3] live
+ *   [4 + i] C[i] = q_0 + ... + q_i for i < live, q_i the q of the weight in slot
+ *           (start + i) % capacity: logical order, oldest first, the ring's wrap handled here
+ *   behind that, private scratch of the scan's upper levels.
+ * Words [0, 4 + live) are the contract. The scan is tiled and spread over consecutive launches:
+ * a workgroup scans its tile into C (a shuffle scan of the 64-bit values within a wavefront, the
+ * wavefronts combined through LDS) and writes the tile's total; the totals are scanned the same
+ * way, level on level until one tile holds them (three levels for 2^31 rows at the default tile
+ * of 2^11 rows); the offsets are added back level by level. No workgroup ever waits on another.
+ * tile_log2: 0 for the default tile, else 2^tile_log2 rows per workgroup with tile_log2 in
+ * [6, 12] (a test hook: at 6, 64 * 64 + 1 rows reach the third level); the table's contract
+ * words do not depend on it.
+ * rvz_replay_cdf RVZ_EINVAL (before any HIP call): capacity < 1, live outside [0, capacity],
+ * start outside [0, capacity), tile_log2 outside {0} and [6, 12], and with live > 0 a null
+ * weight, a null cdf or a cdf that is not 16-byte aligned. live = 0 returns RVZ_OK without a
+ * launch, and then nothing is written.
+ *
+ * rvz_replay_batch_weighted: rvz_replay_batch's arguments and, per output row r, its Philox
+ * block x (the same key and counter), its k and its outputs; the logical row is drawn otherwise:
+ *   u = word[r] if word is given, else ((uint64) x.2 << 32) | x.3
+ *   t = (u * total) >> 64 in 128-bit terms (the multiply-high of two 64-bit words), 0 <= t < total
+ *   i = the smallest logical row with C[i] > t. A row with q = 0 has C[i] == C[i - 1] and is
+ *       never chosen. Of the 2^64 words, floor(2^64 q_i / total) or one more lead to row i: its
+ *       probability is within 2^-64 of q_i / total.
+ * A given idx[r] takes the place of the draw, with rvz_replay_batch's handling of an idx outside
+ * [0, live); the table is then read for out_prob alone. The draws are NOT those of
+ * rvz_replay_batch, not even with all weights equal: that call draws from x.0, this one from
+ * x.2 and x.3. Only k (x.1) is shared.
+ * out_prob float32 [nb], nullable: (float) ((double) q_i / (double) total) of the row taken
+ * (given or drawn) wherever out_slot[r] >= 0, else 0, and 0 with total == 0; a caller forms
+ * importance weights from it.
+ * Zero rows (states and policy all zero, out_value 0, out_slot -1, out_sym -1, out_prob 0) are
+ * written for every row when the table's words [2], [3] differ from the call's start / live (a
+ * stale table), and for every row without a given idx when total == 0. Both are checked in the
+ * kernel, no host synchronisation.
+ * The search reads 64 evenly spaced pivots of the current range per round, one per lane, and one
+ * ballot narrows the range 64-fold: 4 rounds at 2^21 rows, 6 at 2^31. The result is defined by
+ * the rule above, not by the method.
+ * Every output element of all nb rows is written by exactly one lane. A row's outputs depend on
+ * (the ring, the table, start, live, capacity, seed, step, r, idx[r], sym[r], word[r]) alone, not
+ * on nb or the launch geometry. The outputs must not overlap the ring, the table or each other.
+ * RVZ_EINVAL (before any HIP call): as rvz_replay_batch, and with nb > 0 a null cdf or a cdf
+ * that is not 16-byte aligned. nb = 0 returns RVZ_OK without a launch. */
+int64_t rvz_replay_cdf_size(int32_t capacity, int32_t tile_log2);
+int rvz_replay_cdf(int32_t capacity, const float *weight /* [capacity] */, int32_t start,
+                   int32_t live, int32_t tile_log2, void *cdf /* 16-byte aligned */,
+                   void *hip_stream);
+int rvz_replay_batch_weighted(int32_t board_size, int32_t capacity, const uint64_t *mover,
+                              const uint64_t *opponent /* [capacity] */,
+                              const float *policy /* [capacity][S*S+1] */,
+                              const float *value /* [capacity] */,
+                              const void *cdf /* rvz_replay_cdf's table */, int32_t start,
+                              int32_t live, int32_t nb, const int32_t *idx /* [nb], nullable */,
+                              const int32_t *sym /* [nb], nullable */,
+                              const uint64_t *word /* [nb], nullable */, int32_t random_sym,
+                              uint64_t seed, uint64_t step,
+                              float *out_states /* [nb][3][S][S], 16-byte aligned */,
+                              float *out_policy /* [nb][S*S+1] */, float *out_value /* [nb] */,
+                              int32_t *out_slot /* [nb] */, int32_t *out_sym /* [nb] */,
+                              float *out_prob /* [nb], nullable */, void *hip_stream);
+
 /* ---- policy/value loss on the full policy target -------------------------------------------
  * AlphaZero's own loss, -pi . log p + (y - t)^2, on the whole target distribution (a merged
  * position's mean search policy, the uniform distribution over the proven-optimal moves, a visit
