@@ -19,9 +19,9 @@
 // consecutive launches on one stream (a tile's local scan and its total, the totals scanned the
 // same way, the offsets added back), so no workgroup ever waits on another; every sum is an
 // integer, so the table's bytes depend on neither the tile nor the order of the adds.
-// k_replay_batch_weighted is k_replay_batch with another draw: t = mulhi64(u, total) of a uniform
-// 64-bit word u, and the row is the first i with C[i] > t, found 64 pivots at a time (a load per
-// lane and one ballot per round, 4 rounds at 2^21 rows).
+// rvz_replay_batch_weighted is k_replay_batch with another draw: t = mulhi64(u, total) of a
+// uniform 64-bit word u, and the row is the first i with C[i] > t, found 64 pivots at a time (a
+// load per lane and one ballot per round, 4 rounds at 2^21 rows).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,48 +35,7 @@ namespace {
 
 using namespace rvz;
 
-template <int BS>
-__global__ __launch_bounds__(SYM_THREADS) void k_replay_batch(
-    int capacity, const uint64_t* __restrict__ mover, const uint64_t* __restrict__ opponent,
-    const float* __restrict__ policy, const float* __restrict__ value, int start, int live, int nb,
-    const int32_t* __restrict__ idx, const int32_t* __restrict__ sym, int random_sym, uint32_t key0,
-    uint32_t key1, uint32_t step0, uint32_t step1, float* __restrict__ out_states,
-    float* __restrict__ out_policy, float* __restrict__ out_value, int32_t* __restrict__ out_slot,
-    int32_t* __restrict__ out_sym) {
-    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int stride = gridDim.x * SYM_WAVES;       // nb * NPOL fits int32, so r + stride does too
-    for (int r = blockIdx.x * SYM_WAVES + wave; r < nb; r += stride) {  // wave-uniform trip count
-        const uint4 x = philox4x32_10(key0, key1, (uint32_t)r, step0, step1, 0u);
-        const int i = idx ? idx[r] : (int)__umulhi(x.x, (uint32_t)live);
-        const int k = sym ? sym[r] : (random_sym ? (int)(x.y & 7u) : 0);
-        const bool in = i >= 0 && i < live;
-        const int64_t at = (int64_t)start + (in ? i : 0);              // below 2 * capacity
-        const int slot = (int)(at >= capacity ? at - capacity : at);
-        const bool ok = in && k >= 0 && k < 8;
-        uint64_t P = 0ull, O = 0ull;
-        float pv = 0.0f, pass = 0.0f, v = 0.0f;
-        if (ok) {                                                       // wave-uniform
-            P = mover[slot];
-            O = opponent[slot];
-            const float* prow = policy + (size_t)slot * NPOL;           // capacity * NPOL: 64-bit
-            pv = lane < NSQ ? prow[lane] : 0.0f;
-            pass = prow[NSQ];
-            v = value[slot];
-        }
-        const uint64_t V = legal<BS>(P, O);
-        write_image<BS>(lane, P, O, V, pv, pass, ok ? k : -1, (size_t)r, out_states, out_policy,
-                        nullptr);
-        if (lane == 0) {
-            out_value[r] = v;
-            out_slot[r] = in ? slot : -1;
-            out_sym[r] = ok ? k : -1;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- the weighted draw
+// ---------------------------------------------------------------- the weighted draw's table
 constexpr int CDF_THREADS = 256;                 // 4 waves a tile
 constexpr int CDF_WAVES = CDF_THREADS / 64;
 constexpr int CDF_HEAD = 4;                      // total, invalid weights, start, live
@@ -179,80 +138,129 @@ __global__ __launch_bounds__(CDF_THREADS) void k_cdf_add(
     }
 }
 
-// k_replay_batch with the weighted draw. The search keeps [lo, hi] with C[hi] > t and C[lo - 1]
-// <= t: each round lane j reads pivot lo + (j + 1) * step - 1 (step = ceil(size / 64), clamped to
-// hi, which is known to be above t), and the first lane whose pivot is above t names the next
-// range.
-template <int BS>
-__global__ __launch_bounds__(SYM_THREADS) void k_replay_batch_weighted(
+// ---------------------------------------------------------------- the draws and the batch kernel
+// A draw is k_replay_batch's compile-time parameter, built once per wave from its Args (the host's
+// part). `fresh`: it was built for this ring state (else every row is a zero row); row(): output
+// row r's logical row from r's Philox block, by the whole wave (-1: none); prob(): lane 0's store.
+
+// i = mulhi(x.0, live)
+struct UniformDraw {
+    struct Args {};
+    static constexpr bool fresh = true;
+    __device__ UniformDraw(Args, int, int) {}
+    __device__ int row(int, int, const uint4& x, int live) const {
+        return (int)__umulhi(x.x, (uint32_t)live);
+    }
+    __device__ void prob(int, int, bool) const {}
+};
+
+// The first i with C[i] > t, t = mulhi64(u, total). The search keeps [lo, hi] with C[hi] > t and
+// C[lo - 1] <= t: each round lane j reads pivot lo + (j + 1) * step - 1 (step = ceil(size / 64),
+// clamped to hi, which is known to be above t), and the first lane whose pivot is above t names
+// the next range. Its trip count depends on live alone.
+struct WeightedDraw {
+    struct Args { const uint64_t *cdf, *word; float* out_prob; };      // word, out_prob: or null
+    const uint64_t *__restrict__ C, *__restrict__ word;
+    float* __restrict__ out_prob;
+    uint64_t total;
+    bool fresh;
+    __device__ WeightedDraw(Args a, int start, int live)
+        : C(a.cdf + CDF_HEAD), word(a.word), out_prob(a.out_prob), total(a.cdf[0]),
+          fresh(a.cdf[2] == (uint64_t)start && a.cdf[3] == (uint64_t)live) {}
+    __device__ int row(int lane, int r, const uint4& x, int live) const {
+        if (!(fresh && total)) return -1;                               // wave-uniform
+        const uint64_t u = word ? word[r] : (((uint64_t)x.z << 32) | x.w);
+        const uint64_t t = __umul64hi(u, total);                        // < total = C[live - 1]
+        int64_t lo = 0, hi = live - 1;
+        while (hi - lo >= 64) {
+            const int64_t step = (hi - lo + 64) >> 6;                   // ceil((hi - lo + 1) / 64)
+            const int64_t mine = lo + (int64_t)(lane + 1) * step - 1;
+            const bool above = mine >= hi || C[mine] > t;
+            const int f = __ffsll((unsigned long long)__ballot(above)) - 1;     // lane 63 is
+            const int64_t top = lo + (int64_t)(f + 1) * step - 1;
+            lo += (int64_t)f * step;
+            hi = top < hi ? top : hi;
+        }
+        const bool above = lo + lane >= hi || C[lo + lane] > t;
+        return (int)(lo + __ffsll((unsigned long long)__ballot(above)) - 1);
+    }
+    __device__ void prob(int r, int i, bool in) const {
+        if (!out_prob) return;
+        float p = 0.0f;
+        if (in && total) {
+            const uint64_t q = C[i] - (i ? C[i - 1] : 0ull);
+            p = (float)((double)q / (double)total);
+        }
+        out_prob[r] = p;
+    }
+};
+
+// One wavefront per output row: the logical row (given or drawn), its slot, the record, its image
+// (write_record) and lane 0's per-row words. A row that is not `ok` is written too, as zeros.
+template <int BS, class Draw>
+__global__ __launch_bounds__(SYM_THREADS) void k_replay_batch(
     int capacity, const uint64_t* __restrict__ mover, const uint64_t* __restrict__ opponent,
-    const float* __restrict__ policy, const float* __restrict__ value,
-    const uint64_t* __restrict__ cdf, int start, int live, int nb,
+    const float* __restrict__ policy, const float* __restrict__ value, int start, int live, int nb,
     const int32_t* __restrict__ idx, const int32_t* __restrict__ sym,
-    const uint64_t* __restrict__ word, int random_sym, uint32_t key0, uint32_t key1,
+    const typename Draw::Args draw_args, int random_sym, uint32_t key0, uint32_t key1,
     uint32_t step0, uint32_t step1, float* __restrict__ out_states,
     float* __restrict__ out_policy, float* __restrict__ out_value, int32_t* __restrict__ out_slot,
-    int32_t* __restrict__ out_sym, float* __restrict__ out_prob) {
-    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    int32_t* __restrict__ out_sym) {
+    constexpr int NPOL = Geo<BS>::NPOL;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int stride = gridDim.x * SYM_WAVES;       // nb * NPOL fits int32, so r + stride does too
-    const uint64_t total = cdf[0];
-    const bool fresh = cdf[2] == (uint64_t)start && cdf[3] == (uint64_t)live;
-    const uint64_t* __restrict__ C = cdf + CDF_HEAD;
+    const Draw draw(draw_args, start, live);
     for (int r = blockIdx.x * SYM_WAVES + wave; r < nb; r += stride) {  // wave-uniform trip count
         const uint4 x = philox4x32_10(key0, key1, (uint32_t)r, step0, step1, 0u);
         const int k = sym ? sym[r] : (random_sym ? (int)(x.y & 7u) : 0);
-        int i = -1;
-        if (idx) {
-            i = idx[r];
-        } else if (fresh && total) {                                    // wave-uniform
-            const uint64_t u = word ? word[r] : (((uint64_t)x.z << 32) | x.w);
-            const uint64_t t = __umul64hi(u, total);                    // < total = C[live - 1]
-            int64_t lo = 0, hi = live - 1;
-            while (hi - lo >= 64) {
-                const int64_t step = (hi - lo + 64) >> 6;               // ceil((hi - lo + 1) / 64)
-                const int64_t mine = lo + (int64_t)(lane + 1) * step - 1;
-                const bool above = mine >= hi || C[mine] > t;
-                const int f = __ffsll((unsigned long long)__ballot(above)) - 1;  // lane 63 is
-                const int64_t top = lo + (int64_t)(f + 1) * step - 1;
-                lo += (int64_t)f * step;
-                hi = top < hi ? top : hi;
-            }
-            const bool above = lo + lane >= hi || C[lo + lane] > t;
-            i = (int)(lo + __ffsll((unsigned long long)__ballot(above)) - 1);
-        }
-        const bool in = fresh && i >= 0 && i < live;
+        const int i = idx ? idx[r] : draw.row(lane, r, x, live);        // idx: wave-uniform
+        const bool in = draw.fresh && i >= 0 && i < live;
         const int64_t at = (int64_t)start + (in ? i : 0);              // below 2 * capacity
         const int slot = (int)(at >= capacity ? at - capacity : at);
         const bool ok = in && k >= 0 && k < 8;
         uint64_t P = 0ull, O = 0ull;
-        float pv = 0.0f, pass = 0.0f, v = 0.0f;
+        float v = 0.0f;
         if (ok) {                                                       // wave-uniform
             P = mover[slot];
             O = opponent[slot];
-            const float* prow = policy + (size_t)slot * NPOL;           // capacity * NPOL: 64-bit
-            pv = lane < NSQ ? prow[lane] : 0.0f;
-            pass = prow[NSQ];
             v = value[slot];
         }
-        const uint64_t V = legal<BS>(P, O);
-        write_image<BS>(lane, P, O, V, pv, pass, ok ? k : -1, (size_t)r, out_states, out_policy,
-                        nullptr);
+        write_record<BS, 1>(lane, P, O, policy + (size_t)slot * NPOL, ok, ok ? k : -1, (size_t)r,
+                            out_states, out_policy, nullptr);           // capacity * NPOL: 64-bit
         if (lane == 0) {
             out_value[r] = v;
             out_slot[r] = in ? slot : -1;
             out_sym[r] = ok ? k : -1;
-            if (out_prob) {
-                float p = 0.0f;
-                if (in && total) {
-                    const uint64_t q = C[i] - (i ? C[i - 1] : 0ull);
-                    p = (float)((double)q / (double)total);
-                }
-                out_prob[r] = p;
-            }
+            draw.prob(r, i, in);
         }
     }
+}
+
+// What the two entry points share. RVZ_EINVAL: a bad ring or nb (at nb == 0 too), or at nb > 0 a
+// missing pointer (draw_ok: the draw's own) or out_states off 16 bytes; RVZ_OK at nb == 0; else
+// the one launch.
+template <class Draw>
+int batch(int bs, int capacity, const uint64_t* mover, const uint64_t* opponent,
+          const float* policy, const float* value, int start, int live, int nb, const int32_t* idx,
+          const int32_t* sym, typename Draw::Args draw, bool draw_ok, int random_sym, uint64_t seed,
+          uint64_t step, float* out_states, float* out_policy, float* out_value, int32_t* out_slot,
+          int32_t* out_sym, void* stream) {
+    if (!board_ok(bs) || capacity < 1 || live < 1 || live > capacity || start < 0 ||
+        start >= capacity || nb < 0)
+        return RVZ_EINVAL;
+    if ((int64_t)nb * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
+    if (nb > 0 && (!mover || !opponent || !policy || !value || !out_states || !out_policy ||
+                   !out_value || !out_slot || !out_sym || !draw_ok ||
+                   ((uintptr_t)out_states & 15u) != 0))                 // float4 stores
+        return RVZ_EINVAL;
+    if (nb == 0) return RVZ_OK;
+    const Geometry g = strided(nb, SYM_WAVES, SYM_THREADS);
+    return launch_bs(bs, k_replay_batch<8, Draw>, k_replay_batch<6, Draw>, g.grid, g.block,
+                     (hipStream_t)stream, capacity, mover, opponent, policy, value, start, live, nb,
+                     idx, sym, draw, random_sym, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (uint32_t)step, (uint32_t)(step >> 32), out_states, out_policy, out_value,
+                     out_slot, out_sym);
 }
 
 }  // namespace
@@ -264,20 +272,9 @@ extern "C" int rvz_replay_batch(int32_t bs, int32_t capacity, const uint64_t* mo
                                 uint64_t step, float* out_states, float* out_policy,
                                 float* out_value, int32_t* out_slot, int32_t* out_sym,
                                 void* stream) {
-    if (!board_ok(bs) || capacity < 1 || live < 1 || live > capacity || start < 0 ||
-        start >= capacity || nb < 0)
-        return RVZ_EINVAL;
-    if ((int64_t)nb * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
-    if (nb > 0 && (!mover || !opponent || !policy || !value || !out_states || !out_policy ||
-                   !out_value || !out_slot || !out_sym ||
-                   ((uintptr_t)out_states & 15u) != 0))                 // float4 stores
-        return RVZ_EINVAL;
-    if (nb == 0) return RVZ_OK;
-    return launch_bs(bs, k_replay_batch<8>, k_replay_batch<6>,
-                     dim3(sym_blocks_for(nb, SYM_WAVES)), dim3(SYM_THREADS), (hipStream_t)stream,
-                     capacity, mover, opponent, policy, value, start, live, nb, idx, sym,
-                     random_sym, (uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)step,
-                     (uint32_t)(step >> 32), out_states, out_policy, out_value, out_slot, out_sym);
+    return batch<UniformDraw>(bs, capacity, mover, opponent, policy, value, start, live, nb, idx,
+                              sym, {}, true, random_sym, seed, step, out_states, out_policy,
+                              out_value, out_slot, out_sym, stream);
 }
 
 extern "C" int64_t rvz_replay_cdf_size(int32_t capacity, int32_t tile_log2) {
@@ -344,19 +341,8 @@ extern "C" int rvz_replay_batch_weighted(int32_t bs, int32_t capacity, const uin
                                          float* out_states, float* out_policy, float* out_value,
                                          int32_t* out_slot, int32_t* out_sym, float* out_prob,
                                          void* stream) {
-    if (!board_ok(bs) || capacity < 1 || live < 1 || live > capacity || start < 0 ||
-        start >= capacity || nb < 0)
-        return RVZ_EINVAL;
-    if ((int64_t)nb * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
-    if (nb > 0 && (!mover || !opponent || !policy || !value || !cdf || !out_states ||
-                   !out_policy || !out_value || !out_slot || !out_sym ||
-                   ((uintptr_t)out_states & 15u) != 0 || ((uintptr_t)cdf & 15u) != 0))
-        return RVZ_EINVAL;
-    if (nb == 0) return RVZ_OK;
-    return launch_bs(bs, k_replay_batch_weighted<8>, k_replay_batch_weighted<6>,
-                     dim3(sym_blocks_for(nb, SYM_WAVES)), dim3(SYM_THREADS), (hipStream_t)stream,
-                     capacity, mover, opponent, policy, value, (const uint64_t*)cdf, start, live,
-                     nb, idx, sym, word, random_sym, (uint32_t)seed, (uint32_t)(seed >> 32),
-                     (uint32_t)step, (uint32_t)(step >> 32), out_states, out_policy, out_value,
-                     out_slot, out_sym, out_prob);
+    return batch<WeightedDraw>(bs, capacity, mover, opponent, policy, value, start, live, nb, idx,
+                               sym, {(const uint64_t*)cdf, word, out_prob},
+                               cdf && ((uintptr_t)cdf & 15u) == 0, random_sym, seed, step,
+                               out_states, out_policy, out_value, out_slot, out_sym, stream);
 }

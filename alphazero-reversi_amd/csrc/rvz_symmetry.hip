@@ -17,7 +17,7 @@
 // and no table lives in memory. Per image the wave stores the 3*S*S plane floats as float4 (48
 // lanes on 8x8, 27 on 6x6), the S*S+1 policy floats as dwords and one quirk word: 1028 B on 8x8
 // (1032 B with the quirk), 580 B (584 B) on 6x6, each byte written once. The wave's part
-// (sym_src, write_image) is in rvz_symmetry.hip.h, shared with the replay buffer's k_replay_batch.
+// (write_record, write_image) is in rvz_symmetry.hip.h, shared with the replay's k_replay_batch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(SYM_THREADS) void k_training_rows(
     const int32_t* __restrict__ status, const float* __restrict__ policy,
     const int32_t* __restrict__ sym, float* __restrict__ out_states,
     float* __restrict__ out_policy, int32_t* __restrict__ out_quirk) {
-    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    constexpr int NPOL = Geo<BS>::NPOL;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int step = gridDim.x * SYM_WAVES;
@@ -90,19 +90,8 @@ __global__ __launch_bounds__(SYM_THREADS) void k_training_rows(
         const int side = status[4 * i];
         const uint64_t b = black[i], w = white[i];
         const uint64_t P = side == 1 ? b : w, O = side == 1 ? w : b;    // as k_board_canonical
-        const uint64_t V = legal<BS>(P, O);
-        const float* prow = policy + (size_t)i * NPOL;
-        const float pv = lane < NSQ ? prow[lane] : 0.0f;
-        const float pass = prow[NSQ];
-        if constexpr (FAN == 1) {
-            write_image<BS>(lane, P, O, V, pv, pass, sym[i], (size_t)i, out_states, out_policy,
-                            out_quirk);
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                write_image<BS>(lane, P, O, V, pv, pass, k, (size_t)i * 8 + k, out_states,
-                                out_policy, out_quirk);
-        }
+        write_record<BS, FAN>(lane, P, O, policy + (size_t)i * NPOL, true, FAN == 1 ? sym[i] : 0,
+                              (size_t)i, out_states, out_policy, out_quirk);
     }
 }
 
@@ -115,8 +104,8 @@ extern "C" int rvz_board_symmetry(int32_t bs, int32_t n, const uint64_t* black,
         (n > 0 && (!black || !white || !sym || !out_black || !out_white)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    return launch_bs(bs, k_board_symmetry<8>, k_board_symmetry<6>,
-                     dim3(sym_blocks_for(n, SYM_THREADS)), dim3(SYM_THREADS),
+    const Geometry g = strided(n, SYM_THREADS, SYM_THREADS);          // one thread per board
+    return launch_bs(bs, k_board_symmetry<8>, k_board_symmetry<6>, g.grid, g.block,
                      (hipStream_t)stream, n, black, white, sym, out_black, out_white);
 }
 
@@ -130,10 +119,10 @@ extern "C" int rvz_training_rows(int32_t bs, int32_t n, const uint64_t* black,
                   (fan == 1 && !sym) || ((uintptr_t)out_states & 15u) != 0))   // float4 stores
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
+    const Geometry g = strided(n, SYM_WAVES, SYM_THREADS);            // one wavefront per row
     const auto launch = [&](auto k8, auto k6) {
-        return launch_bs(bs, k8, k6, dim3(sym_blocks_for(n, SYM_WAVES)), dim3(SYM_THREADS),
-                         (hipStream_t)stream, n, black, white, status, policy, sym, out_states,
-                         out_policy, out_quirk);
+        return launch_bs(bs, k8, k6, g.grid, g.block, (hipStream_t)stream, n, black, white,
+                         status, policy, sym, out_states, out_policy, out_quirk);
     };
     return fan == 1 ? launch(k_training_rows<8, 1>, k_training_rows<6, 1>)
                     : launch(k_training_rows<8, 8>, k_training_rows<6, 8>);

@@ -1,7 +1,8 @@
 // rvz_symmetry.hip.h — what the two kernels that write training rows from bitboards share
 // (k_training_rows in rvz_symmetry.hip, k_replay_batch in rvz_replay.hip): the source square of an
-// output square under T_k, the wave that writes one image of one row, and the launch geometry of
-// one wavefront per row. Numbering (include/rvz.h): k = 4 * f + r, T_k(x)[i][j] = x[src_k(i, j)].
+// output square under T_k, the wave that writes one image of one row and the one that writes a
+// record's rows. Device code only.
+// Numbering (include/rvz.h): k = 4 * f + r, T_k(x)[i][j] = x[src_k(i, j)].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -12,12 +13,6 @@ namespace rvz {
 
 constexpr int SYM_THREADS = 256;                 // 4 waves, one row each per step
 constexpr int SYM_WAVES = SYM_THREADS / 64;
-constexpr int SYM_MAX_BLOCKS = 2048;             // grid-stride beyond that
-
-inline int sym_blocks_for(int64_t units, int per_block) {
-    const int64_t need = (units + per_block - 1) / per_block;
-    return (int)(need < SYM_MAX_BLOCKS ? need : SYM_MAX_BLOCKS);
-}
 
 // the source square of output square s under T_k (k in [0, 8))
 template <int BS>
@@ -63,6 +58,33 @@ __device__ __forceinline__ void write_image(int lane, uint64_t P, uint64_t O, ui
     if (out_quirk) {             // wave-uniform; the image position's own mask, a direction per lane
         const uint64_t own = legal_wave<BS>(TP, TO, lane);
         if (lane == 0) out_quirk[row] = ok ? (int32_t)(own != TV) : -1;
+    }
+}
+
+// The rows of one record (P, O, its policy row prow), by the whole wave; all wave-uniform. prow
+// is read only if has_policy (else: zeros): the caller's own condition, not a null test, so no
+// caller branches twice. FAN == 1: output row `row` is the image under T_k (k outside [0, 8):
+// write_image's zero row). FAN == 8: k is not read, rows 8 * row + j are the images under T_j.
+template <int BS, int FAN>
+__device__ __forceinline__ void write_record(int lane, uint64_t P, uint64_t O,
+                                             const float* __restrict__ prow, bool has_policy,
+                                             int k, size_t row, float* __restrict__ out_states,
+                                             float* __restrict__ out_policy,
+                                             int32_t* __restrict__ out_quirk) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    const uint64_t V = legal<BS>(P, O);
+    float pv = 0.0f, pass = 0.0f;
+    if (has_policy) {                            // wave-uniform
+        pv = lane < NSQ ? prow[lane] : 0.0f;
+        pass = prow[NSQ];
+    }
+    if constexpr (FAN == 1) {
+        write_image<BS>(lane, P, O, V, pv, pass, k, row, out_states, out_policy, out_quirk);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            write_image<BS>(lane, P, O, V, pv, pass, j, row * 8 + j, out_states, out_policy,
+                            out_quirk);
     }
 }
 

@@ -35,15 +35,16 @@ Batched core:
 from ._lib import RvzError, load  # noqa: F401
 from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa: F401
                      SOLVE_NOT_A_MOVE, Engine, action_probs, alphabeta, alphabeta_weights,
-                     best_moves, board_apply, board_canonical, board_legal, board_symmetry,
-                     dirichlet_noise, merge_positions, policy_softmax, replay_batch,
-                     replay_batch_weighted, replay_cdf, solve, solve_moves, solve_moves_wld,
-                     solve_window, solve_wld, symmetry_compose, symmetry_inverse, training_rows)
+                     best_moves, board_apply, board_canonical, board_legal, dirichlet_noise,
+                     policy_softmax, solve, solve_moves, solve_moves_wld, solve_window, solve_wld)
 from .game import Board, ReversiGame  # noqa: F401
 from .loss import full_policy_loss, policy_value_loss  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)
+from .records import (board_symmetry, merge_positions, replay_batch,  # noqa: F401
+                      replay_batch_weighted, replay_cdf, symmetry_compose, symmetry_inverse,
+                      training_rows)
 from .replay import ReplayBuffer  # noqa: F401
 from .selfplay import LaneRunner, SelfPlay, SelfPlayRunner  # noqa: F401
 

@@ -215,6 +215,12 @@ def check_schedule_args(moves, late_temperature=0.0):
     return int(moves), late
 
 
+def check_board_size(board_size, who: str = "") -> None:
+    """8 or 6; who: the caller's name, where its message begins with it."""
+    if board_size not in (8, 6):
+        raise RvzError((who + ": " if who else "") + "board_size must be 8 or 6")
+
+
 def check(rc: int, handle=None, what: str = "") -> int:
     if rc < 0:
         msg = load().rvz_last_error(handle)

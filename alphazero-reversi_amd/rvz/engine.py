@@ -10,17 +10,19 @@ self-play batch are advanced in lockstep (self_play.py:80-101, mcts.py:322-694):
 
 Every tensor handed to the library is a device tensor on ``eng.device``; all work is enqueued on
 the current torch stream of that device (graph-capturable: no host syncs inside ``search``/``act``).
+
+The stateless wrappers of training records (symmetries, merging, replay) are in ``rvz.records``.
 """
 from __future__ import annotations
 
 import ctypes as C
-import numbers
 from typing import Callable, Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import RVZ_DONE, RVZ_LEAF_BF16, RVZ_LEAF_F32, RvzError, check, ptr
+from ._lib import (RVZ_DONE, RVZ_LEAF_BF16, RVZ_LEAF_F32, RvzError, check, check_board_size,
+                   ptr)
 
 U64 = 0xFFFFFFFFFFFFFFFF
 SOLVE_MAX_EMPTIES = _lib.RVZ_SOLVE_MAX_EMPTIES
@@ -577,346 +579,6 @@ def board_canonical(black: torch.Tensor, white: torch.Tensor, status: torch.Tens
     return out
 
 
-# ------------------------------------------------------------------ board symmetries
-# include/rvz.h: k = 4*f + r, T_k(x) = fliplr(rot90(x, r)) if f else rot90(x, r);
-# T_k(x)[i][j] = x[_sym_src(k, i, j, S)]
-def _sym_src(k: int, i: int, j: int, S: int):
-    if k & 4:
-        j = S - 1 - j
-    return ((i, j), (j, S - 1 - i), (S - 1 - i, S - 1 - j), (S - 1 - j, i))[k & 3]
-
-
-# each T_k as the permutation of a 3x3 board's squares (3x3 tells all eight apart)
-_SYM_PERMS = [tuple(3 * a + b for a, b in (_sym_src(k, i, j, 3) for i in range(3) for j in range(3)))
-              for k in range(8)]
-
-
-def _sym_index(k, what: str) -> int:
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= k < 8:
-        raise RvzError(f"{what}: a symmetry is an int in [0, 8), not {k!r}")
-    return int(k)
-
-
-def symmetry_compose(a: int, b: int) -> int:
-    """The symmetry c with T_c(x) == T_a(T_b(x)) for every board x (b is applied first)."""
-    a, b = _sym_index(a, "symmetry_compose"), _sym_index(b, "symmetry_compose")
-    # T_a(T_b(x))[s] = T_b(x)[src_a(s)] = x[src_b(src_a(s))]
-    return _SYM_PERMS.index(tuple(_SYM_PERMS[b][s] for s in _SYM_PERMS[a]))
-
-
-def symmetry_inverse(k: int) -> int:
-    """The symmetry c with T_c(T_k(x)) == x for every board x."""
-    k = _sym_index(k, "symmetry_inverse")
-    return next(c for c in range(8) if symmetry_compose(c, k) == 0)
-
-
-def board_symmetry(black: torch.Tensor, white: torch.Tensor, sym: torch.Tensor,
-                   board_size: int = 8):
-    """rvz_board_symmetry: the images of n boards under the eight symmetries of the square board
-    (include/rvz.h has the numbering). black / white int64 [n] (bit patterns), sym [n] integers,
-    device tensors. Returns (black', white') int64 [n]: row i transformed by T_sym[i]; both 0 for
-    a sym[i] outside [0, 8). On 6x6 input bits at or above 36 are ignored."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
-    lib = _lib.load()
-    n = black.numel()
-    if black.dim() != 1 or white.shape != (n,) or sym.shape != (n,):
-        raise RvzError("board_symmetry: black, white and sym hold one entry per board")
-    if black.dtype != torch.int64 or white.dtype != torch.int64:
-        raise RvzError("board_symmetry: black and white are int64 bit patterns")
-    if sym.dtype.is_floating_point or sym.dtype == torch.bool:
-        raise RvzError("board_symmetry: sym holds integers")
-    dev = black.device
-    b, w = black.contiguous(), white.to(dev).contiguous()
-    sy = sym.to(dev, torch.int32).contiguous()
-    ob, ow = torch.empty_like(b), torch.empty_like(w)
-    if n:
-        check(lib.rvz_board_symmetry(board_size, n, ptr(b), ptr(w), ptr(sy), ptr(ob), ptr(ow),
-                                     _lib.stream_handle(dev)), None, "rvz_board_symmetry")
-    return ob, ow
-
-
-def training_rows(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
-                  policy: torch.Tensor, sym: Optional[torch.Tensor] = None, board_size: int = 8,
-                  all_images: bool = False, quirk: bool = False):
-    """rvz_training_rows: augmented training rows straight from the bitboards. black / white
-    int64 [n], status int32 [n, 4] (only the side is read), policy float32 [n, S*S+1], device
-    tensors. all_images=False: sym [n] integers, output row i is row i's image under T_sym[i].
-    all_images=True: sym is ignored, output row 8*i + k is the image under T_k (rows [::8] are the
-    untransformed rows). Returns (states float32 [m, 3, S, S], policy float32 [m, S*S+1]) with
-    m = n or 8*n, and with quirk=True also quirk int32 [m]: 1 where the engine's own legal mask of
-    the image position differs from the image of the original's mask (the third plane is always
-    the latter), 0 where they agree, -1 for a row whose sym is outside [0, 8) (a zero row)."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
-    npol = board_size * board_size + 1
-    lib = _lib.load()
-    n = black.numel()
-    if black.dim() != 1 or white.shape != (n,) or status.shape != (n, 4):
-        raise RvzError("training_rows: black and white hold one entry per row, status is [n, 4]")
-    if black.dtype != torch.int64 or white.dtype != torch.int64:
-        raise RvzError("training_rows: black and white are int64 bit patterns")
-    if policy.shape != (n, npol) or policy.dtype != torch.float32:
-        raise RvzError(f"training_rows: policy must be float32 [n, {npol}]")
-    fan = 8 if all_images else 1
-    if n * fan * npol >= 2 ** 31:
-        raise RvzError("training_rows: n * fan * (S*S + 1) does not fit int32")
-    dev = black.device
-    sy = None
-    if not all_images:
-        if sym is None or sym.shape != (n,) or sym.dtype.is_floating_point or \
-                sym.dtype == torch.bool:
-            raise RvzError("training_rows: sym holds one integer per row (or pass all_images=True)")
-        sy = sym.to(dev, torch.int32).contiguous()
-    b, w = black.contiguous(), white.to(dev).contiguous()
-    st = status.to(dev, torch.int32).contiguous()
-    pol = policy.to(dev).contiguous()
-    states = torch.empty(n * fan, 3, board_size, board_size, dtype=torch.float32, device=dev)
-    out_p = torch.empty(n * fan, npol, dtype=torch.float32, device=dev)
-    q = torch.empty(n * fan, dtype=torch.int32, device=dev) if quirk else None
-    if n:
-        check(lib.rvz_training_rows(board_size, n, ptr(b), ptr(w), ptr(st), ptr(pol),
-                                    ptr(sy) if sy is not None else None, fan, ptr(states),
-                                    ptr(out_p), ptr(q) if quirk else None,
-                                    _lib.stream_handle(dev)), None, "rvz_training_rows")
-    return (states, out_p, q) if quirk else (states, out_p)
-
-
-def merge_positions(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor,
-                    policy: torch.Tensor, value: torch.Tensor, board_size: int = 8,
-                    table_log2: int = 0, trim: bool = True):
-    """rvz_merge_positions: one row per distinct position, carrying the mean of the targets of all
-    its occurrences. black / white int64 [n], status int32 [n, 4] (only the side is read), policy
-    float32 [n, S*S+1] in [0, 1], value float32 [n] or [n, 1] in [-1, 1], device tensors. Two rows
-    are the same position iff their (mover, opponent) bitboards are equal, so a row and its
-    colour-swapped twin merge. Returns a dict: "m" the number of distinct positions, and for the
-    m positions in order of first occurrence "first" int32 (the lowest input row of the group),
-    "count" int32 (its members), "policy" float32 [m, S*S+1] and "value" float32 [m] (the means,
-    summed in fixed point: bitwise reproducible; a group of one keeps its row's bits); "group"
-    int32 [n] maps every input row to its output row, -1 for a malformed row (overlapping discs,
-    bits off the board, a side other than 1 or 2, a target out of range or NaN), which joins no
-    group. trim=True: m is an int and the four per-position arrays are sliced to m, at the cost of
-    the function's one host read. trim=False: they are returned at length n with the rows from m
-    on unwritten, m is a 0-d int32 device tensor and nothing synchronises (with n = 0, m is 0).
-    table_log2: 0 for the default hash table, else a table of 2^table_log2 > n slots; the
-    results do not depend on it."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
-    npol = board_size * board_size + 1
-    lib = _lib.load()
-    n = black.numel()
-    if black.dim() != 1 or white.shape != (n,) or status.shape != (n, 4):
-        raise RvzError("merge_positions: black and white hold one entry per row, status is [n, 4]")
-    if black.dtype != torch.int64 or white.dtype != torch.int64:
-        raise RvzError("merge_positions: black and white are int64 bit patterns")
-    if policy.shape != (n, npol) or policy.dtype != torch.float32:
-        raise RvzError(f"merge_positions: policy must be float32 [n, {npol}]")
-    if value.shape not in ((n,), (n, 1)) or value.dtype != torch.float32:
-        raise RvzError("merge_positions: value must be float32 [n] or [n, 1]")
-    if n * npol >= 2 ** 31:
-        raise RvzError("merge_positions: n * (S*S + 1) does not fit int32")
-    if isinstance(table_log2, bool) or not isinstance(table_log2, numbers.Integral):
-        raise RvzError(f"merge_positions: table_log2 is an int, not {table_log2!r}")
-    size = lib.rvz_merge_scratch_size(board_size, n, int(table_log2))
-    if size < 0:
-        raise RvzError(f"merge_positions: table_log2 = {table_log2} must be 0 or give more than "
-                       f"n = {n} slots (at most 2^30)")
-    dev = black.device
-    b, w = black.contiguous(), white.to(dev).contiguous()
-    st = status.to(dev, torch.int32).contiguous()
-    pol = policy.to(dev).contiguous()
-    val = value.to(dev).reshape(n).contiguous()
-    m = torch.zeros((), dtype=torch.int32, device=dev)
-    first = torch.empty(n, dtype=torch.int32, device=dev)
-    count = torch.empty(n, dtype=torch.int32, device=dev)
-    out_p = torch.empty(n, npol, dtype=torch.float32, device=dev)
-    out_v = torch.empty(n, dtype=torch.float32, device=dev)
-    group = torch.empty(n, dtype=torch.int32, device=dev)
-    if n:
-        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
-        check(lib.rvz_merge_positions(board_size, n, ptr(b), ptr(w), ptr(st), ptr(pol), ptr(val),
-                                      int(table_log2), ptr(scratch), ptr(m), ptr(first),
-                                      ptr(count), ptr(out_p), ptr(out_v), ptr(group),
-                                      _lib.stream_handle(dev)), None, "rvz_merge_positions")
-    if trim:
-        m = int(m.item())
-        first, count, out_p, out_v = first[:m], count[:m], out_p[:m], out_v[:m]
-    return {"m": m, "first": first, "count": count, "policy": out_p, "value": out_v,
-            "group": group}
-
-
-def replay_batch(mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
-                 value: torch.Tensor, start: int, live: int, nb: int, seed: int, step: int,
-                 random_sym: bool = True, idx: Optional[torch.Tensor] = None,
-                 sym: Optional[torch.Tensor] = None, board_size: int = 8):
-    """rvz_replay_batch: nb training rows drawn from a ring of compact records (include/rvz.h has
-    the draw). mover / opponent int64 [capacity] (bit patterns), policy float32 [capacity, S*S+1],
-    value float32 [capacity] or [capacity, 1], device tensors; the ring's `live` rows start at
-    slot `start`, oldest first, and wrap. seed and step are integers taken mod 2^64: row r's record
-    and symmetry are a pure function of (seed, step, r). idx [nb] integers: the logical rows to
-    take instead of the draw; sym [nb] integers: the symmetries instead of the draw
-    (random_sym=False: the identity). Returns (states float32 [nb, 3, S, S], policy float32
-    [nb, S*S+1], value float32 [nb, 1], slot int32 [nb], sym int32 [nb]); a row whose given idx is
-    outside [0, live) or whose given sym is outside [0, 8) is all zero with sym -1 (and slot -1
-    for the idx)."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
-    npol = board_size * board_size + 1
-    lib = _lib.load()
-    for name, x in (("start", start), ("live", live), ("nb", nb), ("seed", seed), ("step", step)):
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
-            raise RvzError(f"replay_batch: {name} is an int, not {x!r}")
-    cap = mover.numel()
-    if mover.dim() != 1 or opponent.shape != (cap,):
-        raise RvzError("replay_batch: mover and opponent hold one entry per slot")
-    if mover.dtype != torch.int64 or opponent.dtype != torch.int64:
-        raise RvzError("replay_batch: mover and opponent are int64 bit patterns")
-    if policy.shape != (cap, npol) or policy.dtype != torch.float32:
-        raise RvzError(f"replay_batch: policy must be float32 [capacity, {npol}]")
-    if value.shape not in ((cap,), (cap, 1)) or value.dtype != torch.float32:
-        raise RvzError("replay_batch: value must be float32 [capacity] or [capacity, 1]")
-    if cap < 1 or cap >= 2 ** 31:
-        raise RvzError("replay_batch: the ring holds between 1 and 2^31 - 1 slots")
-    if not 1 <= live <= cap or not 0 <= start < cap:
-        raise RvzError(f"replay_batch: live = {live} must be in [1, {cap}] and start = {start} "
-                       f"in [0, {cap})")
-    if nb < 0 or nb * npol >= 2 ** 31:
-        raise RvzError("replay_batch: nb must be >= 0 and nb * (S*S + 1) fit int32")
-    dev = mover.device
-    given = []
-    for name, x in (("idx", idx), ("sym", sym)):
-        if x is not None and (x.shape != (nb,) or x.dtype.is_floating_point or
-                              x.dtype == torch.bool):
-            raise RvzError(f"replay_batch: {name} holds one integer per output row")
-        given.append(None if x is None else x.to(dev, torch.int32).contiguous())
-    m, o = mover.contiguous(), opponent.to(dev).contiguous()
-    pol = policy.to(dev).contiguous()
-    val = value.to(dev).reshape(cap).contiguous()
-    states = torch.empty(nb, 3, board_size, board_size, dtype=torch.float32, device=dev)
-    out_p = torch.empty(nb, npol, dtype=torch.float32, device=dev)
-    out_v = torch.empty(nb, 1, dtype=torch.float32, device=dev)
-    slot = torch.empty(nb, dtype=torch.int32, device=dev)
-    out_k = torch.empty(nb, dtype=torch.int32, device=dev)
-    if nb:
-        check(lib.rvz_replay_batch(board_size, cap, ptr(m), ptr(o), ptr(pol), ptr(val), int(start),
-                                   int(live), int(nb), ptr(given[0]), ptr(given[1]),
-                                   int(bool(random_sym)), int(seed) & (2 ** 64 - 1),
-                                   int(step) & (2 ** 64 - 1), ptr(states), ptr(out_p), ptr(out_v),
-                                   ptr(slot), ptr(out_k), _lib.stream_handle(dev)),
-              None, "rvz_replay_batch")
-    return states, out_p, out_v, slot, out_k
-
-
-def replay_cdf(weight: torch.Tensor, start: int, live: int, tile_log2: int = 0,
-               out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """rvz_replay_cdf: the table rvz.replay_batch_weighted draws from (include/rvz.h has the
-    layout). weight float32 [capacity], the ring's per-slot sampling weights, a device tensor; the
-    ring's `live` rows start at slot `start`. A weight w counts as rint(w * 2^16); one that is not
-    finite or outside [0, 65536] counts as 0 and is reported in word 1. Returns the table, int64
-    (the uint64 words' bit patterns, all below 2^63): word 0 the total, 1 the invalid weights,
-    2 start, 3 live, 4 + i the inclusive prefix sum up to logical row i; the words behind 4 + live
-    are scratch. out: an int64 device tensor of at least rvz_replay_cdf_size(capacity, tile_log2)
-    bytes to build into (a buffer kept across calls); None allocates one. tile_log2: 0, or the
-    scan's tile as a power of two in [6, 12]; the table does not depend on it. live = 0 writes
-    nothing. Asynchronous on the current stream."""
-    lib = _lib.load()
-    for name, x in (("start", start), ("live", live), ("tile_log2", tile_log2)):
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
-            raise RvzError(f"replay_cdf: {name} is an int, not {x!r}")
-    cap = weight.numel()
-    if weight.dim() != 1 or weight.dtype != torch.float32:
-        raise RvzError("replay_cdf: weight must be float32 [capacity]")
-    if cap < 1 or cap >= 2 ** 31:
-        raise RvzError("replay_cdf: the ring holds between 1 and 2^31 - 1 slots")
-    if not 0 <= live <= cap or not 0 <= start < cap:
-        raise RvzError(f"replay_cdf: live = {live} must be in [0, {cap}] and start = {start} in "
-                       f"[0, {cap})")
-    size = lib.rvz_replay_cdf_size(cap, int(tile_log2))
-    if size < 0:
-        raise RvzError(f"replay_cdf: tile_log2 = {tile_log2} must be 0 or in [6, 12]")
-    dev = weight.device
-    if out is None:
-        out = torch.empty(size // 8, dtype=torch.int64, device=dev)
-    elif out.dtype != torch.int64 or out.dim() != 1 or out.numel() * 8 < size or \
-            out.device != dev or not out.is_contiguous():
-        raise RvzError(f"replay_cdf: out must be a contiguous int64 tensor of at least {size // 8} "
-                       "words on the weights' device")
-    w = weight.contiguous()
-    check(lib.rvz_replay_cdf(cap, ptr(w), int(start), int(live), int(tile_log2), ptr(out),
-                             _lib.stream_handle(dev)), None, "rvz_replay_cdf")
-    return out
-
-
-def replay_batch_weighted(mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
-                          value: torch.Tensor, cdf: torch.Tensor, start: int, live: int, nb: int,
-                          seed: int, step: int, random_sym: bool = True,
-                          idx: Optional[torch.Tensor] = None, sym: Optional[torch.Tensor] = None,
-                          word: Optional[torch.Tensor] = None, board_size: int = 8):
-    """rvz_replay_batch_weighted: rvz.replay_batch with every row drawn in proportion to its
-    sampling weight, through the table `cdf` that rvz.replay_cdf built for the same (start, live).
-    word [nb] int64 (uint64 bit patterns): the uniform 64-bit words to draw with instead of the
-    generator's. The other arguments are replay_batch's. Returns replay_batch's five outputs and
-    prob float32 [nb], the probability q_i / total of each row taken. Row r's symmetry is
-    replay_batch's for the same (seed, step, r); its record is not, not even for equal weights.
-    Every row is a zero row (slot -1, sym -1, prob 0) when the table was built for another start
-    or live, and every drawn one when the weights' total is 0."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
-    npol = board_size * board_size + 1
-    lib = _lib.load()
-    for name, x in (("start", start), ("live", live), ("nb", nb), ("seed", seed), ("step", step)):
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
-            raise RvzError(f"replay_batch_weighted: {name} is an int, not {x!r}")
-    cap = mover.numel()
-    if mover.dim() != 1 or opponent.shape != (cap,):
-        raise RvzError("replay_batch_weighted: mover and opponent hold one entry per slot")
-    if mover.dtype != torch.int64 or opponent.dtype != torch.int64:
-        raise RvzError("replay_batch_weighted: mover and opponent are int64 bit patterns")
-    if policy.shape != (cap, npol) or policy.dtype != torch.float32:
-        raise RvzError(f"replay_batch_weighted: policy must be float32 [capacity, {npol}]")
-    if value.shape not in ((cap,), (cap, 1)) or value.dtype != torch.float32:
-        raise RvzError("replay_batch_weighted: value must be float32 [capacity] or [capacity, 1]")
-    if cap < 1 or cap >= 2 ** 31:
-        raise RvzError("replay_batch_weighted: the ring holds between 1 and 2^31 - 1 slots")
-    if not 1 <= live <= cap or not 0 <= start < cap:
-        raise RvzError(f"replay_batch_weighted: live = {live} must be in [1, {cap}] and start = "
-                       f"{start} in [0, {cap})")
-    if nb < 0 or nb * npol >= 2 ** 31:
-        raise RvzError("replay_batch_weighted: nb must be >= 0 and nb * (S*S + 1) fit int32")
-    dev = mover.device
-    if cdf.dtype != torch.int64 or cdf.dim() != 1 or cdf.numel() < 4 + live or \
-            cdf.device != dev or not cdf.is_contiguous():
-        raise RvzError("replay_batch_weighted: cdf is rvz.replay_cdf's table (contiguous int64, at "
-                       "least 4 + live words, on the ring's device)")
-    given = []
-    for name, x in (("idx", idx), ("sym", sym)):
-        if x is not None and (x.shape != (nb,) or x.dtype.is_floating_point or
-                              x.dtype == torch.bool):
-            raise RvzError(f"replay_batch_weighted: {name} holds one integer per output row")
-        given.append(None if x is None else x.to(dev, torch.int32).contiguous())
-    if word is not None and (word.shape != (nb,) or word.dtype != torch.int64):
-        raise RvzError("replay_batch_weighted: word holds one int64 (a uint64 bit pattern) per "
-                       "output row")
-    wd = None if word is None else word.to(dev).contiguous()
-    m, o = mover.contiguous(), opponent.to(dev).contiguous()
-    pol = policy.to(dev).contiguous()
-    val = value.to(dev).reshape(cap).contiguous()
-    states = torch.empty(nb, 3, board_size, board_size, dtype=torch.float32, device=dev)
-    out_p = torch.empty(nb, npol, dtype=torch.float32, device=dev)
-    out_v = torch.empty(nb, 1, dtype=torch.float32, device=dev)
-    slot = torch.empty(nb, dtype=torch.int32, device=dev)
-    out_k = torch.empty(nb, dtype=torch.int32, device=dev)
-    prob = torch.empty(nb, dtype=torch.float32, device=dev)
-    if nb:
-        check(lib.rvz_replay_batch_weighted(
-            board_size, cap, ptr(m), ptr(o), ptr(pol), ptr(val), ptr(cdf), int(start), int(live),
-            int(nb), ptr(given[0]), ptr(given[1]), ptr(wd), int(bool(random_sym)),
-            int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), ptr(states), ptr(out_p),
-            ptr(out_v), ptr(slot), ptr(out_k), ptr(prob), _lib.stream_handle(dev)),
-            None, "rvz_replay_batch_weighted")
-    return states, out_p, out_v, slot, out_k, prob
-
-
 def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor, salt: int,
                     alpha: float, board_size: int = 8, bits: bool = False):
     """rvz_dirichlet_noise: the eta rows Engine.root_noise mixes into the roots' priors, by the
@@ -925,8 +587,7 @@ def dirichlet_noise(legal: torch.Tensor, seed32: torch.Tensor, tag: torch.Tensor
     [n, S*S+1] (0 at illegal squares and at the pass index), and with bits=True also the
     attempt-0 Philox4x32-10 block of every square, int32 [n, S*S, 4] (uint32 bit patterns)."""
     _lib.check_noise_args(alpha)
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
+    check_board_size(board_size)
     lib = _lib.load()
     dev = legal.device
     lg = legal.to(torch.int64).contiguous()
@@ -954,8 +615,7 @@ def action_probs(visits: torch.Tensor, temperature, u: Optional[torch.Tensor] = 
     np.random.random_sample() would return; None: zeros). Returns (idx int32 [n], p float64
     [n, S*S+1], drew int32 [n]: 1 where the row consumed its u), device tensors. A row with a
     negative count gets idx -3 and a zero p row."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
+    check_board_size(board_size)
     npol = board_size * board_size + 1
     if visits.dim() != 2 or visits.shape[1] != npol:
         raise RvzError(f"visits must be [n, {npol}]")
@@ -1126,8 +786,7 @@ def alphabeta_weights(board_size: int = 8):
     other edge squares 10 and 5, the second ring -2, the centre -1; one legal move more than the
     opponent is worth 10. Invariant under the eight board symmetries and within
     RVZ_AB_HEUR_MAX (8x8: 928 + 64 * 10 = 1568; 6x6: 860 + 36 * 10 = 1220)."""
-    if board_size not in (6, 8):
-        raise RvzError("alphabeta_weights: board_size must be 8 or 6")
+    check_board_size(board_size, "alphabeta_weights")
     bs = int(board_size)
     fold = lambda i: min(i, bs - 1 - i)
     table = [_AB_SQUARE_CLASS[tuple(sorted((fold(s // bs), fold(s % bs))))] for s in range(bs * bs)]

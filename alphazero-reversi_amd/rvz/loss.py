@@ -37,8 +37,7 @@ def check_loss_args(logits, value, policy_targets, value_targets, weights, polic
                     value_weight, board_size) -> int:
     """The shape, dtype and weight rules of policy_value_loss, checked before any device call;
     returns n."""
-    if board_size not in (8, 6):
-        raise RvzError("board_size must be 8 or 6")
+    _lib.check_board_size(board_size)
     npol = board_size * board_size + 1
     for name, t in (("logits", logits), ("value", value), ("policy_targets", policy_targets),
                     ("value_targets", value_targets)):

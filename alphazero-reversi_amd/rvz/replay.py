@@ -21,7 +21,7 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib
-from .engine import replay_batch, replay_batch_weighted, replay_cdf
+from .records import replay_batch, replay_batch_weighted, replay_cdf
 
 
 class ReplayBuffer:

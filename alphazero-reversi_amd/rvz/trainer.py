@@ -25,9 +25,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
-                     solve_moves, solve_moves_wld, solve_wld, training_rows)
-from .engine import merge_positions as _merge_positions
+                     solve_moves, solve_moves_wld, solve_wld)
 from .loss import full_policy_loss
+from .records import merge_positions as _merge_positions, training_rows
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,

@@ -2,7 +2,8 @@
 (tests/replay_weighted_ref.py) byte for byte over its contract words, at every size where the
 tiled scan takes another path; rvz_replay_batch_weighted against the reference and against
 rvz_training_rows on the reported (slot, sym), bit for bit; the search's edges through `word`,
-given and bad idx / sym, stale and all-zero tables, purity, graph capture of table + draw,
+given and bad idx / sym (and rvz_replay_batch's own bytes for them), stale and all-zero tables,
+purity, graph capture of table + draw,
 ReplayBuffer(weighted=True) on the device against the reference-driven buffer, and one
 SelfPlayTrainer(replay_sampling="counts") iteration. Outputs are pre-filled with NaN / a sentinel
 before every raw call, so a comparison also shows that every element was written."""
@@ -14,6 +15,7 @@ import replay_ref as RR
 import replay_weighted_ref as W
 from test_gpu_replay import (PARENT_KEYS, SENTINEL, _appends, _bits, _by_training_rows, _fresh,
                              _i32, _ring)
+from test_gpu_replay import _raw as _raw_uniform
 
 pytestmark = pytest.mark.gpu
 
@@ -206,6 +208,35 @@ def test_given_and_bad_rows(bs):
     two = _raw(bs, dev, table, start, live, nb, 3, 4, sym=_i32(sym))
     _same(two, W.batch(*host, ref_table, start, live, nb, 3, 4, True, None, sym, None, bs))
     assert int((two[4] == -1).sum()) == 3 and int((two[3] == -1).sum()) == 0
+
+
+@pytest.mark.parametrize("nb", [1, 5])
+@pytest.mark.parametrize("live", [7, 4])
+@pytest.mark.parametrize("bs", [8, 6])
+def test_given_rows_are_the_uniform_entry_points_rows(bs, live, nb):
+    """One kernel behind both entry points: with idx and sym given (one idx outside [0, live),
+    one sym outside [0, 8)) and a table for the same (start, live), the five common outputs are
+    rvz_replay_batch's bit for bit; with a table built for another start every row is the zero
+    row. Capacity 7 from slot 5: the rows wrap; nb = 5 is one block of four waves and one more."""
+    cap, start = 7, 5
+    _, dev = _ring(bs, cap, 11, odd_values=True)
+    w = np.array([3, 0.5, 0, 1, 65536, 2.0 ** -17, 7], np.float32)
+    idx = _i32(np.array([live - 1, 0, live, 2, 3], np.int32)[:nb])
+    sym = _i32(np.array([7, 8, 2, 5, 0], np.int32)[:nb])
+    if nb == 1:                                               # the row that wraps the furthest
+        idx, sym = _i32([live - 1]), _i32([3])
+    want = _raw_uniform(bs, dev, start, live, nb, 9, 2, idx=idx, sym=sym)
+    got = _raw(bs, dev, _table(w, start, live), start, live, nb, 9, 2, idx=idx, sym=sym)
+    for g, x, name in zip(got, want, NAMES):
+        assert g.dtype == x.dtype and torch.equal(_bits(g), _bits(x)), name
+    assert not bool(torch.isnan(got[5]).any())
+    if nb == 5:
+        assert got[3].tolist()[1:3] == [5, -1] and got[4].tolist()[1:3] == [-1, -1]
+        assert bool(got[0][0].any()) and not bool(got[0][1:3].any())
+    stale = _raw(bs, dev, _table(w, start - 1, live), start, live, nb, 9, 2, idx=idx, sym=sym)
+    for t in stale[:3] + stale[5:]:
+        assert torch.equal(_bits(t), torch.zeros_like(_bits(t)))
+    assert set(stale[3].tolist()) == {-1} and set(stale[4].tolist()) == {-1}
 
 
 # ---------------------------------------------------------------- errors and robustness
