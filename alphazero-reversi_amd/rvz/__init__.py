@@ -28,6 +28,10 @@ Batched core:
                             ReplayBuffer(weighted=True), a table of integer prefix sums
                             (rvz_replay_cdf) and the search through it
                             (rvz_replay_batch_weighted)
+    replay_priority, replay_is_weight   prioritized replay: a trained batch's losses written
+                            back as the rows' sampling weights (rvz_replay_priority) and the
+                            importance weights of a drawn batch (rvz_replay_is_weight):
+                            ReplayBuffer(prioritized=True)
     policy_value_loss, full_policy_loss   the loss on the full policy target, weighted per row,
                             with its gradients in one deterministic float64 call
                             (rvz_policy_value_loss), and its differentiable torch form
@@ -43,8 +47,8 @@ from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)
 from .records import (board_symmetry, merge_positions, replay_batch,  # noqa: F401
-                      replay_batch_weighted, replay_cdf, symmetry_compose, symmetry_inverse,
-                      training_rows)
+                      replay_batch_weighted, replay_cdf, replay_is_weight, replay_priority,
+                      symmetry_compose, symmetry_inverse, training_rows)
 from .replay import ReplayBuffer  # noqa: F401
 from .selfplay import LaneRunner, SelfPlay, SelfPlayRunner  # noqa: F401
 

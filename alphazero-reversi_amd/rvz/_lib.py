@@ -110,6 +110,12 @@ SIGNATURES = {
     "rvz_replay_batch_weighted": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                             C.c_int32, C.c_int32, _P, _P, _P, C.c_int32,
                                             C.c_uint64, C.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
+    "rvz_replay_is_weight_scratch_size": (C.c_int64, [C.c_int32]),
+    "rvz_replay_is_weight": (C.c_int, [C.c_int32, _P, _P, C.c_double, _P, _P, _P, _P]),
+    "rvz_replay_priority_scratch_size": (C.c_int64, [C.c_int32]),
+    "rvz_replay_priority": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_double,
+                                      C.c_int32, C.c_double, C.c_double, C.c_double, _P, _P, _P,
+                                      _P, _P]),
     "rvz_loss_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_policy_value_loss": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_double,
                                         C.c_double, _P, _P, _P, _P, _P, _P]),

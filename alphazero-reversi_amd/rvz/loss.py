@@ -112,8 +112,8 @@ def policy_value_loss(logits: torch.Tensor, value: torch.Tensor, policy_targets:
 
 class _Loss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, value, kernel, args):
-        out = kernel(logits.detach(), value.detach(), *args, rows=False, grads=True)
+    def forward(ctx, logits, value, kernel, args, rows=False):
+        out = kernel(logits.detach(), value.detach(), *args, rows=rows, grads=True)
         ctx.save_for_backward(out["grad_logits"], out["grad_value"])
         ctx.shapes = (logits.shape, value.shape)
         return out["loss"].to(logits.dtype)
@@ -122,24 +122,27 @@ class _Loss(torch.autograd.Function):
     def backward(ctx, grad_output):
         gl, gv = ctx.saved_tensors
         g = grad_output.to(gl.dtype)
-        return (g * gl).reshape(ctx.shapes[0]), (g * gv).reshape(ctx.shapes[1]), None, None
+        return (g * gl).reshape(ctx.shapes[0]), (g * gv).reshape(ctx.shapes[1]), None, None, None
 
 
 def differentiable(kernel):
     """A function of full_policy_loss's signature around any `kernel` of policy_value_loss's
-    signature and results (tests on a host without a GPU wrap the NumPy reference)."""
+    signature and results (tests on a host without a GPU wrap the NumPy reference). rows=True:
+    the kernel is asked for its per-row output and stats["rows"] holds it."""
     def loss_fn(logits, value, policy_targets, value_targets, weights=None, policy_weight=1.0,
-                value_weight=1.0, board_size=8):
+                value_weight=1.0, board_size=8, rows: bool = False):
         holder = {}
 
         def call(*a, **k):
             holder["out"] = kernel(*a, **k)
             return holder["out"]
-        loss = _Loss.apply(logits, value, call,
-                           (policy_targets, value_targets, weights, policy_weight, value_weight,
-                            board_size))
+        args = (policy_targets, value_targets, weights, policy_weight, value_weight, board_size)
+        loss = (_Loss.apply(logits, value, call, args, True) if rows else
+                _Loss.apply(logits, value, call, args))
         out = holder["out"]
         stats = {k: out[k] for k in ("target_entropy", "agreement", "weight_sum", "malformed")}
+        if rows:
+            stats["rows"] = out["rows"]
         return loss, out["policy_loss"], out["value_loss"], stats
     return loss_fn
 
@@ -149,13 +152,18 @@ _full = differentiable(policy_value_loss)
 
 def full_policy_loss(logits: torch.Tensor, value: torch.Tensor, policy_targets: torch.Tensor,
                      value_targets: torch.Tensor, weights: Optional[torch.Tensor] = None,
-                     policy_weight: float = 1.0, value_weight: float = 1.0, board_size: int = 8):
+                     policy_weight: float = 1.0, value_weight: float = 1.0, board_size: int = 8,
+                     rows: bool = False):
     """policy_value_loss as a differentiable torch function (one rvz_policy_value_loss call in
     the forward, which also computes the gradients; the backward multiplies the saved gradients
     by the upstream factor). Returns (loss, policy_loss, value_loss, stats): loss a 0-d tensor of
     logits' dtype, differentiable with respect to logits and value; policy_loss and value_loss
     the weighted means P and V, 0-d float64; stats the 0-d float64 device tensors
-    "target_entropy", "agreement", "weight_sum" and "malformed". Nothing synchronises with the
-    host."""
+    "target_entropy", "agreement", "weight_sum" and "malformed", and with rows=True "rows", the
+    float64 [n, 3] tensor of each row's {Lp, Lv, H} (what rvz.replay_priority reads). Nothing
+    synchronises with the host."""
+    if rows:
+        return _full(logits, value, policy_targets, value_targets, weights, policy_weight,
+                     value_weight, board_size, rows=True)
     return _full(logits, value, policy_targets, value_targets, weights, policy_weight,
                  value_weight, board_size)

@@ -50,7 +50,8 @@ class SelfPlayTrainer:
                  replay_iterations: int = 0, replay_capacity: Optional[int] = None,
                  replay_steps: Optional[int] = None, replay_symmetries: bool = True,
                  policy_target: str = "argmax", count_weights: bool = False,
-                 replay_sampling: str = "uniform", replay_recency_decay: float = 1.0):
+                 replay_sampling: str = "uniform", replay_recency_decay: float = 1.0,
+                 replay_priority_alpha: float = 0.6, replay_priority_beta=0.4):
         """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
@@ -112,7 +113,21 @@ class SelfPlayTrainer:
         merge_positions=True, ValueError otherwise. The sampling then carries the counts, so
         with policy_target="full" every drawn row weighs 1 in the loss. replay_recency_decay: d in
         (0, 1]: a held row's sampling weight is multiplied by d with every newer iteration
-        appended, under either replay_sampling; a d other than 1 needs replay_iterations > 0.
+        appended, under any replay_sampling; a d other than 1 needs replay_iterations > 0.
+        replay_sampling="priority": prioritized replay (Schaul et al. 2016; ReplayBuffer(
+        prioritized=True); the rvz_replay_priority / rvz_replay_is_weight HIP kernels). An
+        iteration's rows enter the buffer at the running maximum priority, every training step
+        draws in proportion to the priorities, weighs each drawn row by its importance weight
+        (pmin / prob) ** beta in the loss, and writes the step's per-row losses back as the rows'
+        new priorities, so training dwells on the positions the net currently gets most wrong
+        with the sampling bias corrected. It needs replay_iterations > 0 and policy_target="full"
+        (the weights and the per-row losses are that loss's), ValueError otherwise.
+        replay_priority_alpha in [0, 1]: the exponent of the priorities (0: uniform).
+        replay_priority_beta: the exponent of the importance weights, a float in [0, 1] or
+        (start, end, iterations): linear in the iteration number from start to end over
+        `iterations` iterations, then end. run_iteration then also reports
+        replay_priority_max, the running maximum priority after the iteration (in this mode
+        alone: the other modes' result keeps its keys).
         policy_target: "argmax" (the default: the reference's criterion) or "full": the trainer's
         loss is AlphaZero's own -pi . log p on the whole policy target (DDPTrainer;
         rvz.full_policy_loss, the rvz_policy_value_loss HIP kernels), so a merged row's mean
@@ -137,9 +152,36 @@ class SelfPlayTrainer:
         if count_weights and replay_iterations:
             raise ValueError("count_weights=True needs replay_iterations=0: the replay ring "
                              "stores no position counts")
-        if replay_sampling not in ("uniform", "counts"):
-            raise ValueError("replay_sampling must be 'uniform' or 'counts', not "
+        if replay_sampling not in ("uniform", "counts", "priority"):
+            raise ValueError("replay_sampling must be 'uniform', 'counts' or 'priority', not "
                              f"{replay_sampling!r}")
+        if replay_sampling == "priority" and not replay_iterations:
+            raise ValueError("replay_sampling='priority' needs replay_iterations > 0: it is the "
+                             "replay buffer's draw")
+        if replay_sampling == "priority" and policy_target != "full":
+            raise ValueError("replay_sampling='priority' needs policy_target='full': the "
+                             "importance weights and the per-row losses are that loss's")
+        if replay_sampling != "priority" and (replay_priority_alpha != 0.6 or
+                                              replay_priority_beta != 0.4):
+            raise ValueError("replay_priority_alpha and replay_priority_beta need "
+                             "replay_sampling='priority'")
+        def _unit(x):
+            return not isinstance(x, bool) and isinstance(x, numbers.Real) and 0.0 <= x <= 1.0
+        if not _unit(replay_priority_alpha):
+            raise ValueError("replay_priority_alpha must be in [0, 1], not "
+                             f"{replay_priority_alpha!r}")
+        beta = replay_priority_beta
+        if isinstance(beta, (tuple, list)):
+            if len(beta) != 3 or not _unit(beta[0]) or not _unit(beta[1]) or \
+                    isinstance(beta[2], bool) or not isinstance(beta[2], numbers.Integral) or \
+                    beta[2] < 1:
+                raise ValueError("replay_priority_beta must be a float in [0, 1] or (start, end, "
+                                 f"iterations >= 1) with both ends in [0, 1], not {beta!r}")
+            beta = (float(beta[0]), float(beta[1]), int(beta[2]))
+        elif not _unit(beta):
+            raise ValueError("replay_priority_beta must be a float in [0, 1] or (start, end, "
+                             f"iterations), not {beta!r}")
+        self.replay_priority_beta = beta
         if replay_sampling == "counts" and not replay_iterations:
             raise ValueError("replay_sampling='counts' needs replay_iterations > 0: it is the "
                              "replay buffer's draw")
@@ -223,11 +265,15 @@ class SelfPlayTrainer:
             if replay_capacity is None:
                 replay_capacity = self.replay_iterations * self.games * self.max_plies
             weighted = self.replay_sampling == "counts" or self.replay_recency_decay != 1.0
+            priority = ({"prioritized": True, "priority_alpha": float(replay_priority_alpha),
+                         "recency_decay": self.replay_recency_decay}
+                        if self.replay_sampling == "priority" else {})
             self.buffer = ReplayBuffer(int(replay_capacity), bs, self.device,
                                        window_iterations=self.replay_iterations,
-                                       **({"weighted": True,
-                                           "recency_decay": self.replay_recency_decay}
-                                          if weighted else {}))
+                                       **(priority or
+                                          ({"weighted": True,
+                                            "recency_decay": self.replay_recency_decay}
+                                           if weighted else {})))
         self.iteration = 0
 
     def _seeds(self):
@@ -298,9 +344,19 @@ class SelfPlayTrainer:
         out.update(stats)
         return out
 
+    def priority_beta(self, iteration: Optional[int] = None) -> float:
+        """replay_priority_beta at `iteration` (default: the current one)."""
+        beta = self.replay_priority_beta
+        if not isinstance(beta, tuple):
+            return float(beta)
+        it = self.iteration if iteration is None else int(iteration)
+        start, end, n = beta
+        return end if it >= n else start + (end - start) * it / n
+
     def _append(self, data: Dict[str, torch.Tensor]) -> None:
         """The iteration's compact rows into the replay buffer; with replay_sampling="counts" each
-        merged row's position_counts is its sampling weight."""
+        merged row's position_counts is its sampling weight (with "priority" the buffer gives the
+        rows its running maximum priority)."""
         counts = ({"weight": data["position_counts"].to(torch.float32)}
                   if self.replay_sampling == "counts" else {})
         self.buffer.append(data["mover"], data["opponent"], data["policy_targets"],
@@ -317,8 +373,10 @@ class SelfPlayTrainer:
                 steps = -(-data["mover"].shape[0] // self.trainer.batch_size)
             if self.train_steps is not None:
                 steps = min(steps, self.train_steps)
+            beta = ({"priority_beta": self.priority_beta()}
+                    if self.replay_sampling == "priority" else {})
             out = self.trainer.train_replay(self.buffer, steps, seed=self.seed + self.iteration,
-                                            symmetries=self.replay_symmetries)
+                                            symmetries=self.replay_symmetries, **beta)
         else:
             out = self.trainer.train_epoch(data, seed=self.seed + self.iteration,
                                            max_steps=self.train_steps, local_data=True)
@@ -358,4 +416,6 @@ class SelfPlayTrainer:
                     "replay_rows": len(self.buffer) if self.buffer is not None else 0,
                     "replay_iterations_held": (len(self.buffer.rows_by_iteration())
                                                if self.buffer is not None else 0)})
+        if self.replay_sampling == "priority":
+            out["replay_priority_max"] = self.buffer.max_priority()
         return out

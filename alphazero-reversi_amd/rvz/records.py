@@ -68,6 +68,18 @@ def _i32(x: Optional[torch.Tensor], dev) -> Optional[torch.Tensor]:
     return None if x is None else x.to(dev, torch.int32).contiguous()
 
 
+def _addr(t: Optional[torch.Tensor]):
+    """Device address of a contiguous device tensor that a kernel reads and writes in single
+    elements (ptr() also asks for the 16-byte alignment of vector accesses)."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RvzError("rvz buffers must be device tensors (no host fallback)")
+    if not t.is_contiguous():
+        raise RvzError("rvz buffers must be contiguous")
+    return t.data_ptr()
+
+
 # ------------------------------------------------------------------ board symmetries
 # include/rvz.h: k = 4*f + r, T_k(x) = fliplr(rot90(x, r)) if f else rot90(x, r);
 # T_k(x)[i][j] = x[_sym_src(k, i, j, S)]
@@ -325,3 +337,127 @@ def replay_batch_weighted(mover: torch.Tensor, opponent: torch.Tensor, policy: t
             *map(ptr, given), ptr(wd), int(bool(random_sym)), int(seed) & _U64, int(step) & _U64,
             *map(ptr, out), ptr(prob), _lib.stream_handle(dev)), None, "rvz_replay_batch_weighted")
     return (*out, prob)
+
+
+# ------------------------------------------------------------------ prioritized replay
+PRIORITY_MIN_FLOOR, PRIORITY_MAX_CAP = 2.0 ** -16, 65536.0
+
+
+def _number(who: str, name: str, x, lo: float, hi: float, closed_hi: bool = True) -> float:
+    """A real number (not a bool) in [lo, hi] (or [lo, hi)); NaN fails."""
+    if isinstance(x, bool) or not isinstance(x, numbers.Real) or \
+            not (lo <= float(x) <= hi if closed_hi else lo <= float(x) < hi):
+        raise RvzError(f"{who}: {name} must be a number in [{lo}, {hi}{']' if closed_hi else ')'}"
+                       f", not {x!r}")
+    return float(x)
+
+
+def check_is_weight_args(prob, slot, beta, who: str = "replay_is_weight") -> int:
+    """The argument rules of replay_is_weight, checked before any device call (the CPU tests'
+    NumPy restatement calls it too); returns nb."""
+    if not isinstance(prob, torch.Tensor) or prob.dim() != 1 or prob.dtype != torch.float32:
+        raise RvzError(f"{who}: prob must be float32 [nb]")
+    nb = prob.numel()
+    if not isinstance(slot, torch.Tensor):
+        raise RvzError(f"{who}: slot holds one integer per drawn row")
+    _given(who, nb, "drawn row", optional=False, slot=slot)
+    _number(who, "beta", beta, 0.0, 1.0)
+    return nb
+
+
+def check_priority_args(weight, slot, rows, policy_coef=1.0, value_coef=1.0,
+                        subtract_entropy=True, alpha=0.6, floor=2.0 ** -8, cap=2.0 ** 8,
+                        max_priority=None, who: str = "replay_priority") -> int:
+    """The argument rules of replay_priority, checked before any device call (the CPU tests'
+    NumPy restatement calls it too); returns nb."""
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 1 or \
+            weight.dtype != torch.float32 or not weight.is_contiguous() or \
+            not 1 <= weight.numel() < 2 ** 31:
+        raise RvzError(f"{who}: weight must be a contiguous float32 [capacity] (it is written in "
+                       "place), 1 <= capacity < 2^31")
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] != 3 or \
+            rows.dtype != torch.float64:
+        raise RvzError(f"{who}: rows must be float64 [nb, 3], the loss's per-row "
+                       "{Lp, Lv, H}")
+    nb = rows.shape[0]
+    if nb > 2 ** 30:
+        raise RvzError(f"{who}: nb must be at most 2^30")
+    if not isinstance(slot, torch.Tensor):
+        raise RvzError(f"{who}: slot holds one integer per row of rows")
+    _given(who, nb, "row of rows", optional=False, slot=slot)
+    for name, x in (("policy_coef", policy_coef), ("value_coef", value_coef)):
+        _number(who, name, x, 0.0, float("inf"), closed_hi=False)
+    if not isinstance(subtract_entropy, numbers.Integral):      # a bool is one
+        raise RvzError(f"{who}: subtract_entropy is a bool, not {subtract_entropy!r}")
+    _number(who, "alpha", alpha, 0.0, 1.0)
+    lo = _number(who, "floor", floor, PRIORITY_MIN_FLOOR, PRIORITY_MAX_CAP)
+    hi = _number(who, "cap", cap, PRIORITY_MIN_FLOOR, PRIORITY_MAX_CAP)
+    if lo > hi:
+        raise RvzError(f"{who}: floor = {floor!r} must not exceed cap = {cap!r}")
+    if max_priority is not None and (not isinstance(max_priority, torch.Tensor) or
+                                     max_priority.numel() != 1 or
+                                     max_priority.dtype != torch.float32 or
+                                     max_priority.device != weight.device):
+        raise RvzError(f"{who}: max_priority is None or one float32 on the weights' device (it "
+                       "is updated in place)")
+    return nb
+
+
+def replay_is_weight(prob: torch.Tensor, slot: torch.Tensor, beta: float,
+                     with_min: bool = False):
+    """rvz_replay_is_weight: the importance-sampling weights of a drawn batch (include/rvz.h has
+    the definition). prob float32 [nb] and slot [nb] integers: replay_batch_weighted's prob and
+    slot, device tensors; beta in [0, 1]. Returns weight float32 [nb]: (pmin / prob[r]) ** beta in
+    float64 with the correctly rounded power, pmin the smallest probability among the valid rows
+    (slot >= 0, prob finite and > 0), so every weight is in (0, 1] and the rarest row weighs 1;
+    0 for any other row. with_min=True: (weight, min_prob), min_prob float32 [1] holding pmin (0
+    with no valid row). Asynchronous on the current stream; nothing synchronises."""
+    nb = check_is_weight_args(prob, slot, beta)
+    lib = _lib.load()
+    dev = prob.device
+    pr, sl = prob.contiguous(), _i32(slot, dev)
+    out = torch.empty(nb, dtype=torch.float32, device=dev)
+    pmin = torch.zeros(1, dtype=torch.float32, device=dev)
+    if nb:
+        scratch = torch.empty(lib.rvz_replay_is_weight_scratch_size(nb), dtype=torch.uint8,
+                              device=dev)
+        check(lib.rvz_replay_is_weight(nb, _addr(pr), _addr(sl), float(beta), ptr(scratch),
+                                       _addr(out), _addr(pmin), _lib.stream_handle(dev)), None,
+              "rvz_replay_is_weight")
+    return (out, pmin) if with_min else out
+
+
+def replay_priority(weight: torch.Tensor, slot: torch.Tensor, rows: torch.Tensor,
+                    policy_coef: float = 1.0, value_coef: float = 1.0,
+                    subtract_entropy: bool = True, alpha: float = 0.6, floor: float = 2.0 ** -8,
+                    cap: float = 2.0 ** 8, max_priority: Optional[torch.Tensor] = None):
+    """rvz_replay_priority: a batch's loss rows written into the ring's sampling weights
+    (include/rvz.h has the definition). weight float32 [capacity], contiguous, written in place;
+    slot [nb] integers, the batch's slots (replay_batch_weighted's); rows float64 [nb, 3],
+    policy_value_loss's "rows" {Lp, Lv, H}; device tensors. A valid row's priority is
+    min(cap, max(floor, (policy_coef * k + value_coef * Lv) ** alpha)) as float32, k = max(Lp - H,
+    0) with subtract_entropy (the policy's KL divergence from its target) or Lp without; where
+    several valid rows name one slot the last one's priority is written, and a slot no valid row
+    names keeps its bytes. max_priority: None, or one float32 on the device, raised in place to
+    the largest priority of the valid rows. Returns (priority float32 [nb], 0 for an invalid row;
+    state int32 [nb]: 1 written, 0 superseded by a later row, -1 invalid). No append may have
+    overwritten the batch's slots since the draw. The table of prefix sums is not updated: rebuild
+    it (replay_cdf) before the next draw. Asynchronous on the current stream; nothing
+    synchronises."""
+    nb = check_priority_args(weight, slot, rows, policy_coef, value_coef, subtract_entropy, alpha,
+                             floor, cap, max_priority)
+    lib = _lib.load()
+    dev = weight.device
+    sl, rw = _i32(slot, dev), rows.to(dev).contiguous()
+    pri = torch.zeros(nb, dtype=torch.float32, device=dev)
+    state = torch.full((nb,), -1, dtype=torch.int32, device=dev)
+    if nb:
+        scratch = torch.empty(lib.rvz_replay_priority_scratch_size(nb), dtype=torch.uint8,
+                              device=dev)
+        check(lib.rvz_replay_priority(weight.numel(), _addr(weight), nb, _addr(sl), _addr(rw),
+                                      float(policy_coef), float(value_coef),
+                                      int(bool(subtract_entropy)), float(alpha), float(floor),
+                                      float(cap), ptr(scratch), _addr(max_priority), _addr(pri),
+                                      _addr(state), _lib.stream_handle(dev)), None,
+              "rvz_replay_priority")
+    return pri, state

@@ -12,6 +12,12 @@ straight from the bitboards, no host randomness.
 a priority) and a recency decay, and draws rows in proportion to their weights: a table of integer
 prefix sums built on the device after each append (``rvz.replay_cdf`` / rvz_replay_cdf) and one
 kernel that draws through it (``rvz.replay_batch_weighted`` / rvz_replay_batch_weighted).
+
+``ReplayBuffer(prioritized=True)`` is the prioritized replay of Schaul et al. (2016) on top of
+that: new rows enter at the running maximum priority, ``update_priorities`` writes a trained
+batch's losses back as the rows' weights (``rvz.replay_priority`` / rvz_replay_priority) and
+``is_weights`` corrects the sampling bias in the loss (``rvz.replay_is_weight`` /
+rvz_replay_is_weight).
 """
 from __future__ import annotations
 
@@ -21,13 +27,18 @@ from typing import List, Optional, Tuple
 import torch
 
 from . import _lib
-from .records import replay_batch, replay_batch_weighted, replay_cdf
+from ._lib import RvzError
+from .records import (check_priority_args, replay_batch, replay_batch_weighted, replay_cdf,
+                      replay_is_weight, replay_priority)
 
 
 class ReplayBuffer:
     def __init__(self, capacity: int, board_size: int = 8, device=None,
                  window_iterations: int = 0, batcher=None, weighted: bool = False,
-                 recency_decay: float = 1.0, weighted_batcher=None, cdf_builder=None):
+                 recency_decay: float = 1.0, weighted_batcher=None, cdf_builder=None,
+                 prioritized: bool = False, priority_alpha: float = 0.6,
+                 priority_floor: float = 2.0 ** -8, priority_cap: float = 2.0 ** 8,
+                 subtract_entropy: bool = True, priority_updater=None, is_weighter=None):
         """capacity: the ring's rows. window_iterations = K > 0: an append of iteration t also
         drops every row of an iteration before t - K + 1 (0: rows leave only when overwritten).
         batcher(mover, opponent, policy, value, start, live, nb, seed, step, random_sym, idx, sym,
@@ -49,7 +60,24 @@ class ReplayBuffer:
         rvz.replay_cdf. weighted_batcher(mover, opponent, policy, value, cdf, start, live, nb,
         seed, step, random_sym, idx, sym, word, board_size) -> batcher's five outputs and prob
         [nb]: default rvz.replay_batch_weighted. total_weight() and invalid_weights() read the
-        table's first two words: the only host synchronisations."""
+        table's first two words: the only host synchronisations.
+        prioritized=True (implies weighted): the weights are priorities driven by the training
+        loss. An append without `weight` gives its rows the running maximum priority (one float32
+        on the device, 1.0 at first, broadcast into the slice without a host synchronisation), so
+        a new row is drawn at least as readily as any held row until it has been trained on once;
+        an explicit `weight` still wins. update_priorities(slot, rows) then writes
+        min(priority_cap, max(priority_floor, e ** priority_alpha)) into the slots of a trained
+        batch, e = policy_coef * k + value_coef * Lv of the batch's loss rows, k the policy's KL
+        divergence from its target with subtract_entropy (the default: the cross-entropy Lp alone
+        can never reach 0 on a high-entropy target and would favour opening rows for ever), Lp
+        without. priority_alpha = 0.6 is the value of Schaul et al. (0: uniform sampling);
+        priority_floor = 2^-8 and priority_cap = 2^8 are choices, not measurements: a span of
+        2^16 between the rarest and the commonest held row, inside the fixed point's [2^-16, 2^16].
+        recency_decay multiplies the held weights as before and leaves the running maximum alone.
+        priority_updater(weight, slot, rows, policy_coef, value_coef, subtract_entropy, alpha,
+        floor, cap, max_priority) -> (priority, state), writing weight and max_priority in place:
+        default rvz.replay_priority. is_weighter(prob, slot, beta) -> weight: default
+        rvz.replay_is_weight."""
         for name, x in (("capacity", capacity), ("window_iterations", window_iterations)):
             if isinstance(x, bool) or not isinstance(x, numbers.Integral):
                 raise ValueError(f"ReplayBuffer: {name} is an int, not {x!r}")
@@ -63,7 +91,14 @@ class ReplayBuffer:
         self.window_iterations = int(window_iterations)
         self.device = torch.device("cuda" if device is None else device)
         self.batcher = replay_batch if batcher is None else batcher
-        self.weighted = bool(weighted)
+        self.prioritized = bool(prioritized)
+        self.weighted = bool(weighted) or self.prioritized
+        if not self.prioritized and (priority_updater is not None or is_weighter is not None or
+                                     (priority_alpha, priority_floor, priority_cap) !=
+                                     (0.6, 2.0 ** -8, 2.0 ** 8) or subtract_entropy is not True):
+            raise ValueError("ReplayBuffer: priority_alpha, priority_floor, priority_cap, "
+                             "subtract_entropy, priority_updater and is_weighter need "
+                             "prioritized=True")
         if not self.weighted and (recency_decay != 1.0 or weighted_batcher is not None or
                                   cdf_builder is not None):
             raise ValueError("ReplayBuffer: recency_decay, weighted_batcher and cdf_builder need "
@@ -90,6 +125,21 @@ class ReplayBuffer:
             words = _lib.load().rvz_replay_cdf_size(self.capacity, 0) // 8
             self._cdf = torch.zeros(words, dtype=torch.int64, device=self.device)
             self._dirty = True
+        if self.prioritized:
+            try:                        # the rules of rvz.replay_priority, on an empty batch
+                check_priority_args(self.weight, torch.zeros(0, dtype=torch.int32),
+                                    torch.zeros(0, 3, dtype=torch.float64), 1.0, 1.0,
+                                    subtract_entropy, priority_alpha, priority_floor,
+                                    priority_cap, who="ReplayBuffer")
+            except RvzError as err:
+                raise ValueError(str(err)) from None
+            self.priority_alpha = float(priority_alpha)
+            self.priority_floor, self.priority_cap = float(priority_floor), float(priority_cap)
+            self.subtract_entropy = bool(subtract_entropy)
+            self.priority_updater = replay_priority if priority_updater is None \
+                else priority_updater
+            self.is_weighter = replay_is_weight if is_weighter is None else is_weighter
+            self._max_priority = torch.ones(1, dtype=torch.float32, device=self.device)
 
     def __len__(self) -> int:
         return self._live
@@ -115,7 +165,7 @@ class ReplayBuffer:
         tensor), over the oldest rows once the ring is full. mover / opponent int64 [n], policy
         float32 [n, S*S+1], value float32 [n] or [n, 1]. Iterations are appended in
         non-decreasing order. weight (weighted=True only): float32 [n], the rows' sampling
-        weights; None: 1.0 each."""
+        weights; None: 1.0 each (prioritized=True: the running maximum priority each)."""
         if isinstance(iteration, bool) or not isinstance(iteration, numbers.Integral):
             raise ValueError(f"ReplayBuffer.append: iteration is an int, not {iteration!r}")
         n = mover.numel()
@@ -149,7 +199,9 @@ class ReplayBuffer:
                     # they are never read)
                     factor = self.recency_decay ** (int(iteration) - self._ledger[-1][0])
                     self.weight.mul_(torch.tensor(factor, dtype=torch.float32).item())
-                if weight is None:
+                if weight is None and self.prioritized:
+                    weight = self._max_priority.expand(n)       # read on the device
+                elif weight is None:
                     weight = torch.ones(n, dtype=torch.float32, device=self.device)
                 fields.append((self.weight, weight))
                 self._dirty = True
@@ -218,3 +270,35 @@ class ReplayBuffer:
         if not self.weighted:
             raise ValueError("ReplayBuffer.invalid_weights needs ReplayBuffer(weighted=True)")
         return int(self._table()[1].item()) if self._live else 0
+
+    def _need_priorities(self, who: str) -> None:
+        if not self.prioritized:
+            raise ValueError(f"ReplayBuffer.{who} needs ReplayBuffer(prioritized=True)")
+
+    def update_priorities(self, slot: torch.Tensor, rows: torch.Tensor, policy_coef: float = 1.0,
+                          value_coef: float = 1.0):
+        """A trained batch's losses as its rows' new sampling weights: slot [nb] the batch's
+        slots (sample's fourth output), rows float64 [nb, 3] its loss rows {Lp, Lv, H}
+        (full_policy_loss(rows=True)'s stats["rows"]), policy_coef / value_coef the loss's own
+        weights. Where a slot was drawn more than once the last row's priority is written; a
+        row with slot -1 or a non-finite loss writes nothing. Raises the running maximum and
+        marks the table stale (the next sample rebuilds it). No append may have come between the
+        draw and this call. Returns (priority float32 [nb], state int32 [nb]: 1 written, 0
+        superseded, -1 invalid). Nothing synchronises."""
+        self._need_priorities("update_priorities")
+        out = self.priority_updater(self.weight, slot, rows, policy_coef, value_coef,
+                                    self.subtract_entropy, self.priority_alpha,
+                                    self.priority_floor, self.priority_cap, self._max_priority)
+        self._dirty = True
+        return out
+
+    def is_weights(self, prob: torch.Tensor, slot: torch.Tensor, beta: float) -> torch.Tensor:
+        """The importance-sampling weights of a drawn batch, float32 [nb]: (pmin / prob) ** beta,
+        1 at the rarest drawn row, 0 at a zero row (sample(with_prob=True)'s prob and slot)."""
+        self._need_priorities("is_weights")
+        return self.is_weighter(prob, slot, beta)
+
+    def max_priority(self) -> float:
+        """The running maximum priority: what the next appended row enters at. Synchronises."""
+        self._need_priorities("max_priority")
+        return float(self._max_priority.item())

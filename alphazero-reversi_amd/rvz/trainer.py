@@ -303,12 +303,13 @@ class DDPTrainer:
     def rank_world(self):
         return (dist.get_rank(), dist.get_world_size()) if self.distributed else (0, 1)
 
-    def train_step(self, states, policy_targets, value_targets, weights=None):
+    def train_step(self, states, policy_targets, value_targets, weights=None, rows=False):
         """One optimizer step (pipeline.py:297-340); returns (loss, policy_loss, value_loss).
         weights (policy_target="full" only): float32 [n], each row's weight in the batch's mean;
-        None weights every row 1. In "full" mode last_stats holds the step's loss_fn stats."""
-        if weights is not None and self.policy_target != "full":
-            raise ValueError("train_step: weights need policy_target='full'")
+        None weights every row 1. In "full" mode last_stats holds the step's loss_fn stats; with
+        rows=True ("full" only) loss_fn is asked for its per-row losses, last_stats["rows"]."""
+        if (weights is not None or rows) and self.policy_target != "full":
+            raise ValueError("train_step: weights and rows need policy_target='full'")
         self.net.train()
         self.opt.zero_grad()
         logits, value = self.net(states)
@@ -316,7 +317,8 @@ class DDPTrainer:
             board = int(getattr(self.model, "board_size", 8))
             loss, policy_loss, value_loss, self.last_stats = self.loss_fn(
                 logits.view(-1, logits.size(-1)), value.squeeze(-1), policy_targets,
-                value_targets.reshape(-1), weights, self.wp, self.wv, board)
+                value_targets.reshape(-1), weights, self.wp, self.wv, board,
+                **({"rows": True} if rows else {}))
         else:
             policy_loss = F.cross_entropy(logits.view(-1, logits.size(-1)),
                                           policy_targets.argmax(dim=1))
@@ -407,8 +409,8 @@ class DDPTrainer:
             tot = t / ranks
         return self._loss_dict(tot, steps)
 
-    def train_replay(self, buffer, steps: int, seed: int = 0, symmetries: bool = True
-                     ) -> Dict[str, float]:
+    def train_replay(self, buffer, steps: int, seed: int = 0, symmetries: bool = True,
+                     priority_beta: float = 0.4) -> Dict[str, float]:
         """`steps` optimizer steps on minibatches drawn from a rvz.ReplayBuffer: step s trains
         on buffer.sample(batch_size, seed * world + rank, s, symmetries), a uniform draw with
         replacement over the rows held, each under a fresh board symmetry. The buffer is this
@@ -419,7 +421,21 @@ class DDPTrainer:
         in "full" mode every drawn row weighs 1. With a ReplayBuffer(weighted=True) the draw is in
         proportion to the rows' sampling weights instead; where those are record counts
         (SelfPlayTrainer(replay_sampling="counts")) the sampling carries the counts, and every
-        drawn row still weighs 1 in the loss."""
+        drawn row still weighs 1 in the loss.
+        With a ReplayBuffer(prioritized=True) every step is one round of prioritized replay: the
+        batch is drawn with its probabilities, every row weighs its importance weight
+        (pmin / prob) ** priority_beta in the loss (buffer.is_weights; 0.4 is where Schaul et al.
+        start their anneal, 1 corrects the sampling bias in full), and the step's per-row losses
+        become the drawn rows' new priorities (buffer.update_priorities with the trainer's loss
+        weights). That needs policy_target="full", whose loss takes the weights and returns the
+        rows: ValueError otherwise. The loss dict then gains "train/is_weight_mean" (the mean
+        importance weight of the drawn rows) and "train/priority_mean" (the mean priority
+        written, over the rows that had one). priority_beta is ignored by any other buffer."""
+        prioritized = bool(getattr(buffer, "prioritized", False))
+        if prioritized and self.policy_target != "full":
+            raise ValueError("train_replay: a ReplayBuffer(prioritized=True) needs "
+                             "policy_target='full' (the importance weights and the loss rows "
+                             "are the full policy loss's)")
         rank, world = self.rank_world()
         steps = int(steps)
         if self.distributed:          # every rank must run the same number of DDP steps
@@ -427,9 +443,20 @@ class DDPTrainer:
                              device=self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             steps = int(t.item())
-        tot = torch.zeros(5 if self.policy_target == "full" else 3, dtype=torch.float64,
-                          device=self.device)
+        tot = torch.zeros((5 if self.policy_target == "full" else 3) + 2 * prioritized,
+                          dtype=torch.float64, device=self.device)
         for s in range(steps):
+            if prioritized:
+                states, policy, value, slot, _, prob = buffer.sample(
+                    self.batch_size, seed * world + rank, s, symmetries, with_prob=True)
+                weights = buffer.is_weights(prob, slot, priority_beta)
+                losses = self.train_step(states, policy, value, weights, rows=True)
+                priority, state = buffer.update_priorities(slot, self.last_stats["rows"],
+                                                           self.wp, self.wv)
+                valid = (state >= 0).sum().clamp(min=1)
+                extra = torch.stack([weights.double().mean(), priority.double().sum() / valid])
+                tot += torch.cat([self._step_totals(losses), extra.to(tot.device)])
+                continue
             states, policy, value = buffer.sample(self.batch_size, seed * world + rank, s,
                                                   symmetries)[:3]
             losses = self.train_step(states, policy, value)
@@ -439,4 +466,8 @@ class DDPTrainer:
             t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t)
             tot = t / world
-        return self._loss_dict(tot, steps)
+        out = self._loss_dict(tot, steps)
+        if prioritized:
+            out["train/is_weight_mean"] = float(tot[-2])
+            out["train/priority_mean"] = float(tot[-1])
+        return out

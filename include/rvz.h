@@ -647,6 +647,80 @@ int rvz_replay_batch_weighted(int32_t board_size, int32_t capacity, const uint64
                               int32_t *out_slot /* [nb] */, int32_t *out_sym /* [nb] */,
                               float *out_prob /* [nb], nullable */, void *hip_stream);
 
+/* ---- prioritized replay: importance weights and loss-driven priorities ---------------------
+ * The two calls that join rvz_replay_batch_weighted (its out_slot and out_prob) and
+ * rvz_policy_value_loss (its out_row) into the prioritized replay of Schaul et al. (2016): the
+ * importance weights of a drawn batch, and the batch's losses written back into the ring's weight
+ * as the rows' new sampling weights. Both (csrc/rvz_priority.hip) are stateless, on caller arrays
+ * (device pointers), asynchronous on hip_stream and graph-capturable: no allocation, no copy, no
+ * memset, no synchronisation; the scratch needs no preparation; no workgroup waits on another;
+ * every output element is written exactly once; rows are checked in the kernel, no host
+ * synchronisation. Neither sees a board: only slots, losses and probabilities.
+ * All arithmetic is float64 (IEEE, no contraction); pow is the correctly rounded power
+ * (csrc/rvz_pow.hip.h pow_cr, the one k_act uses), so the results are a pure function of the
+ * arguments, independent of nb's neighbours and of the launch geometry, and a host reference
+ * reproduces them bit for bit.
+ *
+ * rvz_replay_is_weight: row r is valid iff slot[r] >= 0 and prob[r] is finite and > 0;
+ *   pmin = the smallest prob among the valid rows
+ *   out_weight[r] = (float) pow((double) pmin / (double) prob[r], beta)   for a valid row, else 0
+ *   out_min_prob  = pmin, or 0 with no valid row (then every weight is 0)
+ * This is (N P(i))^-beta divided by its maximum over the batch (N cancels): every valid row's
+ * weight lies in (0, 1] and the rarest drawn row weighs 1; a zero row of a stale or empty table
+ * weighs nothing in the loss. pmin is an integer minimum over the bit patterns of the valid
+ * probabilities (positive floats order as their bits), so it depends on no order.
+ * rvz_replay_is_weight_scratch_size: the scratch's bytes (16); negative for nb < 0.
+ * RVZ_EINVAL (before any HIP call): nb < 0, beta not finite or outside [0, 1], and with nb > 0 a
+ * null prob / slot / out_weight / scratch or a scratch that is not 16-byte aligned. nb = 0 returns
+ * RVZ_OK without a launch, and then nothing is written.
+ *
+ * rvz_replay_priority: row[r] = {Lp, Lv, H} is rvz_policy_value_loss's out_row of the batch whose
+ * out_slot is slot. Per row r:
+ *   k = subtract_entropy ? (Lp - H > 0 ? Lp - H : 0) : Lp
+ *       with the flag, the divergence KL(target || net policy): Lp alone never reaches 0 on a
+ *       high-entropy target; a divergence that rounding made negative is 0
+ *   e = policy_coef * k + value_coef * Lv        two products and one sum, each rounded on its own
+ *   valid iff 0 <= slot[r] < capacity, Lp, Lv and H are finite, Lp >= 0, Lv >= 0 and e is finite
+ *   p = (float) min(cap, max(floor, pow(e, alpha)))
+ * floor >= 2^-16 keeps a written row's fixed-point weight in rvz_replay_cdf above 0, so it can be
+ * drawn again; alpha = 0 writes pow = 1 everywhere (uniform sampling).
+ * weight (the ring's per-slot weights, in/out) becomes what the sequential loop
+ *   for r in 0 .. nb - 1: if valid(r): weight[slot[r]] = p_r
+ * leaves: of the valid rows that name one slot (a batch is drawn with replacement, and one record
+ * can appear under several symmetries with different losses) the one with the highest r wins, and
+ * a slot no valid row names keeps its bytes. The result does not depend on timing.
+ *   out_state[r]    = 1 for a winner, 0 for a valid row a later one superseded, -1 if invalid
+ *   out_priority[r] = p_r for a valid row, else 0
+ *   *max_priority   = max(*max_priority, max over the valid rows of p_r), winners or not: a
+ *                     running maximum (an integer maximum on the bits of non-negative floats;
+ *                     the value held must be one, not NaN)
+ * The caller guarantees that no append has overwritten the batch's slots between the draw and
+ * this call: the call cannot tell a slot's new tenant from the row that was drawn. The table of
+ * prefix sums is not updated: rebuild it with rvz_replay_cdf before the next draw.
+ * weight, slot, row, the scratch and the outputs must not overlap.
+ * rvz_replay_priority_scratch_size: the scratch's bytes (16 + 4 per row + a hash table of the
+ * power of two >= max(2 nb, 64) entries of 8 bytes), non-decreasing in nb; negative for nb < 0 or
+ * nb > 2^30.
+ * RVZ_EINVAL (before any HIP call): capacity < 1, nb < 0 or nb > 2^30, a coefficient that is
+ * negative or not finite, alpha outside [0, 1], floor / cap breaking 2^-16 <= floor <= cap <=
+ * 65536, and with nb > 0 a null weight / slot / row / scratch or a scratch that is not 16-byte
+ * aligned. nb = 0 returns RVZ_OK without a launch, and then nothing is written. */
+int64_t rvz_replay_is_weight_scratch_size(int32_t nb);
+int rvz_replay_is_weight(int32_t nb, const float *prob /* [nb] */, const int32_t *slot /* [nb] */,
+                         double beta, void *scratch /* 16-byte aligned */,
+                         float *out_weight /* [nb] */, float *out_min_prob /* [1], nullable */,
+                         void *hip_stream);
+int64_t rvz_replay_priority_scratch_size(int32_t nb);
+int rvz_replay_priority(int32_t capacity, float *weight /* [capacity], in/out */, int32_t nb,
+                        const int32_t *slot /* [nb]: the batch's out_slot */,
+                        const double *row /* [nb][3]: rvz_policy_value_loss's out_row */,
+                        double policy_coef, double value_coef, int32_t subtract_entropy,
+                        double alpha, double floor, double cap,
+                        void *scratch /* 16-byte aligned */,
+                        float *max_priority /* [1], in/out, nullable */,
+                        float *out_priority /* [nb], nullable */,
+                        int32_t *out_state /* [nb], nullable */, void *hip_stream);
+
 /* ---- policy/value loss on the full policy target -------------------------------------------
  * AlphaZero's own loss, -pi . log p + (y - t)^2, on the whole target distribution (a merged
  * position's mean search policy, the uniform distribution over the proven-optimal moves, a visit
