@@ -1,0 +1,295 @@
+// rvz_records.hip — a window of autoreset self-play records cut into finished games
+// (rvz_records_games; contract in include/rvz.h).
+//
+// rvz_play with reset = 1 writes one record per ply and slot, a slot's games one after another.
+// Three consecutive launches on one stream turn a window [plies][n_games] of such records into the
+// compact rows a replay ring holds; no workgroup waits on another, nothing is an atomic, and every
+// output element is written once.
+//
+// k_rec_walk, a lane per slot: the walk of the contract down the slot's column (the [ply][slot]
+// layout makes each ply's loads coalesced across the lanes) with the engine's own make_move
+// (rvz_rules.hip.h). A record enters the scratch as "open" with its side; when its segment ends or
+// is abandoned, the lane goes back over the segment's plies and writes each record's final state,
+// its value target and, for an emitted record, its rank among the slot's rows. A record is
+// revisited once at most (segments are disjoint), and a lane reads back only words it wrote
+// itself. The slot's seven counts go to the scratch, slot-minor.
+//
+// k_rec_scan, one workgroup: the exclusive scan of the slots' row counts (a shuffle scan of 64-bit
+// items within each wave, the waves' totals through LDS, a running carry from chunk to chunk, as
+// k_cdf_scan) and the seven sums in 64 bits; it writes out_m and out_stats.
+//
+// k_rec_rows, a wavefront per record, lane = policy entry (on 8x8 lane 0 also carries the pass
+// entry, as in rvz_policy_value_loss): out_state of every record, and for an emitted one the row
+// at offset[slot] + rank: the policy converted to float32, the two bitboards from the mover's
+// side, the value, the source index.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rvz.h"
+#include "rvz_host.hip.h"
+#include "rvz_rules.hip.h"
+
+namespace {
+
+using namespace rvz;
+
+constexpr int WALK_THREADS = 64;                 // k_rec_walk: one wave a workgroup, a lane a slot
+constexpr int SCAN_THREADS = 1024;               // k_rec_scan's one workgroup: 16 waves
+constexpr int SCAN_WAVES = SCAN_THREADS / 64;
+constexpr int ROWS_WAVES = 4;                    // k_rec_rows: records per workgroup and step
+constexpr int ROWS_THREADS = ROWS_WAVES * 64;
+constexpr int N_COUNTS = 7;                      // out_stats [0, 7) per slot
+
+// a record's states (out_state)
+constexpr int ST_MALFORMED = -5, ST_NONE = -1, ST_OPEN = 0, ST_EMITTED = 1, ST_EARLIER = 2,
+              ST_ABANDONED = 3;
+
+// the scratch's word per record: bits 0-7 state + 8, bits 8-9 the side, bits 16-17 value + 1
+__device__ __forceinline__ int32_t pack(int state, int side, int value) {
+    return (state + 8) | (side << 8) | ((value + 1) << 16);
+}
+__device__ __forceinline__ int word_state(int32_t w) { return (w & 0xff) - 8; }
+__device__ __forceinline__ int word_side(int32_t w) { return (w >> 8) & 3; }
+__device__ __forceinline__ int word_value(int32_t w) { return ((w >> 16) & 3) - 1; }
+
+inline int64_t up16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
+
+// the scratch: offset int64 [n_games], counts int32 [7][n_games], info int32 [records],
+// rank int32 [records]; each part 16-byte aligned
+struct Layout {
+    int64_t offset, counts, info, rank, bytes;
+};
+inline Layout layout(int64_t plies, int64_t n_games) {
+    Layout l;
+    l.offset = 0;
+    l.counts = up16(8 * n_games);
+    l.info = l.counts + up16(4 * N_COUNTS * n_games);
+    l.rank = l.info + up16(4 * plies * n_games);
+    l.bytes = l.rank + up16(4 * plies * n_games);
+    return l;
+}
+
+template <int BS>
+__global__ __launch_bounds__(WALK_THREADS) void k_rec_walk(
+    int plies, int n_games, const uint64_t* __restrict__ rec_black,
+    const uint64_t* __restrict__ rec_white, const int32_t* __restrict__ rec_side,
+    const int32_t* __restrict__ rec_idx, int emit_from, int32_t* info, int32_t* __restrict__ rank,
+    int32_t* __restrict__ counts) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    const int g = blockIdx.x * WALK_THREADS + threadIdx.x;
+    if (g >= n_games) return;
+    const size_t G = (size_t)n_games;
+    int rows = 0, games = 0, abandoned = 0, malformed = 0, headless_games = 0, earlier = 0;
+    bool open = false, headless = false;
+    int seg_start = 0, seg_len = 0;
+    GameS cur = {0ull, 0ull, 1, 0, -1, 0};
+
+    // the segment's records in plies [from, to): every word still open becomes `state`; an
+    // emitted record gets its value against `winner` and the slot's next rank
+    auto close = [&](int from, int to, int state, int winner) {
+        for (int q = from; q < to; ++q) {
+            const size_t at = (size_t)q * G + g;
+            const int32_t w = info[at];
+            if (word_state(w) != ST_OPEN) continue;                     // a ply without a record
+            const int side = word_side(w);
+            const int value = state != ST_EMITTED || winner == 0 ? 0 : (winner == side ? 1 : -1);
+            info[at] = pack(state, side, value);
+            if (state == ST_EMITTED) rank[at] = rows++;
+        }
+    };
+
+    for (int p = 0; p < plies; ++p) {
+        const size_t at = (size_t)p * G + g;
+        const int idx = rec_idx[at];
+        if (idx < 0) {
+            info[at] = pack(ST_NONE, 0, 0);
+            continue;
+        }
+        const uint64_t b = rec_black[at], w = rec_white[at];
+        const int side = rec_side[at];
+        bool ok = !(b & w) && !((b | w) & ~Geo<BS>::FULL) && (side == 1 || side == 2) &&
+                  idx <= NSQ;
+        const bool chained = open && b == cur.black && w == cur.white && side == cur.side;
+        if (ok && open && !chained) {                                   // the chain is broken
+            close(seg_start, p, ST_ABANDONED, 0);
+            abandoned += seg_len;
+            open = false;
+        }
+        GameS t = cur;
+        if (ok) {
+            if (!chained) t = GameS{b, w, side, 0, -1, 0};
+            ok = make_move<BS>(t, idx == NSQ ? -1 : idx);
+        }
+        if (!ok) {
+            info[at] = pack(ST_MALFORMED, 0, 0);
+            ++malformed;
+            if (open) {
+                close(seg_start, p, ST_ABANDONED, 0);
+                abandoned += seg_len;
+                open = false;
+            }
+            continue;
+        }
+        if (!open) {
+            open = true;
+            seg_start = p;
+            seg_len = 0;
+            headless = !(b == Geo<BS>::START_BLACK && w == Geo<BS>::START_WHITE && side == 1);
+        }
+        info[at] = pack(ST_OPEN, side, 0);
+        ++seg_len;
+        cur = t;
+        if (cur.over) {
+            if (p >= emit_from) {
+                close(seg_start, p + 1, ST_EMITTED, cur.winner);
+                ++games;
+                headless_games += headless ? 1 : 0;
+            } else {
+                close(seg_start, p + 1, ST_EARLIER, 0);
+                earlier += seg_len;
+            }
+            open = false;
+        }
+    }
+    counts[0 * G + g] = rows;
+    counts[1 * G + g] = games;
+    counts[2 * G + g] = open ? seg_len : 0;
+    counts[3 * G + g] = abandoned;
+    counts[4 * G + g] = malformed;
+    counts[5 * G + g] = headless_games;
+    counts[6 * G + g] = earlier;
+}
+
+__global__ __launch_bounds__(SCAN_THREADS) void k_rec_scan(int n_games,
+                                                           const int32_t* __restrict__ counts,
+                                                           int64_t* __restrict__ offset,
+                                                           int32_t* __restrict__ out_m,
+                                                           int64_t* __restrict__ out_stats) {
+    __shared__ int64_t part[2][SCAN_WAVES];
+    __shared__ int64_t sums[SCAN_WAVES][N_COUNTS];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const size_t G = (size_t)n_games;
+    int64_t carry = 0, s[N_COUNTS];
+#pragma unroll
+    for (int k = 0; k < N_COUNTS; ++k) s[k] = 0;
+    int c = 0;
+    for (int base = 0; base < n_games; base += SCAN_THREADS, c ^= 1) {  // block-uniform trip count
+        const int i = base + (int)threadIdx.x;
+        int64_t mine = 0;
+        if (i < n_games) {
+            mine = counts[i];
+#pragma unroll
+            for (int k = 0; k < N_COUNTS; ++k) s[k] += counts[k * G + i];
+        }
+        int64_t v = mine;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t up = __shfl_up((long long)v, d, 64);
+            if (lane >= d) v += up;
+        }
+        if (lane == 63) part[c][wave] = v;
+        __syncthreads();
+        int64_t before = carry;
+        for (int w = 0; w < SCAN_WAVES; ++w) {
+            const int64_t t = part[c][w];
+            if (w < wave) before += t;
+            carry += t;
+        }
+        if (i < n_games) offset[i] = before + v - mine;
+    }
+#pragma unroll
+    for (int k = 0; k < N_COUNTS; ++k) {
+#pragma unroll
+        for (int d = 32; d; d >>= 1) s[k] += __shfl_xor((long long)s[k], d, 64);
+        if (lane == 0) sums[wave][k] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        int64_t all = 0;
+        if (threadIdx.x < N_COUNTS)
+            for (int w = 0; w < SCAN_WAVES; ++w) all += sums[w][threadIdx.x];
+        out_stats[threadIdx.x] = all;                                   // [7] is 0
+        if (threadIdx.x == 0) *out_m = (int32_t)all;                    // rows <= records < 2^31
+    }
+}
+
+template <int BS>
+__global__ __launch_bounds__(ROWS_THREADS) void k_rec_rows(
+    int records, int n_games, const uint64_t* __restrict__ rec_black,
+    const uint64_t* __restrict__ rec_white, const double* __restrict__ rec_p,
+    const int32_t* __restrict__ info, const int32_t* __restrict__ rank,
+    const int64_t* __restrict__ offset, uint64_t* __restrict__ out_mover,
+    uint64_t* __restrict__ out_opponent, float* __restrict__ out_policy,
+    float* __restrict__ out_value, int32_t* __restrict__ out_src, int32_t* __restrict__ out_state) {
+    constexpr int NPOL = Geo<BS>::NPOL;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int stride = gridDim.x * ROWS_WAVES;      // records * NPOL fits int32, so r + stride does
+    for (int r = blockIdx.x * ROWS_WAVES + wave; r < records; r += stride) {    // wave-uniform
+        const int32_t w = info[r];
+        const int state = word_state(w);
+        if (lane == 0 && out_state) out_state[r] = state;
+        if (state != ST_EMITTED) continue;
+        const size_t j = (size_t)(offset[r % n_games] + rank[r]);       // < *out_m <= records
+        const double* __restrict__ src = rec_p + (size_t)r * NPOL;
+        float* __restrict__ dst = out_policy + j * NPOL;
+        if (lane < NPOL) dst[lane] = (float)src[lane];
+        if (NPOL > 64 && lane == 0) dst[64] = (float)src[64];
+        if (lane == 0) {
+            const uint64_t b = rec_black[r], wh = rec_white[r];
+            const bool black_moves = word_side(w) == 1;
+            out_mover[j] = black_moves ? b : wh;
+            out_opponent[j] = black_moves ? wh : b;
+            out_value[j] = (float)word_value(w);
+            out_src[j] = r;
+        }
+    }
+}
+
+inline bool shape_ok(int64_t plies, int64_t n_games, int npol) {
+    return plies >= 1 && n_games >= 1 && plies <= INT32_MAX / n_games &&
+           plies * n_games <= INT32_MAX / npol;     // plies * n_games * npol < 2^31
+}
+
+}  // namespace
+
+extern "C" int64_t rvz_records_scratch_size(int32_t plies, int32_t n_games) {
+    if (!shape_ok(plies, n_games, 37)) return -1;   // too many records for either board
+    return layout(plies, n_games).bytes;
+}
+
+extern "C" int rvz_records_games(int32_t bs, int32_t plies, int32_t n_games,
+                                 const uint64_t* rec_black, const uint64_t* rec_white,
+                                 const int32_t* rec_side, const int32_t* rec_idx,
+                                 const double* rec_p, int32_t emit_from, void* scratch,
+                                 int32_t* out_m, uint64_t* out_mover, uint64_t* out_opponent,
+                                 float* out_policy, float* out_value, int32_t* out_src,
+                                 int32_t* out_state, int64_t* out_stats, void* stream) {
+    if (!board_ok(bs) || !shape_ok(plies, n_games, bs * bs + 1) || emit_from < 0 ||
+        emit_from > plies)
+        return RVZ_EINVAL;
+    if (!rec_black || !rec_white || !rec_side || !rec_idx || !rec_p || !scratch || !out_m ||
+        !out_mover || !out_opponent || !out_policy || !out_value || !out_src || !out_stats ||
+        ((uintptr_t)scratch & 15u) != 0)
+        return RVZ_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const Layout l = layout(plies, n_games);
+    char* base = (char*)scratch;
+    int64_t* offset = (int64_t*)(base + l.offset);
+    int32_t* counts = (int32_t*)(base + l.counts);
+    int32_t* info = (int32_t*)(base + l.info);
+    int32_t* rank = (int32_t*)(base + l.rank);
+    const int records = plies * n_games;
+    launch_bs_unchecked(bs, k_rec_walk<8>, k_rec_walk<6>,
+                        dim3((n_games + WALK_THREADS - 1) / WALK_THREADS), dim3(WALK_THREADS), s,
+                        plies, n_games, rec_black, rec_white, rec_side, rec_idx, emit_from, info,
+                        rank, counts);
+    hipLaunchKernelGGL(k_rec_scan, dim3(1), dim3(SCAN_THREADS), 0, s, n_games,
+                       (const int32_t*)counts, offset, out_m, out_stats);
+    const Geometry g = strided(records, ROWS_WAVES, ROWS_THREADS);
+    return launch_bs(bs, k_rec_rows<8>, k_rec_rows<6>, g.grid, g.block, s, records, n_games,
+                     rec_black, rec_white, rec_p, (const int32_t*)info, (const int32_t*)rank,
+                     (const int64_t*)offset, out_mover, out_opponent, out_policy, out_value,
+                     out_src, out_state);
+}

@@ -32,6 +32,9 @@ Batched core:
                             back as the rows' sampling weights (rvz_replay_priority) and the
                             importance weights of a drawn batch (rvz_replay_is_weight):
                             ReplayBuffer(prioritized=True)
+    records_games           a window of autoreset self-play records cut into finished games:
+                            compact rows with value targets, open games held back
+                            (rvz_records_games); SelfPlayRunner(carry_plies=...) keeps the window
     policy_value_loss, full_policy_loss   the loss on the full policy target, weighted per row,
                             with its gradients in one deterministic float64 call
                             (rvz_policy_value_loss), and its differentiable torch form
@@ -46,9 +49,9 @@ from .loss import full_policy_loss, policy_value_loss  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)
-from .records import (board_symmetry, merge_positions, replay_batch,  # noqa: F401
-                      replay_batch_weighted, replay_cdf, replay_is_weight, replay_priority,
-                      symmetry_compose, symmetry_inverse, training_rows)
+from .records import (board_symmetry, merge_positions, records_games,  # noqa: F401
+                      replay_batch, replay_batch_weighted, replay_cdf, replay_is_weight,
+                      replay_priority, symmetry_compose, symmetry_inverse, training_rows)
 from .replay import ReplayBuffer  # noqa: F401
 from .selfplay import LaneRunner, SelfPlay, SelfPlayRunner  # noqa: F401
 

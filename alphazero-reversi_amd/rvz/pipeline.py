@@ -29,9 +29,10 @@ import torch.distributed as dist
 
 from .engine import SOLVE_MAX_EMPTIES, Engine
 from .network import LeafEvaluator, leaf_evaluator
+from .records import records_games
 from .replay import ReplayBuffer
 from .selfplay import SelfPlayRunner
-from .trainer import DDPTrainer, adjudicate, records_to_training
+from .trainer import DDPTrainer, adjudicate, games_to_training, records_to_training
 
 
 class SelfPlayTrainer:
@@ -51,8 +52,29 @@ class SelfPlayTrainer:
                  replay_steps: Optional[int] = None, replay_symmetries: bool = True,
                  policy_target: str = "argmax", count_weights: bool = False,
                  replay_sampling: str = "uniform", replay_recency_decay: float = 1.0,
-                 replay_priority_alpha: float = 0.6, replay_priority_beta=0.4):
-        """root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
+                 replay_priority_alpha: float = 0.6, replay_priority_beta=0.4,
+                 continuous_plies: Optional[int] = None):
+        """continuous_plies: None (off: the keys and bytes of before) or K >= 1: continuous
+        self-play, the operating point bench.py measures. An iteration is ONE rvz_play launch of K
+        plies with autoreset (a finished game restarts at once with its slot's next seed, so no
+        slot idles and the games spread over all move numbers) into the runner's window, behind a
+        carry of the C = S*S - 4 plies before it (SelfPlayRunner(carry_plies=C)). A game has at
+        most C records, so every game that ends in the new part lies wholly in the window:
+        rvz.records_games(emit_from=C) cuts the window into those games' compact rows with their
+        value targets (the rvz_records_games HIP kernels; reading the row count is the one host
+        synchronisation, as with merging), games_to_training applies exact_endgame, exact_policy
+        and merge_positions to them, they are appended to the replay buffer, and the window rolls
+        on. The games are started once, at the first iteration, and continued by the later ones;
+        train() refreshes the evaluator (new weights, the memo dropped, a new table generation),
+        so a game can be played by two successive nets: its early records carry the search
+        policies of the older one. The slots' seeds advance by games x world per finished game.
+        It needs the fused h2 path and replay_iterations > 0 (the rows are compact), and raises
+        ValueError with adjudicate_empties or symmetries. replay_capacity then defaults to
+        replay_iterations x games x (C + K), since no iteration yields more; an iteration that
+        finds the buffer still empty (K below a game's length, at the start) trains no step.
+        run_iteration also reports games_emitted, records_open, records_abandoned and
+        records_headless_games from records_games' stats (in this mode alone).
+        root_noise: None (off) or (alpha, epsilon[, salt]): Dirichlet noise at the search
         roots of the self-play games (Engine.root_noise), set before any graph is captured.
         temperature_schedule: None (off) or (moves, late): a game's first `moves` moves are chosen
         at `temperature`, the later ones at `late` (Engine.temperature_schedule), set before any
@@ -196,6 +218,24 @@ class SelfPlayTrainer:
         if replay_recency_decay != 1.0 and not replay_iterations:
             raise ValueError("replay_recency_decay != 1 needs replay_iterations > 0: it ages "
                              "the replay buffer's rows")
+        if continuous_plies is not None:
+            if isinstance(continuous_plies, bool) or \
+                    not isinstance(continuous_plies, numbers.Integral) or continuous_plies < 1:
+                raise ValueError("continuous_plies must be None or an int >= 1, not "
+                                 f"{continuous_plies!r}")
+            if not replay_iterations:
+                raise ValueError("continuous_plies needs replay_iterations > 0: its rows are the "
+                                 "replay buffer's compact records")
+            if not fused:
+                raise ValueError("continuous_plies needs fused=True: it is one rvz_play launch "
+                                 "with autoreset")
+            if adjudicate_empties:
+                raise ValueError("continuous_plies plays every game to its end: "
+                                 "adjudicate_empties must be 0")
+            if symmetries is not None:
+                raise ValueError("continuous_plies leaves the symmetry to the replay buffer's "
+                                 f"draw: symmetries must be None, not {symmetries!r}")
+        self.continuous_plies = None if continuous_plies is None else int(continuous_plies)
         self.model = model.eval()
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -255,15 +295,25 @@ class SelfPlayTrainer:
             table_slots = 1 << min(22, max(12, (32 * self.games - 1).bit_length()))
         if self.fused and table_slots:
             self.eng.table(table_slots, table_discs)
+        if self.continuous_plies and not self.fused:
+            raise ValueError("continuous_plies needs the fused h2 path: the h2 kernels do not "
+                             "cover this net")
+        # continuous: a window of max_plies carried plies and continuous_plies new ones, the
+        # slots restarting with autoreset; a slot's seeds go seed_g, seed_g + games * world, ...
+        continuous = ({"autoreset": True, "carry_plies": self.max_plies,
+                       "seed_stride": self.games * self.world}
+                      if self.continuous_plies else {})
         self.runner = SelfPlayRunner(self.eng, self.evaluator, temperature, record=True,
-                                     max_plies=self.max_plies,
+                                     max_plies=self.continuous_plies or self.max_plies,
                                      seed_base=self.seed + self.rank * self.games,
-                                     fused=self.fused, skip_last_eval=self.fused and memo)
+                                     fused=self.fused, skip_last_eval=self.fused and memo,
+                                     **continuous)
         self.graph = bool(graph) and h2
         self.buffer = None
         if self.replay_iterations:
             if replay_capacity is None:
-                replay_capacity = self.replay_iterations * self.games * self.max_plies
+                replay_capacity = self.replay_iterations * self.games * (
+                    self.max_plies + (self.continuous_plies or 0))
             weighted = self.replay_sampling == "counts" or self.replay_recency_decay != 1.0
             priority = ({"prioritized": True, "priority_alpha": float(replay_priority_alpha),
                          "recency_decay": self.replay_recency_decay}
@@ -297,6 +347,8 @@ class SelfPlayTrainer:
         """One iteration's self-play: every game of this rank from the start to its end.
         Returns the training arrays (states, policy_targets, value_targets) on the device."""
         run = self.runner
+        if self.continuous_plies:
+            return self._continuous()
         self._seeds()
         run.start()
         plies = self.max_plies - self.adjudicate_empties
@@ -319,6 +371,25 @@ class SelfPlayTrainer:
                                    exact_wld=self.exact_wld, exact_policy=self.exact_policy,
                                    **self._symmetry_args(), **self._merge_args(),
                                    **self._compact_args())
+
+    def _continuous(self) -> Dict[str, torch.Tensor]:
+        """generate() with continuous_plies on: one launch of K plies with autoreset behind the
+        carry, the games that finished in it as compact training rows, the window rolled on."""
+        run, C = self.runner, self.max_plies
+        if self.iteration == 0:         # the games start once; later iterations continue them
+            self._seeds()
+            run.start()
+        run.play_record(self.continuous_plies)
+        run.check()
+        rows = records_games(run.rec_black, run.rec_white, run.rec_side, run.rec_idx, run.rec_p,
+                             self.eng.board_size, emit_from=C)
+        out = games_to_training(rows, self.eng.board_size, exact_endgame=self.exact_endgame,
+                                exact_node_limit=self.exact_node_limit,
+                                exact_wld=self.exact_wld, exact_policy=self.exact_policy,
+                                **self._merge_args(), compact=True)
+        run.roll()
+        out["records_stats"] = rows["stats"]
+        return out
 
     def _adjudicated(self, plies: int) -> Dict[str, torch.Tensor]:
         """generate()'s tail with adjudication on: the games stand after `plies` plies."""
@@ -373,7 +444,9 @@ class SelfPlayTrainer:
                 steps = -(-data["mover"].shape[0] // self.trainer.batch_size)
             if self.train_steps is not None:
                 steps = min(steps, self.train_steps)
-            beta = ({"priority_beta": self.priority_beta()}
+            if self.continuous_plies and len(self.buffer) == 0:
+                steps = 0               # no game has finished yet: nothing to draw from
+            beta =({"priority_beta": self.priority_beta()}
                     if self.replay_sampling == "priority" else {})
             out = self.trainer.train_replay(self.buffer, steps, seed=self.seed + self.iteration,
                                             symmetries=self.replay_symmetries, **beta)
@@ -418,4 +491,8 @@ class SelfPlayTrainer:
                                                if self.buffer is not None else 0)})
         if self.replay_sampling == "priority":
             out["replay_priority_max"] = self.buffer.max_priority()
+        if self.continuous_plies:
+            stats = data["records_stats"].tolist()
+            out.update({"games_emitted": stats[1], "records_open": stats[2],
+                        "records_abandoned": stats[3], "records_headless_games": stats[5]})
         return out

@@ -1,5 +1,6 @@
 """Training records on the device: the stateless wrappers of the C-ABI's record entry points
-(include/rvz.h): board symmetries, merge_positions and the replay ring's draws. Every argument rule
+(include/rvz.h): board symmetries, merge_positions, the replay ring's draws and the cut of autoreset
+self-play records into finished games. Every argument rule
 is one private helper that raises ``RvzError``, its message beginning with the caller's name,
 before any device call."""
 from __future__ import annotations
@@ -337,6 +338,80 @@ def replay_batch_weighted(mover: torch.Tensor, opponent: torch.Tensor, policy: t
             *map(ptr, given), ptr(wd), int(bool(random_sym)), int(seed) & _U64, int(step) & _U64,
             *map(ptr, out), ptr(prob), _lib.stream_handle(dev)), None, "rvz_replay_batch_weighted")
     return (*out, prob)
+
+
+# ------------------------------------------------------------------ continuous self-play records
+def check_records_args(rec_black, rec_white, rec_side, rec_idx, rec_p, board_size, emit_from,
+                       who: str = "records_games"):
+    """The argument rules of records_games, checked before any device call (the CPU tests'
+    NumPy restatement calls it too); returns (plies, n_games)."""
+    check_board_size(board_size, who)
+    npol = board_size * board_size + 1
+    _ints(who, emit_from=emit_from)
+    if not all(isinstance(t, torch.Tensor) for t in (rec_black, rec_white, rec_side, rec_idx,
+                                                     rec_p)):
+        raise RvzError(f"{who}: the five record arrays are tensors")
+    if rec_idx.dim() != 2 or any(t.shape != rec_idx.shape for t in (rec_black, rec_white,
+                                                                     rec_side)):
+        raise RvzError(f"{who}: rec_black, rec_white, rec_side and rec_idx are [plies, n_games]")
+    P, G = rec_idx.shape
+    _bitboards(who, rec_black.reshape(-1), rec_white.reshape(-1), "rec_black and rec_white",
+               "record")
+    _given(who, P * G, "record", optional=False, rec_side=rec_side.reshape(-1),
+           rec_idx=rec_idx.reshape(-1))
+    if rec_p.shape != (P, G, npol) or rec_p.dtype != torch.float64:
+        raise RvzError(f"{who}: rec_p must be float64 [plies, n_games, {npol}]")
+    _fits_int32(who, P * G, npol, "plies * n_games")
+    if not 0 <= emit_from <= P:
+        raise RvzError(f"{who}: emit_from = {emit_from} must be in [0, plies = {P}]")
+    return P, G
+
+
+def records_games(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
+                  rec_idx: torch.Tensor, rec_p: torch.Tensor, board_size: int = 8,
+                  emit_from: int = 0, state: bool = False):
+    """rvz_records_games: a window of autoreset self-play records cut into finished games
+    (include/rvz.h has the walk). rec_black / rec_white int64 [plies, n_games] (bit patterns),
+    rec_side / rec_idx [plies, n_games] integers (rec_idx: the moves, negative where a ply holds
+    no record), rec_p float64 [plies, n_games, S*S+1]: SelfPlayRunner's record tensors, a slot's
+    games one after another down its column; device tensors. A game that ends at a ply >=
+    emit_from is emitted: one row per record, slot-major, each with its value target from the
+    game's winner by the engine's own rules. Returns a dict: "m" the number of rows, a 0-d int32
+    device tensor (reading it is the caller's one host synchronisation); at length plies * n_games
+    with the rows from m on unwritten "mover" / "opponent" int64, "policy" float32 [.., S*S+1],
+    "value" float32 and "src" int32 (the record's ply * n_games + slot); "stats" int64 [8]:
+    emitted rows, emitted games, open records, abandoned records, malformed records, headless
+    emitted games, records an earlier window emitted, 0; and with state=True "state" int32
+    [plies, n_games]: 1 emitted, 0 open, 2 ended before emit_from, 3 abandoned, -1 no record,
+    -5 malformed. Asynchronous on the current stream; nothing synchronises. A window without
+    records (plies or n_games 0) gives m = 0 without a launch."""
+    P, G = check_records_args(rec_black, rec_white, rec_side, rec_idx, rec_p, board_size,
+                              emit_from)
+    npol = board_size * board_size + 1
+    lib = _lib.load()
+    dev = rec_black.device
+    n = P * G
+    b, w = rec_black.contiguous(), rec_white.to(dev).contiguous()
+    sd, ix = _i32(rec_side, dev), _i32(rec_idx, dev)
+    pol = rec_p.to(dev).contiguous()
+    out = {"m": torch.zeros((), dtype=torch.int32, device=dev),
+           "mover": torch.empty(n, dtype=torch.int64, device=dev),
+           "opponent": torch.empty(n, dtype=torch.int64, device=dev),
+           "policy": torch.empty(n, npol, dtype=torch.float32, device=dev),
+           "value": torch.empty(n, dtype=torch.float32, device=dev),
+           "src": torch.empty(n, dtype=torch.int32, device=dev),
+           "stats": torch.zeros(8, dtype=torch.int64, device=dev)}
+    if state:
+        out["state"] = torch.empty(P, G, dtype=torch.int32, device=dev)
+    if n:
+        scratch = torch.empty(lib.rvz_records_scratch_size(P, G), dtype=torch.uint8, device=dev)
+        check(lib.rvz_records_games(board_size, P, G, _addr(b), _addr(w), _addr(sd), _addr(ix),
+                                    _addr(pol), int(emit_from), ptr(scratch), _addr(out["m"]),
+                                    _addr(out["mover"]), _addr(out["opponent"]),
+                                    _addr(out["policy"]), _addr(out["value"]), _addr(out["src"]),
+                                    _addr(out.get("state")), _addr(out["stats"]),
+                                    _lib.stream_handle(dev)), None, "rvz_records_games")
+    return out
 
 
 # ------------------------------------------------------------------ prioritized replay

@@ -4,7 +4,9 @@
 one move per live game, self_play.py:80-101), optionally captured once into a HIP graph and
 replayed (the 13 select / NN / expand rounds and the act of a ply are one graph launch).
 With ``autoreset`` a finished game restarts at once with the next seed of its slot
-(seed_g, seed_g + G, ...), which keeps every slot busy for steady-state measurement.
+(seed_g, seed_g + G, ...), which keeps every slot busy for steady-state measurement; with
+``carry_plies`` the fused recording runner records such play into a rolling window that
+``rvz.records_games`` cuts into finished games (continuous self-play).
 
 ``SelfPlay`` is the drop-in for the reference class: same constructor ``(model, args)``, same
 ``generate_games(n)`` / ``generate_training_data(n)`` outputs (per-game dict of canonical states,
@@ -13,6 +15,7 @@ lockstep instead of one after another.
 """
 from __future__ import annotations
 
+import numbers
 import os
 import time
 from datetime import datetime
@@ -29,8 +32,22 @@ class SelfPlayRunner:
                  fused_softmax: bool = True, autoreset: bool = False, seed_base: int = 42,
                  record: bool = False, max_plies: int = 60, seed_stride: int = None,
                  skip_last_eval: bool = False, fused_bookkeeping: bool = True,
-                 fused: bool = False, temperature_schedule=None, skip_forced_roots=None):
+                 fused: bool = False, temperature_schedule=None, skip_forced_roots=None,
+                 carry_plies: int = 0):
         self.eng = engine
+        # carry_plies = C > 0 (fused and record): the records are a window of C + max_plies
+        # plies for continuous play with autoreset. A launch records behind a carry of the C
+        # plies before it, roll() moves the window on, and rvz.records_games(emit_from=C) cuts
+        # each window into the games that finished in its new part (C >= S*S - 4, the longest
+        # game, keeps every such game whole). 0: the records hold max_plies plies of whole
+        # lockstep games
+        if isinstance(carry_plies, bool) or not isinstance(carry_plies, numbers.Integral) or \
+                carry_plies < 0:
+            raise ValueError(f"carry_plies must be an int >= 0, not {carry_plies!r}")
+        self.carry_plies = int(carry_plies)
+        if self.carry_plies and not (fused and record):
+            raise ValueError("carry_plies is the fused recording runner's (fused=True, "
+                             "record=True)")
         # temperature_schedule: None (the engine's setting stays as it is) or (moves, late): a
         # game's first `moves` moves at `temperature`, the later ones at `late`
         # (Engine.temperature_schedule); set here, before any capture
@@ -50,7 +67,7 @@ class SelfPlayRunner:
         self.play_group = 0       # Engine.play's games_per_workgroup (0: the task queue default)
         if self.fused and not fused_softmax:
             raise ValueError("the fused runner plays with fused_softmax")
-        if self.fused and record and autoreset:
+        if self.fused and record and autoreset and not self.carry_plies:
             raise ValueError("a recording fused runner plays whole games (no autoreset)")
         # fused_bookkeeping: ply counting and autoreset in one engine kernel (rvz_env_autoreset)
         # instead of ~12 small torch kernels per ply; the games are the same either way
@@ -74,13 +91,14 @@ class SelfPlayRunner:
         self._mask = torch.zeros(G, dtype=torch.uint8, device=dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         if record:
-            self.rec_black = torch.zeros(max_plies, G, dtype=torch.int64, device=dev)
-            self.rec_white = torch.zeros(max_plies, G, dtype=torch.int64, device=dev)
-            self.rec_side = torch.zeros(max_plies, G, dtype=torch.int32, device=dev)
-            self.rec_idx = torch.full((max_plies, G), -2, dtype=torch.int32, device=dev)
-            self.rec_p = torch.zeros(max_plies, G, engine.npol, dtype=torch.float64, device=dev)
-            self.rec_over = torch.zeros(max_plies, G, 4, dtype=torch.int32, device=dev)
-        self.ply_index = 0
+            rows = self.carry_plies + max_plies
+            self.rec_black = torch.zeros(rows, G, dtype=torch.int64, device=dev)
+            self.rec_white = torch.zeros(rows, G, dtype=torch.int64, device=dev)
+            self.rec_side = torch.zeros(rows, G, dtype=torch.int32, device=dev)
+            self.rec_idx = torch.full((rows, G), -2, dtype=torch.int32, device=dev)
+            self.rec_p = torch.zeros(rows, G, engine.npol, dtype=torch.float64, device=dev)
+            self.rec_over = torch.zeros(rows, G, 4, dtype=torch.int32, device=dev)
+        self.ply_index = self.carry_plies
         if self.fused:       # play()'s buffers exist before any capture (Engine.play_buffers)
             engine.play_buffers(evaluator)
 
@@ -95,7 +113,23 @@ class SelfPlayRunner:
 
     def start(self):
         self.eng.reset(self.seeds)
-        self.ply_index = 0
+        self.ply_index = self.carry_plies
+        if self.carry_plies:            # fresh games: nothing of another run is carried
+            self.rec_idx.fill_(-2)
+
+    def roll(self):
+        """carry_plies = C > 0: move the window on. The last C plies of the five record tensors
+        go to the front, the rest of rec_idx is refilled with -2 (no record) and the next launch
+        records from ply C again. Device copies, no host synchronisation."""
+        C = self.carry_plies
+        if not C:
+            raise ValueError("roll() moves the window of a runner with carry_plies > 0")
+        rows = self.rec_idx.shape[0]
+        for t in (self.rec_black, self.rec_white, self.rec_side, self.rec_idx, self.rec_p):
+            tail = t[rows - C:]
+            t[:C].copy_(tail.clone() if rows < 2 * C else tail)     # the two may overlap
+        self.rec_idx[C:].fill_(-2)
+        self.ply_index = C
 
     def check(self):
         """Synchronise; raise RvzError on a device error word or an evaluator overflow

@@ -131,6 +131,20 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     v = torch.where(winner == side.to(torch.int32), 1.0, -1.0)
     v = torch.where(winner == 0, torch.zeros_like(v), v)
     v = torch.where(over != 0, v, -torch.ones_like(v))      # winner None -> -1 (self_play.py:121-126)
+    return _training_tail(black, white, st, states, policy, v, board_size, canonical,
+                          exact_endgame, solver, exact_node_limit, exact_wld, exact_policy,
+                          moves_solver, symmetries, symmetry_seed, augment, merge_positions,
+                          merger, compact)
+
+
+def _training_tail(black, white, st, states, policy, v, board_size, canonical, exact_endgame,
+                   solver, exact_node_limit, exact_wld, exact_policy, moves_solver, symmetries,
+                   symmetry_seed, augment, merge_positions, merger, compact):
+    """What records_to_training and games_to_training share: the kept records (black, white, st
+    [n, 4], policy float32 [n, S*S+1], v [n] from the games' outcomes; states the canonical planes
+    or None where a later step writes them) through exact_endgame, exact_policy, merge_positions,
+    compact and symmetries, in records_to_training's order and with its keys. Every target it
+    computes is relative to the player to move."""
     # compact: the two bitboards are filled in below, once merging has chosen the rows
     out = {"mover": None, "opponent": None} if compact else {"states": states}
     out.update({"policy_targets": policy, "value_targets": v.reshape(-1, 1).float()})
@@ -196,6 +210,45 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
                                             device=out["states"].device)
         out["symmetry_quirk_rows"] = (quirk == 1).sum()
     return out
+
+
+def games_to_training(rows: Dict[str, torch.Tensor], board_size: int = 8, canonical=None,
+                      exact_endgame: int = 0, solver=None, exact_node_limit: int = 2 ** 24,
+                      exact_wld: bool = False, exact_policy: int = 0, moves_solver=None,
+                      symmetries: Optional[str] = None, symmetry_seed: int = 0, augment=None,
+                      merge_positions: bool = False, merger=None,
+                      compact: bool = True) -> Dict[str, torch.Tensor]:
+    """rvz.records_games' rows -> training arrays: records_to_training for continuous self-play.
+
+    rows: records_games' dict; its first m rows ("m": an int, or the 0-d device tensor, whose
+    reading is this function's one host synchronisation) are the finished games' records, games
+    in order, plies in order, "value" already relative to the player to move. They go through
+    records_to_training's own tail as black = mover, white = opponent, side = 1 (a position from
+    its mover's side, the equivalence rvz_replay_batch relies on), so every option means what it
+    means there and the result carries the same keys: exact_endgame, exact_policy (with solver,
+    moves_solver, exact_node_limit, exact_wld), merge_positions (merger), symmetries (augment,
+    symmetry_seed) and compact, which defaults to True here: "mover" and "opponent" in place of
+    "states", the rows a rvz.ReplayBuffer holds (compact=False calls `canonical` for the planes).
+    Every target those options compute is relative to the mover, so they compose with the value
+    targets rows carries."""
+    if symmetries not in (None, "all", "random"):
+        raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
+    if compact and symmetries is not None:
+        raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
+                         f"symmetries must be None, not {symmetries!r}")
+    if canonical is None:
+        canonical = board_canonical
+    m = int(rows["m"])
+    black, white = rows["mover"][:m].contiguous(), rows["opponent"][:m].contiguous()
+    side = torch.ones(m, dtype=torch.int32, device=black.device)
+    st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
+                      torch.zeros_like(side)], dim=1).contiguous()
+    states = (canonical(black, white, st, board_size)
+              if symmetries is None and not merge_positions and not compact else None)
+    return _training_tail(black, white, st, states, rows["policy"][:m],
+                          rows["value"][:m].reshape(-1), board_size, canonical, exact_endgame,
+                          solver, exact_node_limit, exact_wld, exact_policy, moves_solver,
+                          symmetries, symmetry_seed, augment, merge_positions, merger, compact)
 
 
 def adjudicate(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int,

@@ -721,6 +721,75 @@ int rvz_replay_priority(int32_t capacity, float *weight /* [capacity], in/out */
                         float *out_priority /* [nb], nullable */,
                         int32_t *out_state /* [nb], nullable */, void *hip_stream);
 
+/* ---- continuous self-play records: a window of autoreset play cut into finished games -------
+ * rvz_play with reset = 1 keeps every slot busy: a finished game restarts at once, and a slot's
+ * column of the records (rec_black / rec_white / rec_side / rec_p / hist at [ply][game]) holds
+ * one game after another. rvz_records_games (csrc/rvz_records.hip) turns a window of such records
+ * into the compact rows a replay ring holds: it finds the game boundaries, recovers each finished
+ * game's winner by the engine's own rules, gives every record its value target relative to its
+ * mover, holds back the games that are still open and compacts the rest. It is stateless, on
+ * caller arrays (device pointers), asynchronous on hip_stream and graph-capturable: no
+ * allocation, no copy, no memset, no synchronisation; the scratch needs no preparation; no
+ * workgroup waits on another (three consecutive launches); every output element below is written
+ * exactly once; records are checked in the kernel, no host synchronisation. No atomics and no
+ * floating-point arithmetic but one conversion: the outputs are a pure function of the inputs and
+ * emit_from, independent of timing and launch geometry.
+ *
+ * The walk, per slot g, over the plies p = 0 .. plies - 1 in order. There is at most one open
+ * segment, and an expected position (black, white, side, and the engine's count of passes in a
+ * row) that exists exactly while a segment is open.
+ *   rec_idx[p][g] < 0: no record at this ply (a game already over without reset, a ply beyond a
+ *     ply_budget, the caller's pre-fill): out_state = -1; the open segment and the expectation
+ *     stay as they are.
+ *   Otherwise the record is (black, white, side, idx). It is malformed if black & white != 0, a
+ *     bit at or above S*S is set, side is not 1 or 2, idx > S*S, or make_move refuses the move:
+ *     the make_move of csrc/rvz_rules.hip.h the engine plays by (the wrap-around quirk, the
+ *     auto-pass, the game end, set_winner), idx == S*S being the pass. A malformed record gets
+ *     out_state = -5, the open segment is abandoned and the expectation cleared.
+ *   If a segment is open and (black, white, side) differs from the expectation, the chain is
+ *     broken: the open segment is abandoned (every record of it gets out_state = 3) and a new
+ *     segment starts at this record.
+ *   If no segment is open, one starts here, with no passes in a row behind it; it is headless
+ *     iff the record is not the start position with black to move.
+ *   The move is applied. If the game is now over, the segment ends at p with winner w (0 draw,
+ *     1, 2): for p >= emit_from every record of it is emitted (out_state = 1), for p < emit_from
+ *     every record gets out_state = 2 (an earlier window emitted it); no segment is open
+ *     afterwards. Otherwise the expectation becomes the position after the move.
+ *   After the last ply, the records of a segment still open get out_state = 0.
+ * Emitted rows are slot-major: slots in increasing g, within a slot in increasing p (games in
+ * order, plies in order). *out_m is their number; rows at and above it are not written. Row j of
+ * the record at (p, g), whose segment ended with winner w:
+ *   out_src[j]      = p * n_games + g
+ *   out_mover[j]    = side == 1 ? black : white, out_opponent[j] the other board
+ *   out_policy[j][a] = (float) rec_p[p][g][a]     IEEE round to nearest
+ *   out_value[j]    = 0 if w == 0, +1 if w == side, else -1
+ * out_stats: [0] emitted rows, [1] emitted games, [2] open records, [3] abandoned records,
+ * [4] malformed records, [5] emitted games that are headless, [6] records in state 2, [7] 0.
+ * Carry: a game has at most S*S - 4 records (every committed ply places a disc), so a caller that
+ * keeps the last C = S*S - 4 plies of a window in front of the next K new ones and passes
+ * emit_from = C emits every finished game exactly once, whole.
+ * rvz_records_scratch_size: the scratch's bytes (8 + 28 per slot and 8 per record, each part
+ * rounded up to 16), non-decreasing in both arguments; negative for plies < 1, n_games < 1 or
+ * plies * n_games * 37 >= 2^31.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, plies < 1, n_games < 1,
+ * plies * n_games * (S*S + 1) >= 2^31, emit_from outside [0, plies], a null pointer other than
+ * out_state, or a scratch that is not 16-byte aligned. The inputs, the scratch and the outputs
+ * must not overlap. */
+int64_t rvz_records_scratch_size(int32_t plies, int32_t n_games);
+int rvz_records_games(int32_t board_size, int32_t plies, int32_t n_games,
+                      const uint64_t *rec_black, const uint64_t *rec_white, /* [plies][n_games] */
+                      const int32_t *rec_side,                              /* [plies][n_games] */
+                      const int32_t *rec_idx,   /* [plies][n_games]: rvz_play's hist */
+                      const double *rec_p,      /* [plies][n_games][S*S+1] */
+                      int32_t emit_from, void *scratch /* 16-byte aligned */,
+                      int32_t *out_m /* [1] */,
+                      uint64_t *out_mover, uint64_t *out_opponent,  /* [plies*n_games] */
+                      float *out_policy /* [plies*n_games][S*S+1] */,
+                      float *out_value /* [plies*n_games] */,
+                      int32_t *out_src /* [plies*n_games] */,
+                      int32_t *out_state /* [plies][n_games], nullable */,
+                      int64_t *out_stats /* [8] */, void *hip_stream);
+
 /* ---- policy/value loss on the full policy target -------------------------------------------
  * AlphaZero's own loss, -pi . log p + (y - t)^2, on the whole target distribution (a merged
  * position's mean search policy, the uniform distribution over the proven-optimal moves, a visit
