@@ -7,9 +7,9 @@
 //
 // Three kinds of launch on the caller's stream, no host step between them:
 //   k_loss_rows    one wavefront per row: the malformed-row rules, then m, lse, S, Lp, H, Lv and
-//                  the agreement, each wave sum a fixed float64 butterfly (every lane ends with
-//                  the same bits). The row's {Lp, Lv, H} go to out_row; its six cross-row terms
-//                  (w, w Lp, w Lv, w H, w agree, malformed) and {lse, S} go to the scratch.
+//                  the agreement, each wave sum a fixed float64 butterfly (rvz_wave.hip.h: every
+//                  lane ends with the same bits). The row's {Lp, Lv, H} go to out_row; its six
+//                  terms (w, w Lp, w Lv, w H, w agree, malformed) and {lse, S} go to the scratch.
 //   k_loss_reduce  the cross-row tree, one launch per level: a workgroup of 1024 threads sums
 //                  RED_CHUNK = 4096 consecutive items of each of the six terms (thread t adds
 //                  items t, t + 1024, t + 2048, t + 3072 in that order; the 64 lanes of a wave by
@@ -26,12 +26,11 @@
 
 #include "../../include/rvz.h"
 #include "rvz_host.hip.h"
+#include "rvz_wave.hip.h"
 
 namespace {
 
-using rvz::board_ok;
-using rvz::launch_bs;
-using rvz::launch_bs_unchecked;
+using namespace rvz;
 
 constexpr int LOSS_WAVES = 4;                    // rows per workgroup in the two row kernels
 constexpr int LOSS_THREADS = LOSS_WAVES * 64;
@@ -41,45 +40,33 @@ constexpr int RED_CHUNK = RED_THREADS * RED_ITEMS;
 constexpr int NTERM = 6;                         // w, w Lp, w Lv, w H, w agree, malformed
 constexpr int MAX_LEVELS = 3;                    // 4096^3 > 2^31 / 37
 
-struct Layout {                                  // byte offsets into the scratch
-    int64_t hdr, aux, level[MAX_LEVELS], total;
+struct Layout {                                  // the scratch's parts
+    double *hdr, *aux, *level[MAX_LEVELS];
+    int64_t total = -1;                          // -1: bad arguments
     int32_t count[MAX_LEVELS + 1];               // items of each level; count[levels] == 1
-    int32_t levels;
+    int32_t levels = 0;
+    Layout(int32_t bs, int32_t n, void* scratch) {
+        if (!board_ok(bs) || n < 0 || (int64_t)n * (bs * bs + 1) > INT32_MAX) return;
+        Carver c(scratch);
+        hdr = c.take<double>(8);                 // [0]: W
+        aux = c.packed<double>(2 * (int64_t)n);  // {lse, S} per row
+        int32_t m = n;
+        do {                                     // level k: NTERM arrays of count[k] doubles
+            count[levels] = m;
+            level[levels] = c.packed<double>((int64_t)NTERM * m);
+            m = (m + RED_CHUNK - 1) / RED_CHUNK;
+            ++levels;
+        } while (m > 1);
+        count[levels] = 1;
+        total = c.at;
+    }
 };
-
-// false: bad arguments
-bool layout(int32_t bs, int32_t n, Layout* L) {
-    if (!board_ok(bs) || n < 0) return false;
-    if ((int64_t)n * (bs * bs + 1) > INT32_MAX) return false;
-    int64_t at = 0;
-    L->hdr = at;  at += 64;                      // [0]: W
-    L->aux = at;  at += 16 * (int64_t)n;         // {lse, S} per row
-    int32_t m = n;
-    L->levels = 0;
-    do {                                         // level k: NTERM arrays of count[k] doubles
-        L->count[L->levels] = m;
-        L->level[L->levels] = at;
-        at += 8 * (int64_t)NTERM * m;
-        m = (m + RED_CHUNK - 1) / RED_CHUNK;
-        ++L->levels;
-    } while (m > 1);
-    L->count[L->levels] = 1;
-    L->total = at;
-    return true;
-}
 
 template <int BS>
 struct LG {
     static constexpr int NPOL = BS * BS + 1;
     static constexpr int SLOTS = (NPOL + 63) / 64;      // entries a lane carries: lane, lane + 64
 };
-
-// the same bits in every lane: a + b and b + a are one sum
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
 
 // the first maximum of a row: (value, index) under "larger value, then lower index"
 __device__ __forceinline__ int wave_argmax(float v, int i) {
@@ -132,9 +119,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_rows(
             if (z[s] > zm) { zm = z[s]; zi = lane + 64 * s; }
             if (pi[s] > pm) { pm = pi[s]; pidx = lane + 64 * s; }
         }
-        float mx = zm;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+        const float mx = wave_reduce(zm, [](float a, float b) { return fmaxf(a, b); });
         const int zarg = wave_argmax(zm, zi);
         // an empty lane's pi is 0 at an index >= NPOL: ties go to the lower index, so it never wins
         const int parg = wave_argmax(pm, pidx);
@@ -268,8 +253,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_grads(
 }  // namespace
 
 extern "C" int64_t rvz_loss_scratch_size(int32_t bs, int32_t n) {
-    Layout L;
-    return layout(bs, n, &L) ? L.total : -1;
+    return Layout(bs, n, nullptr).total;
 }
 
 extern "C" int rvz_policy_value_loss(int32_t bs, int32_t n, const float* logits,
@@ -278,34 +262,30 @@ extern "C" int rvz_policy_value_loss(int32_t bs, int32_t n, const float* logits,
                                      double policy_weight, double value_weight, void* scratch,
                                      double* out_loss, double* out_row, float* grad_logits,
                                      float* grad_value, void* stream) {
-    Layout L;
-    if (!layout(bs, n, &L)) return RVZ_EINVAL;
+    const Layout L(bs, n, scratch);
+    if (L.total < 0) return RVZ_EINVAL;
     if (!(policy_weight >= 0.0 && policy_weight <= DBL_MAX) ||
         !(value_weight >= 0.0 && value_weight <= DBL_MAX))
         return RVZ_EINVAL;
-    if (n > 0 && (!logits || !value || !policy_target || !value_target || !scratch || !out_loss ||
-                  (grad_logits == nullptr) != (grad_value == nullptr) ||
-                  ((uintptr_t)scratch & 15u) != 0))
+    if (n > 0 && (!logits || !value || !policy_target || !value_target || !scratch_ok(scratch) ||
+                  !out_loss || (grad_logits == nullptr) != (grad_value == nullptr)))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
-    char* base = (char*)scratch;
-    double* hdr = (double*)(base + L.hdr);
-    double* aux = (double*)(base + L.aux);
-    double* term = (double*)(base + L.level[0]);
     hipStream_t s = (hipStream_t)stream;
-    const rvz::Geometry rows = rvz::wave_per_row(n, LOSS_WAVES);
+    const Geometry rows = wave_per_row(n, LOSS_WAVES);
 
     launch_bs_unchecked(bs, k_loss_rows<8>, k_loss_rows<6>, rows.grid, rows.block, s, n, logits,
-                        value, policy_target, value_target, weight, aux, term, out_row);
+                        value, policy_target, value_target, weight, L.aux, L.level[0], out_row);
     for (int k = 0; k < L.levels; ++k) {
-        double* dst = k + 1 < L.levels ? (double*)(base + L.level[k + 1]) : nullptr;
+        double* dst = k + 1 < L.levels ? L.level[k + 1] : nullptr;
         hipLaunchKernelGGL(k_loss_reduce, dim3(L.count[k + 1]), dim3(RED_THREADS), 0, s,
-                           L.count[k], (const double*)(base + L.level[k]), dst, policy_weight,
-                           value_weight, hdr, out_loss);
+                           L.count[k], (const double*)L.level[k], dst, policy_weight, value_weight,
+                           L.hdr, out_loss);
     }
-    if (!grad_logits) return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    if (!grad_logits) return last_launch();
     // the last launch: its error return answers for all of them
     return launch_bs(bs, k_loss_grads<8>, k_loss_grads<6>, rows.grid, rows.block, s, n, logits,
-                     value, policy_target, value_target, (const double*)aux, (const double*)term,
-                     (const double*)hdr, policy_weight, value_weight, grad_logits, grad_value);
+                     value, policy_target, value_target, (const double*)L.aux,
+                     (const double*)L.level[0], (const double*)L.hdr, policy_weight, value_weight,
+                     grad_logits, grad_value);
 }

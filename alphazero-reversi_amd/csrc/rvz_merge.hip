@@ -31,12 +31,11 @@
 
 #include "../../include/rvz.h"
 #include "rvz_host.hip.h"
+#include "rvz_wave.hip.h"
 
 namespace {
 
-using rvz::board_ok;
-using rvz::launch_bs;
-using rvz::launch_bs_unchecked;
+using namespace rvz;
 
 constexpr int MG_THREADS = 256;
 constexpr int MG_WAVES = MG_THREADS / 64;
@@ -52,40 +51,36 @@ constexpr int PENDING = -2;                      // prov[]: a well-formed row no
 
 typedef unsigned long long u64;
 
-struct Layout {                                  // byte offsets into the scratch
-    int64_t hdr, table, prov, first, cnt, gidx, sslot, mlist, bsum, sums, total;
+struct Layout {                                  // the scratch's parts
+    int32_t *hdr, *table, *prov, *first, *cnt, *gidx, *sslot, *mlist;
+    u64 *bsum, *sums;
+    int64_t total = -1;                          // -1: bad arguments
     int32_t slots, nblk;
-};
-
-int64_t up16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
-// false: bad arguments
-bool layout(int32_t bs, int32_t n, int32_t table_log2, Layout* L) {
-    if (!board_ok(bs) || n < 0) return false;
-    const int64_t np = bs * bs + 1;
-    if ((int64_t)n * np > INT32_MAX) return false;
-    int lg = table_log2;
-    if (lg == 0) {
-        while (((int64_t)1 << lg) < 2 * (int64_t)n) ++lg;
-    } else if (lg < 0 || lg > 30 || ((int64_t)1 << lg) <= n) {
-        return false;
+    Layout(int32_t bs, int32_t n, int32_t table_log2, void* scratch) {
+        const int64_t np = (int64_t)bs * bs + 1;
+        if (!board_ok(bs) || n < 0 || (int64_t)n * np > INT32_MAX) return;
+        int lg = table_log2;
+        if (lg == 0) {
+            while (((int64_t)1 << lg) < 2 * (int64_t)n) ++lg;
+        } else if (lg < 0 || lg > 30 || ((int64_t)1 << lg) <= n) {
+            return;
+        }
+        slots = (int32_t)1 << lg;
+        nblk = (n + SCAN_ROWS - 1) / SCAN_ROWS;
+        Carver c(scratch);
+        hdr = c.take<int32_t>(16);
+        table = c.take<int32_t>(slots);
+        prov = c.take<int32_t>(n);
+        first = c.take<int32_t>(n);
+        cnt = c.take<int32_t>(n);
+        gidx = c.take<int32_t>(n);
+        sslot = c.take<int32_t>(n);
+        mlist = c.take<int32_t>(n / 2 + 1);
+        bsum = c.take<u64>(nblk + 1);
+        sums = c.packed<u64>((np + 1) * (int64_t)(n / 2));   // groups of two or more: at most n/2
+        total = c.at;
     }
-    L->slots = (int32_t)1 << lg;
-    L->nblk = (n + SCAN_ROWS - 1) / SCAN_ROWS;
-    int64_t at = 0;
-    L->hdr = at;    at += 64;
-    L->table = at;  at += up16(4 * (int64_t)L->slots);
-    L->prov = at;   at += up16(4 * (int64_t)n);
-    L->first = at;  at += up16(4 * (int64_t)n);
-    L->cnt = at;    at += up16(4 * (int64_t)n);
-    L->gidx = at;   at += up16(4 * (int64_t)n);
-    L->sslot = at;  at += up16(4 * (int64_t)n);
-    L->mlist = at;  at += up16(4 * (int64_t)(n / 2 + 1));
-    L->bsum = at;   at += up16(8 * (int64_t)(L->nblk + 1));
-    L->sums = at;   at += 8 * (np + 1) * (int64_t)(n / 2);   // groups of two or more: at most n/2
-    L->total = at;
-    return true;
-}
+};
 
 template <int BS>
 struct MG {
@@ -205,29 +200,12 @@ __device__ __forceinline__ u64 row_flags(int i, const int32_t* __restrict__ prov
     return cnt[r] >= 2 ? (1ull << 32) | 1ull : 1ull;
 }
 
-// exclusive scan of v over the block's NW waves (both 32-bit halves at once: neither carries,
-// every total is at most 2^25); lds holds NW words. Every thread of the block calls it.
+// the exclusive scan of v over the block's NW waves and its total (both 32-bit halves at once:
+// neither carries, every total is at most 2^25): one step of the workgroup scan; lds: NW words
 template <int NW>
 __device__ __forceinline__ u64 block_exclusive_scan(u64 v, u64* lds, u64& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 t = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    u64 before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const u64 x = lds[w];
-        before += w < wave ? x : 0ull;
-        all += x;
-    }
-    __syncthreads();                             // lds may be reused
-    total = all;
-    return before + inc - v;
+    total = 0ull;
+    return block_scan(v, threadIdx.x & 63, threadIdx.x >> 6, NW, lds, total) - v;
 }
 
 __global__ __launch_bounds__(MG_THREADS) void k_count(int n, const int32_t* __restrict__ prov,
@@ -411,8 +389,7 @@ int blocks_for(int64_t units, int per_block) {
 }  // namespace
 
 extern "C" int64_t rvz_merge_scratch_size(int32_t bs, int32_t n, int32_t table_log2) {
-    Layout L;
-    return layout(bs, n, table_log2, &L) ? L.total : -1;
+    return Layout(bs, n, table_log2, nullptr).total;
 }
 
 extern "C" int rvz_merge_positions(int32_t bs, int32_t n, const uint64_t* black,
@@ -421,47 +398,36 @@ extern "C" int rvz_merge_positions(int32_t bs, int32_t n, const uint64_t* black,
                                    void* scratch, int32_t* out_m, int32_t* out_first,
                                    int32_t* out_count, float* out_policy, float* out_value,
                                    int32_t* out_group, void* stream) {
-    Layout L;
-    if (!layout(bs, n, table_log2, &L)) return RVZ_EINVAL;
-    if (n > 0 && (!black || !white || !status || !policy || !value || !scratch || !out_m ||
-                  !out_first || !out_count || !out_policy || !out_value || !out_group ||
-                  ((uintptr_t)scratch & 15u) != 0))
+    const Layout L(bs, n, table_log2, scratch);
+    if (L.total < 0) return RVZ_EINVAL;
+    if (n > 0 && (!black || !white || !status || !policy || !value || !scratch_ok(scratch) ||
+                  !out_m || !out_first || !out_count || !out_policy || !out_value || !out_group))
         return RVZ_EINVAL;
     if (n == 0) return RVZ_OK;
     const char* env = getenv("RVZ_MERGE_HOT");                  // "0": no LDS pre-reduction
     const int hot = !(env && env[0] == '0' && env[1] == 0);
-    char* base = (char*)scratch;
-    int32_t* hdr = (int32_t*)(base + L.hdr);
-    int32_t* table = (int32_t*)(base + L.table);
-    int32_t* prov = (int32_t*)(base + L.prov);
-    int32_t* first = (int32_t*)(base + L.first);
-    int32_t* cnt = (int32_t*)(base + L.cnt);
-    int32_t* gidx = (int32_t*)(base + L.gidx);
-    int32_t* sslot = (int32_t*)(base + L.sslot);
-    int32_t* mlist = (int32_t*)(base + L.mlist);
-    u64* bsum = (u64*)(base + L.bsum);
-    u64* sums = (u64*)(base + L.sums);
     hipStream_t s = (hipStream_t)stream;
     const dim3 block(MG_THREADS);
     const dim3 per_lane(blocks_for(n, MG_THREADS)), per_wave(blocks_for(n, MG_WAVES));
     const int ne = bs * bs + 2;
 
     hipLaunchKernelGGL(k_init, dim3(blocks_for(L.slots > n ? L.slots : n, MG_THREADS)), block, 0,
-                       s, n, L.slots, table, first, cnt, hdr);
+                       s, n, L.slots, L.table, L.first, L.cnt, L.hdr);
     launch_bs_unchecked(bs, k_validate<8>, k_validate<6>, per_wave, block, s, n, black, white,
-                        status, policy, value, prov);
-    hipLaunchKernelGGL(k_insert, per_lane, block, 0, s, n, L.slots, black, white, status, table,
-                       prov, first, cnt);
-    hipLaunchKernelGGL(k_count, dim3(L.nblk), block, 0, s, n, prov, first, cnt, bsum);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(SCAN_TOP), 0, s, L.nblk, bsum, hdr, out_m);
-    hipLaunchKernelGGL(k_assign, dim3(L.nblk), block, 0, s, n, prov, first, cnt, bsum, gidx, sslot,
-                       mlist, out_first, out_count);
+                        status, policy, value, L.prov);
+    hipLaunchKernelGGL(k_insert, per_lane, block, 0, s, n, L.slots, black, white, status, L.table,
+                       L.prov, L.first, L.cnt);
+    hipLaunchKernelGGL(k_count, dim3(L.nblk), block, 0, s, n, L.prov, L.first, L.cnt, L.bsum);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(SCAN_TOP), 0, s, L.nblk, L.bsum, L.hdr, out_m);
+    hipLaunchKernelGGL(k_assign, dim3(L.nblk), block, 0, s, n, L.prov, L.first, L.cnt, L.bsum,
+                       L.gidx, L.sslot, L.mlist, out_first, out_count);
     hipLaunchKernelGGL(k_zero, dim3(blocks_for((int64_t)(n / 2) * ne, 4 * MG_THREADS)), block, 0,
-                       s, hdr, ne, sums);
+                       s, L.hdr, ne, L.sums);
     const dim3 chunks((n + ACC_ROWS - 1) / ACC_ROWS);
     launch_bs_unchecked(bs, k_accumulate<8>, k_accumulate<6>, chunks, block, s, n, hot, policy,
-                        value, prov, gidx, sslot, cnt, sums, out_policy, out_value, out_group);
+                        value, L.prov, L.gidx, L.sslot, L.cnt, L.sums, out_policy, out_value,
+                        out_group);
     // the last of the nine launches: its error return answers for all of them
     return launch_bs(bs, k_divide<8>, k_divide<6>, dim3(blocks_for(n / 2, MG_WAVES)), block, s,
-                     hdr, mlist, out_count, sums, out_policy, out_value);
+                     L.hdr, L.mlist, out_count, L.sums, out_policy, out_value);
 }

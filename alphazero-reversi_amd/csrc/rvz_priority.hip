@@ -25,6 +25,7 @@
 #include "../../include/rvz.h"
 #include "rvz_host.hip.h"
 #include "rvz_pow.hip.h"
+#include "rvz_wave.hip.h"
 
 namespace {
 
@@ -55,15 +56,9 @@ __global__ __launch_bounds__(ISW_THREADS) void k_isw_min(int nb, const float* __
             m = b < m ? b : m;
         }
     }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)m, d, 64);
-        m = o < m ? o : m;
-    }
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_reduce<1>(&m, threadIdx.x & 63, threadIdx.x >> 6, ISW_THREADS / 64, part,
+                        [](uint32_t a, uint32_t b) { return b < a ? b : a; });
     if (threadIdx.x == 0) {
-        for (int w = 1; w < ISW_THREADS / 64; ++w) m = part[w] < m ? part[w] : m;
         *min_bits = m;
         if (out_min_prob) *out_min_prob = m == NO_PROB ? 0.0f : __uint_as_float(m);
     }
@@ -84,12 +79,22 @@ __global__ __launch_bounds__(PRI_THREADS) void k_isw_weight(int nb, const float*
 }
 
 // ---------------------------------------------------------------- the priorities
-inline int64_t pri_table(int32_t nb) {           // T: the power of two >= max(2 nb, 64)
-    int64_t t = 64;
-    while (t < 2 * (int64_t)nb) t <<= 1;
-    return t;
-}
-inline int64_t pri_rows_bytes(int32_t nb) { return ((int64_t)nb * 4 + 15) & ~(int64_t)15; }
+// the scratch: the header, pri [nb], the table's key [T] and, right behind it, val [T]; T: the
+// power of two >= max(2 nb, 64)
+struct Layout {
+    int64_t T = 64, bytes;
+    uint32_t *head, *key, *val;
+    float* pri;
+    Layout(int32_t nb, void* scratch) {
+        while (T < 2 * (int64_t)nb) T <<= 1;
+        Carver c(scratch);
+        head = c.take<uint32_t>(PRI_HEAD / 4);
+        pri = c.take<float>(nb);
+        key = c.take<uint32_t>(T);
+        val = c.take<uint32_t>(T);
+        bytes = c.at;
+    }
+};
 
 __device__ __forceinline__ uint32_t slot_hash(uint32_t s) {             // murmur3's finaliser
     s ^= s >> 16;
@@ -145,11 +150,7 @@ __global__ __launch_bounds__(PRI_THREADS) void k_pri_rows(
         }
         pri[r] = p;                              // 0: an invalid row (a valid one is >= floor > 0)
     }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)bits, d, 64);
-        bits = o > bits ? o : bits;
-    }
+    bits = wave_reduce(bits, [](uint32_t a, uint32_t b) { return b > a ? b : a; });
     if ((threadIdx.x & 63) == 0 && bits) atomicMax(&head[0], bits);
 }
 
@@ -195,8 +196,7 @@ extern "C" int rvz_replay_is_weight(int32_t nb, const float* prob, const int32_t
                                     float* out_min_prob, void* stream) {
     if (nb < 0 || !(beta >= 0.0 && beta <= 1.0)) return RVZ_EINVAL;     // NaN fails
     if (nb == 0) return RVZ_OK;
-    if (!prob || !slot || !out_weight || !scratch || ((uintptr_t)scratch & 15u) != 0)
-        return RVZ_EINVAL;
+    if (!prob || !slot || !out_weight || !scratch_ok(scratch)) return RVZ_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     uint32_t* min_bits = (uint32_t*)scratch;
     hipLaunchKernelGGL(k_isw_min, dim3(1), dim3(ISW_THREADS), 0, s, nb, prob, slot, min_bits,
@@ -204,12 +204,12 @@ extern "C" int rvz_replay_is_weight(int32_t nb, const float* prob, const int32_t
     const Geometry g = thread_per_row(nb);
     hipLaunchKernelGGL(k_isw_weight, g.grid, g.block, 0, s, nb, prob, slot, beta,
                        (const uint32_t*)min_bits, out_weight);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return last_launch();
 }
 
 extern "C" int64_t rvz_replay_priority_scratch_size(int32_t nb) {
     if (nb < 0 || nb > PRI_MAX_NB) return -1;
-    return PRI_HEAD + pri_rows_bytes(nb) + 8 * pri_table(nb);
+    return Layout(nb, nullptr).bytes;
 }
 
 extern "C" int rvz_replay_priority(int32_t capacity, float* weight, int32_t nb,
@@ -223,22 +223,18 @@ extern "C" int rvz_replay_priority(int32_t capacity, float* weight, int32_t nb,
         !(floor_ >= PRI_MIN_FLOOR && floor_ <= cap && cap <= PRI_MAX_CAP))
         return RVZ_EINVAL;
     if (nb == 0) return RVZ_OK;
-    if (!weight || !slot || !row || !scratch || ((uintptr_t)scratch & 15u) != 0)
-        return RVZ_EINVAL;
+    if (!weight || !slot || !row || !scratch_ok(scratch)) return RVZ_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t T = pri_table(nb);
-    uint32_t* head = (uint32_t*)scratch;
-    float* pri = (float*)((char*)scratch + PRI_HEAD);
-    uint32_t* key = (uint32_t*)((char*)scratch + PRI_HEAD + pri_rows_bytes(nb));
-    uint32_t* val = key + T;
-    const uint32_t mask = (uint32_t)(T - 1);
-    const Geometry c = strided(2 * T, PRI_THREADS, PRI_THREADS);
-    hipLaunchKernelGGL(k_pri_clear, c.grid, c.block, 0, s, head, key, 2 * T);
+    const Layout l(nb, scratch);
+    const uint32_t mask = (uint32_t)(l.T - 1);
+    const Geometry c = strided(2 * l.T, PRI_THREADS, PRI_THREADS);
+    hipLaunchKernelGGL(k_pri_clear, c.grid, c.block, 0, s, l.head, l.key, 2 * l.T);
     const Geometry g = thread_per_row(nb);
     hipLaunchKernelGGL(k_pri_rows, g.grid, g.block, 0, s, capacity, nb, slot, row, policy_coef,
-                       value_coef, subtract_entropy, alpha, floor_, cap, head, pri, key, val, mask);
-    hipLaunchKernelGGL(k_pri_write, g.grid, g.block, 0, s, nb, slot, (const uint32_t*)head,
-                       (const float*)pri, (const uint32_t*)key, (const uint32_t*)val, mask, weight,
-                       max_priority, out_priority, out_state);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+                       value_coef, subtract_entropy, alpha, floor_, cap, l.head, l.pri, l.key,
+                       l.val, mask);
+    hipLaunchKernelGGL(k_pri_write, g.grid, g.block, 0, s, nb, slot, (const uint32_t*)l.head,
+                       (const float*)l.pri, (const uint32_t*)l.key, (const uint32_t*)l.val, mask,
+                       weight, max_priority, out_priority, out_state);
+    return last_launch();
 }

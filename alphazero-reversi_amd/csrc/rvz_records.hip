@@ -14,9 +14,9 @@
 // revisited once at most (segments are disjoint), and a lane reads back only words it wrote
 // itself. The slot's seven counts go to the scratch, slot-minor.
 //
-// k_rec_scan, one workgroup: the exclusive scan of the slots' row counts (a shuffle scan of 64-bit
-// items within each wave, the waves' totals through LDS, a running carry from chunk to chunk, as
-// k_cdf_scan) and the seven sums in 64 bits; it writes out_m and out_stats.
+// k_rec_scan, one workgroup: the exclusive scan of the slots' row counts (the chunked workgroup
+// scan of rvz_wave.hip.h, as k_cdf_scan) and the seven sums in 64 bits; it writes out_m and
+// out_stats.
 //
 // k_rec_rows, a wavefront per record, lane = policy entry (on 8x8 lane 0 also carries the pass
 // entry, as in rvz_policy_value_loss): out_state of every record, and for an emitted one the row
@@ -28,6 +28,7 @@
 #include "../../include/rvz.h"
 #include "rvz_host.hip.h"
 #include "rvz_rules.hip.h"
+#include "rvz_wave.hip.h"
 
 namespace {
 
@@ -52,22 +53,21 @@ __device__ __forceinline__ int word_state(int32_t w) { return (w & 0xff) - 8; }
 __device__ __forceinline__ int word_side(int32_t w) { return (w >> 8) & 3; }
 __device__ __forceinline__ int word_value(int32_t w) { return ((w >> 16) & 3) - 1; }
 
-inline int64_t up16(int64_t bytes) { return (bytes + 15) & ~(int64_t)15; }
-
-// the scratch: offset int64 [n_games], counts int32 [7][n_games], info int32 [records],
-// rank int32 [records]; each part 16-byte aligned
+// the scratch: offset [n_games], counts [7][n_games], info [records], rank [records]; each part
+// 16-byte aligned
 struct Layout {
-    int64_t offset, counts, info, rank, bytes;
+    int64_t* offset;
+    int32_t *counts, *info, *rank;
+    int64_t bytes;
+    Layout(int64_t plies, int64_t n_games, void* scratch) {
+        Carver c(scratch);
+        offset = c.take<int64_t>(n_games);
+        counts = c.take<int32_t>(N_COUNTS * n_games);
+        info = c.take<int32_t>(plies * n_games);
+        rank = c.take<int32_t>(plies * n_games);
+        bytes = c.at;
+    }
 };
-inline Layout layout(int64_t plies, int64_t n_games) {
-    Layout l;
-    l.offset = 0;
-    l.counts = up16(8 * n_games);
-    l.info = l.counts + up16(4 * N_COUNTS * n_games);
-    l.rank = l.info + up16(4 * plies * n_games);
-    l.bytes = l.rank + up16(4 * plies * n_games);
-    return l;
-}
 
 template <int BS>
 __global__ __launch_bounds__(WALK_THREADS) void k_rec_walk(
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_rec_scan(int n_games,
                                                            int32_t* __restrict__ out_m,
                                                            int64_t* __restrict__ out_stats) {
     __shared__ int64_t part[2][SCAN_WAVES];
-    __shared__ int64_t sums[SCAN_WAVES][N_COUNTS];
+    __shared__ int64_t sums[SCAN_WAVES * N_COUNTS];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const size_t G = (size_t)n_games;
@@ -182,34 +182,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_rec_scan(int n_games,
 #pragma unroll
             for (int k = 0; k < N_COUNTS; ++k) s[k] += counts[k * G + i];
         }
-        int64_t v = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const int64_t up = __shfl_up((long long)v, d, 64);
-            if (lane >= d) v += up;
-        }
-        if (lane == 63) part[c][wave] = v;
-        __syncthreads();
-        int64_t before = carry;
-        for (int w = 0; w < SCAN_WAVES; ++w) {
-            const int64_t t = part[c][w];
-            if (w < wave) before += t;
-            carry += t;
-        }
-        if (i < n_games) offset[i] = before + v - mine;
+        const int64_t upto = block_scan(mine, lane, wave, SCAN_WAVES, part[c], carry);
+        if (i < n_games) offset[i] = upto - mine;
     }
-#pragma unroll
-    for (int k = 0; k < N_COUNTS; ++k) {
-#pragma unroll
-        for (int d = 32; d; d >>= 1) s[k] += __shfl_xor((long long)s[k], d, 64);
-        if (lane == 0) sums[wave][k] = s[k];
-    }
-    __syncthreads();
+    const int64_t all = block_reduce<N_COUNTS>(s, lane, wave, SCAN_WAVES, sums, Sum());
     if (threadIdx.x < 8) {
-        int64_t all = 0;
-        if (threadIdx.x < N_COUNTS)
-            for (int w = 0; w < SCAN_WAVES; ++w) all += sums[w][threadIdx.x];
-        out_stats[threadIdx.x] = all;                                   // [7] is 0
+        out_stats[threadIdx.x] = all;                                   // thread k: count k; [7] is 0
         if (threadIdx.x == 0) *out_m = (int32_t)all;                    // rows <= records < 2^31
     }
 }
@@ -256,7 +234,7 @@ inline bool shape_ok(int64_t plies, int64_t n_games, int npol) {
 
 extern "C" int64_t rvz_records_scratch_size(int32_t plies, int32_t n_games) {
     if (!shape_ok(plies, n_games, 37)) return -1;   // too many records for either board
-    return layout(plies, n_games).bytes;
+    return Layout(plies, n_games, nullptr).bytes;
 }
 
 extern "C" int rvz_records_games(int32_t bs, int32_t plies, int32_t n_games,
@@ -269,27 +247,22 @@ extern "C" int rvz_records_games(int32_t bs, int32_t plies, int32_t n_games,
     if (!board_ok(bs) || !shape_ok(plies, n_games, bs * bs + 1) || emit_from < 0 ||
         emit_from > plies)
         return RVZ_EINVAL;
-    if (!rec_black || !rec_white || !rec_side || !rec_idx || !rec_p || !scratch || !out_m ||
-        !out_mover || !out_opponent || !out_policy || !out_value || !out_src || !out_stats ||
-        ((uintptr_t)scratch & 15u) != 0)
+    if (!rec_black || !rec_white || !rec_side || !rec_idx || !rec_p || !scratch_ok(scratch) ||
+        !out_m || !out_mover || !out_opponent || !out_policy || !out_value || !out_src ||
+        !out_stats)
         return RVZ_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const Layout l = layout(plies, n_games);
-    char* base = (char*)scratch;
-    int64_t* offset = (int64_t*)(base + l.offset);
-    int32_t* counts = (int32_t*)(base + l.counts);
-    int32_t* info = (int32_t*)(base + l.info);
-    int32_t* rank = (int32_t*)(base + l.rank);
+    const Layout l(plies, n_games, scratch);
     const int records = plies * n_games;
     launch_bs_unchecked(bs, k_rec_walk<8>, k_rec_walk<6>,
                         dim3((n_games + WALK_THREADS - 1) / WALK_THREADS), dim3(WALK_THREADS), s,
-                        plies, n_games, rec_black, rec_white, rec_side, rec_idx, emit_from, info,
-                        rank, counts);
+                        plies, n_games, rec_black, rec_white, rec_side, rec_idx, emit_from, l.info,
+                        l.rank, l.counts);
     hipLaunchKernelGGL(k_rec_scan, dim3(1), dim3(SCAN_THREADS), 0, s, n_games,
-                       (const int32_t*)counts, offset, out_m, out_stats);
+                       (const int32_t*)l.counts, l.offset, out_m, out_stats);
     const Geometry g = strided(records, ROWS_WAVES, ROWS_THREADS);
     return launch_bs(bs, k_rec_rows<8>, k_rec_rows<6>, g.grid, g.block, s, records, n_games,
-                     rec_black, rec_white, rec_p, (const int32_t*)info, (const int32_t*)rank,
-                     (const int64_t*)offset, out_mover, out_opponent, out_policy, out_value,
+                     rec_black, rec_white, rec_p, (const int32_t*)l.info, (const int32_t*)l.rank,
+                     (const int64_t*)l.offset, out_mover, out_opponent, out_policy, out_value,
                      out_src, out_state);
 }

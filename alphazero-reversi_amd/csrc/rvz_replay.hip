@@ -30,6 +30,7 @@
 #include "rvz_philox.hip.h"
 #include "rvz_rules.hip.h"
 #include "rvz_symmetry.hip.h"
+#include "rvz_wave.hip.h"
 
 namespace {
 
@@ -45,24 +46,34 @@ constexpr int CDF_ADD_MAX_BLOCKS = 1 << 16;      // grid-stride beyond that
 
 inline bool tile_ok(int t) { return t == 0 || (t >= 6 && t <= 12); }
 
-// the scan's levels for n rows at tile 2^tl: cnt[0] = n, cnt[k + 1] = ceil(cnt[k] / tile), down to
-// cnt[L] == 1; returns L >= 1
-inline int cdf_levels(int64_t n, int tl, int64_t* cnt) {
-    int L = 0;
-    cnt[0] = n;
-    do {
-        cnt[L + 1] = (cnt[L] + ((int64_t)1 << tl) - 1) >> tl;
-        ++L;
-    } while (cnt[L] > 1);
-    return L;
-}
+// The table of n rows at tile 2^tile_log2 (0: the default): the four header words, then the scan's
+// levels, cnt[0] = n, cnt[k + 1] = ceil(cnt[k] / tile), down to cnt[L] == 1 (L >= 1). Level 0 is C
+// (tot[0]; it has no counts); level k >= 1 is the totals tot[k] and the invalid counts inv[k] of
+// level k - 1's tiles, cnt[k] words each.
+struct CdfLayout {
+    int L = 0, tl;
+    int64_t cnt[CDF_MAX_LEVELS + 1], bytes;
+    uint64_t *head, *tot[CDF_MAX_LEVELS + 1], *inv[CDF_MAX_LEVELS + 1];
+    CdfLayout(int64_t n, int tile_log2, void* cdf) : tl(tile_log2 ? tile_log2 : CDF_TILE_LOG2) {
+        Carver c(cdf);
+        head = c.packed<uint64_t>(CDF_HEAD);
+        cnt[0] = n;
+        tot[0] = c.packed<uint64_t>(n);
+        do {
+            cnt[L + 1] = (cnt[L] + ((int64_t)1 << tl) - 1) >> tl;
+            ++L;
+            tot[L] = c.packed<uint64_t>(cnt[L]);
+            inv[L] = c.packed<uint64_t>(cnt[L]);
+        } while (cnt[L] > 1);
+        bytes = up16(c.at);
+    }
+};
 
 // One tile of one level: the local inclusive scan of the tile's items into vals, the tile's total
 // into tot_out[tile] and its invalid weights into inv_out[tile]. LEAF: item i is q of the weight
 // of logical row i (slot (start + i) % capacity) and vals is C; else item i is vals[i] (the totals
 // of the level below, scanned in place) and its invalid count is inv_in[i]. A chunk of blockDim.x
-// items per step: a shuffle scan of the 64-bit items within each wave, the waves' totals through
-// LDS (two buffers, so one barrier a chunk), a running carry from chunk to chunk.
+// items per step of the workgroup scan (rvz_wave.hip.h; two LDS buffers, so one barrier a chunk).
 template <bool LEAF>
 __global__ __launch_bounds__(CDF_THREADS) void k_cdf_scan(
     const float* __restrict__ weight, int capacity, int start, uint64_t* vals,
@@ -92,30 +103,13 @@ __global__ __launch_bounds__(CDF_THREADS) void k_cdf_scan(
                 nbad += inv_in[i];
             }
         }
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t up = __shfl_up((unsigned long long)v, d, 64);
-            if (lane >= d) v += up;
-        }
-        if (lane == 63) part[c][wave] = v;
-        __syncthreads();
-        uint64_t before = carry;
-        for (int w = 0; w < waves; ++w) {
-            const uint64_t p = part[c][w];
-            if (w < wave) before += p;
-            carry += p;
-        }
-        if (i < end) vals[i] = v + before;
+        v = block_scan(v, lane, wave, waves, part[c], carry);
+        if (i < end) vals[i] = v;
     }
-#pragma unroll
-    for (int d = 32; d; d >>= 1) nbad += __shfl_xor((unsigned long long)nbad, d, 64);
-    if (lane == 0) bad[wave] = nbad;
-    __syncthreads();
+    nbad = block_reduce<1>(&nbad, lane, wave, waves, bad, Sum());
     if (threadIdx.x == 0) {
-        uint64_t all = 0ull;
-        for (int w = 0; w < waves; ++w) all += bad[w];
         tot_out[blockIdx.x] = carry;
-        inv_out[blockIdx.x] = all;
+        inv_out[blockIdx.x] = nbad;
     }
 }
 
@@ -279,11 +273,7 @@ extern "C" int rvz_replay_batch(int32_t bs, int32_t capacity, const uint64_t* mo
 
 extern "C" int64_t rvz_replay_cdf_size(int32_t capacity, int32_t tile_log2) {
     if (capacity < 1 || !tile_ok(tile_log2)) return -1;
-    int64_t cnt[CDF_MAX_LEVELS + 1];
-    const int L = cdf_levels(capacity, tile_log2 ? tile_log2 : CDF_TILE_LOG2, cnt);
-    int64_t words = CDF_HEAD + cnt[0];
-    for (int k = 1; k <= L; ++k) words += 2 * cnt[k];                  // totals and counts
-    return 8 * ((words + 1) & ~(int64_t)1);
+    return CdfLayout(capacity, tile_log2, nullptr).bytes;
 }
 
 extern "C" int rvz_replay_cdf(int32_t capacity, const float* weight, int32_t start, int32_t live,
@@ -292,24 +282,14 @@ extern "C" int rvz_replay_cdf(int32_t capacity, const float* weight, int32_t sta
         !tile_ok(tile_log2))
         return RVZ_EINVAL;
     if (live == 0) return RVZ_OK;
-    if (!weight || !cdf || ((uintptr_t)cdf & 15u) != 0) return RVZ_EINVAL;
-    const int tl = tile_log2 ? tile_log2 : CDF_TILE_LOG2;
+    if (!weight || !scratch_ok(cdf)) return RVZ_EINVAL;
+    const CdfLayout l(live, tile_log2, cdf);                            // of the live rows alone
+    const int tl = l.tl, L = l.L;
     const int tile = 1 << tl;
     const int threads = tile < CDF_THREADS ? tile : CDF_THREADS;
     hipStream_t s = (hipStream_t)stream;
-    int64_t cnt[CDF_MAX_LEVELS + 1];
-    const int L = cdf_levels(live, tl, cnt);
-    // level k's totals tot[k] and counts inv[k], cnt[k] words each, behind C (level 0's values)
-    uint64_t* head = (uint64_t*)cdf;
-    uint64_t *tot[CDF_MAX_LEVELS + 1], *inv[CDF_MAX_LEVELS + 1];
-    tot[0] = head + CDF_HEAD;
-    inv[0] = nullptr;
-    uint64_t* next = tot[0] + cnt[0];
-    for (int k = 1; k <= L; ++k) {
-        tot[k] = next;
-        inv[k] = next + cnt[k];
-        next += 2 * cnt[k];
-    }
+    const int64_t* cnt = l.cnt;
+    uint64_t *head = l.head, *const *tot = l.tot, *const *inv = l.inv;
     hipLaunchKernelGGL(k_cdf_scan<true>, dim3((unsigned)cnt[1]), dim3(threads), 0, s, weight,
                        capacity, start, tot[0], (const uint64_t*)nullptr, cnt[0], tile, tot[1],
                        inv[1]);
@@ -329,7 +309,7 @@ extern "C" int rvz_replay_cdf(int32_t capacity, const float* weight, int32_t sta
         hipLaunchKernelGGL(k_cdf_add, dim3(1), dim3(CDF_THREADS), 0, s, tot[0], cnt[0], tl,
                            (const uint64_t*)tot[1], head, (const uint64_t*)tot[1],
                            (const uint64_t*)inv[1], start, live);
-    return hipGetLastError() == hipSuccess ? RVZ_OK : RVZ_EHIP;
+    return last_launch();
 }
 
 extern "C" int rvz_replay_batch_weighted(int32_t bs, int32_t capacity, const uint64_t* mover,
@@ -342,7 +322,7 @@ extern "C" int rvz_replay_batch_weighted(int32_t bs, int32_t capacity, const uin
                                          int32_t* out_slot, int32_t* out_sym, float* out_prob,
                                          void* stream) {
     return batch<WeightedDraw>(bs, capacity, mover, opponent, policy, value, start, live, nb, idx,
-                               sym, {(const uint64_t*)cdf, word, out_prob},
-                               cdf && ((uintptr_t)cdf & 15u) == 0, random_sym, seed, step,
-                               out_states, out_policy, out_value, out_slot, out_sym, stream);
+                               sym, {(const uint64_t*)cdf, word, out_prob}, scratch_ok(cdf),
+                               random_sym, seed, step, out_states, out_policy, out_value, out_slot,
+                               out_sym, stream);
 }

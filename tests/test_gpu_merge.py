@@ -122,6 +122,29 @@ def test_distinct_rows_are_the_identity(bs):
     _assert_equal(got, M.merge(*rows, bs), n)
 
 
+def test_distinct_rows_past_one_block_sum_per_thread():
+    """The identity again at n = 2^20 + 1025 on 6x6: more than 1,024 scan blocks, so each thread of
+    k_scan_blocks carries two block sums. The rows are made on the device, a counter split over
+    the two bitboards under disjoint masks (distinct, disjoint, on the board, black to move), and
+    the expectation needs no reference run."""
+    bs, n = 6, 1024 * 1024 + 1025
+    i = torch.arange(n, dtype=torch.int64, device="cuda")
+    status = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
+    status[:, 0], status[:, 2] = 1, -1
+    gen = torch.Generator(device="cuda").manual_seed(5)
+    dev = (i & 0x3FF, i & ~0x3FF, status,
+           torch.rand((n, bs * bs + 1), device="cuda", generator=gen),
+           torch.rand((n,), device="cuda", generator=gen) * 2 - 1)
+    assert int((i & ~0x3FF).max()) < 1 << (bs * bs)
+    got = _raw(bs, dev)
+    assert int(got["m"][0]) == n
+    assert torch.equal(got["policy"].view(torch.int32), dev[3].view(torch.int32))
+    assert torch.equal(got["value"].view(torch.int32), dev[4].view(torch.int32))
+    ar = torch.arange(n, dtype=torch.int32, device="cuda")
+    assert torch.equal(got["first"], ar) and torch.equal(got["group"], ar)
+    assert bool((got["count"] == 1).all())
+
+
 @pytest.mark.parametrize("bs", [8, 6])
 def test_probe_chains(bs):
     """1,000 distinct rows in 1,024 slots (load 0.98) and in the default table: equal bytes; so

@@ -44,7 +44,7 @@ def _same(out, ref, what=""):
 
 
 @pytest.mark.parametrize("bs,P,G", [(6, 40, 1), (6, 40, 63), (6, 40, 64), (6, 40, 65),
-                                    (6, 40, 130), (8, 70, 65)])
+                                    (6, 40, 130), (8, 70, 65), (6, 40, 1025), (6, 40, 2049)])
 def test_synthetic_windows(oracle, bs, P, G):
     """Games restarting right after they end, slots opening inside a game, gaps, pass-index
     records: emit_from at 0, in the middle and at P (nothing emitted)."""
