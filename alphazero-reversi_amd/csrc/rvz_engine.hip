@@ -40,6 +40,7 @@
 #include "../../include/rvz.h"
 #include "rvz_h2.hip.h"
 #include "rvz_host.hip.h"
+#include "rvz_openings.hip.h"
 #include "rvz_philox.hip.h"
 #include "rvz_pow.hip.h"
 #include "rvz_rules.hip.h"
@@ -122,6 +123,14 @@ struct View {  // kernel argument: device pointers + sizes
     // call's temperature
     int sched_from;
     double sched_late;
+    // Opening pool (rvz_env_openings; open_n = 0: off): a game reset with seed s starts from row
+    // opening_index(s, open_salt, open_n) of the engine's own copy of the pool, with black or
+    // white (open_side: 1 | 2) to move
+    int open_n;
+    uint32_t open_salt;
+    const uint64_t* open_black;
+    const uint64_t* open_white;
+    const int32_t* open_side;
 };
 
 // A link names an expanded node of the previous search's tree (the same position as the new
@@ -1146,7 +1155,8 @@ __global__ __launch_bounds__(256) void k_action_probs(int n_rows, const int32_t*
 
 // reset: new game (board.py:25-39) + np.random.seed(seed) random_sample() stream.
 // a fresh game g seeded with `seed` (np.random.seed semantics): MT19937 init, its first draws,
-// the start position (one wave; k is the wave's 624-word key scratch in LDS)
+// the start position, or with an opening pool set (rvz_env_openings) the pool row the seed picks
+// (one wave; k is the wave's 624-word key scratch in LDS)
 template <int BS>
 __device__ __forceinline__ void reset_game(const View& v, int g, int lane, uint32_t seed,
                                            uint32_t* k) {
@@ -1177,6 +1187,12 @@ __device__ __forceinline__ void reset_game(const View& v, int g, int lane, uint3
         st.black = Geo<BS>::START_BLACK;
         st.white = Geo<BS>::START_WHITE;
         st.side = 1; st.over = 0; st.winner = -1; st.passed = 0;
+        if (v.open_n > 0) {   // a row of the opening pool, picked by the seed (no draw consumed)
+            const int i = opening_index(seed, v.open_salt, v.open_n);
+            st.black = v.open_black[i];
+            st.white = v.open_white[i];
+            st.side = v.open_side[i];
+        }
         store_game(v, g, st);
         v.rng_pos[g] = 0;
         v.pend[g] = 0;
@@ -1235,6 +1251,22 @@ __global__ void k_board_legal(int n, const uint64_t* __restrict__ black,
     const int side = status[4 * i];
     const uint64_t P = side == 1 ? black[i] : white[i], O = side == 1 ? white[i] : black[i];
     out[i] = legal<BS>(P, O);
+}
+
+// rvz_env_openings' row rules, a thread per pool row: *first_bad ends as the lowest row with
+// overlapping discs, a bit at or above S*S, a side other than 1 | 2 or a mover without a legal
+// square (the caller sets it to INT_MAX)
+template <int BS>
+__global__ void k_openings_validate(int n, const uint64_t* __restrict__ black,
+                                    const uint64_t* __restrict__ white,
+                                    const int32_t* __restrict__ side, int32_t* first_bad) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t b = black[i], w = white[i];
+    const int sd = side[i];
+    bool bad = (b & w) != 0 || ((b | w) & ~Geo<BS>::FULL) != 0 || (sd != 1 && sd != 2);
+    if (!bad) bad = legal<BS>(sd == 1 ? b : w, sd == 1 ? w : b) == 0;
+    if (bad) atomicMin(first_bad, i);
 }
 
 template <int BS>
@@ -1314,6 +1346,8 @@ struct rvz_engine {
     double gate_frac = -1.0, gate_us = 0.0, gate_late_us = 0.0;
     // the device's g_noise_err word (rvz_dirichlet_noise's exhaustion flag), read by rvz_check
     int32_t* noise_err = nullptr;
+    // rvz_env_openings: the engine's copy of the pool (black, white, side, the validation's word)
+    void* open_buf = nullptr;
 };
 
 static thread_local std::string g_create_error;
@@ -1519,6 +1553,11 @@ int rvz_create(const rvz_config* cfg, rvz_engine** out) {
     v.noise_salt = 0u;
     v.sched_from = 0;
     v.sched_late = 0.0;
+    v.open_n = 0;
+    v.open_salt = 0u;
+    v.open_black = nullptr;
+    v.open_white = nullptr;
+    v.open_side = nullptr;
     v.seed32 = dalloc<uint32_t>(e, G);
     v.eta = dalloc<float>(e, (size_t)G * WAVE);
     e->stats_buf = dalloc<unsigned long long>(e, 3 * (size_t)G);
@@ -1556,6 +1595,7 @@ int rvz_create(const rvz_config* cfg, rvz_engine** out) {
 void rvz_destroy(rvz_engine* e) {
     if (!e) return;
     table_free(e);
+    if (e->open_buf) (void)hipFree(e->open_buf);
     for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     for (void* p : e->allocs)
         if (p) (void)hipFree(p);
@@ -1612,6 +1652,71 @@ int rvz_env_autoreset(rvz_engine* e, const int32_t* idx, int64_t* seeds, int64_t
     if (reset) e->pending = 0;
     return launch_games(e, "k_autoreset", k_autoreset<8>, k_autoreset<6>, e->v, idx, seeds, stride,
                         plies, done, reset);
+}
+
+// The pool is copied into one allocation of the engine's own (black, white, side, and the word
+// the validation kernel writes) and checked there; a refused pool leaves the setting as it was.
+// The old copy is freed behind a stream synchronisation, so no launch still reads it; pointers
+// held by an already captured graph would dangle: set the pool before capturing.
+int rvz_env_openings(rvz_engine* e, int32_t n, const uint64_t* black, const uint64_t* white,
+                     const int32_t* side, uint32_t salt) {
+    if (!e) return RVZ_EINVAL;
+    if (n < 0 || (n > 0 && (!black || !white || !side))) {
+        e->err = "rvz_env_openings: n >= 0, and with n > 0 black, white and side";
+        return RVZ_EINVAL;
+    }
+    if (in_search(e, "rvz_env_openings")) return RVZ_EINVAL;
+    void* buf = nullptr;
+    if (n > 0) {
+        const size_t N = (size_t)n;
+        const size_t bytes = (size_t)up16((int64_t)(N * 20)) + 16;
+        if (hipMalloc(&buf, bytes) != hipSuccess) {
+            e->err = "hipMalloc failed (the opening pool)";
+            return RVZ_ENOMEM;
+        }
+        uint64_t* pb = static_cast<uint64_t*>(buf);
+        uint64_t* pw = pb + N;
+        int32_t* ps = reinterpret_cast<int32_t*>(pw + N);
+        int32_t* bad = reinterpret_cast<int32_t*>(static_cast<char*>(buf) + bytes - 16);
+        int32_t first_bad = 0x7fffffff;
+        hipError_t s = hipMemcpyAsync(pb, black, N * 8, hipMemcpyDeviceToDevice, e->stream);
+        s = s == hipSuccess ? hipMemcpyAsync(pw, white, N * 8, hipMemcpyDeviceToDevice, e->stream) : s;
+        s = s == hipSuccess ? hipMemcpyAsync(ps, side, N * 4, hipMemcpyDeviceToDevice, e->stream) : s;
+        s = s == hipSuccess ? hipMemcpyAsync(bad, &first_bad, 4, hipMemcpyHostToDevice, e->stream) : s;
+        if (s == hipSuccess) {
+            const Geometry g = thread_per_row(n);
+            launch_bs_unchecked(e->BS, k_openings_validate<8>, k_openings_validate<6>, g.grid,
+                                g.block, e->stream, n, (const uint64_t*)pb, (const uint64_t*)pw,
+                                (const int32_t*)ps, bad);
+            s = hipGetLastError();
+        }
+        s = s == hipSuccess ? hipMemcpyAsync(&first_bad, bad, 4, hipMemcpyDeviceToHost, e->stream) : s;
+        s = s == hipSuccess ? hipStreamSynchronize(e->stream) : s;
+        if (s != hipSuccess || first_bad != 0x7fffffff) {
+            (void)hipFree(buf);
+            if (s != hipSuccess) {
+                e->err = std::string("rvz_env_openings: ") + hipGetErrorString(s);
+                return RVZ_EHIP;
+            }
+            e->err = "rvz_env_openings: row " + std::to_string(first_bad) +
+                     " is no opening (overlapping discs, a bit at or above S*S, a side other "
+                     "than 1 | 2, or the mover has no legal square)";
+            return RVZ_EINVAL;
+        }
+        e->v.open_black = pb;
+        e->v.open_white = pw;
+        e->v.open_side = ps;
+    } else {
+        RVZ_HIP(hipStreamSynchronize(e->stream), e);
+        e->v.open_black = nullptr;
+        e->v.open_white = nullptr;
+        e->v.open_side = nullptr;
+    }
+    if (e->open_buf) (void)hipFree(e->open_buf);   // synchronised above: no launch reads it
+    e->open_buf = buf;
+    e->v.open_n = n;
+    e->v.open_salt = n > 0 ? salt : 0u;
+    return RVZ_OK;
 }
 
 int rvz_env_get(rvz_engine* e, uint64_t* black, uint64_t* white, int32_t* status) {

@@ -35,6 +35,10 @@ Batched core:
     records_games           a window of autoreset self-play records cut into finished games:
                             compact rows with value targets, open games held back
                             (rvz_records_games); SelfPlayRunner(carry_plies=...) keeps the window
+    openings, opening_suite, opening_index   the distinct positions after d plies under the
+                            engine's own rules (rvz_openings), the balanced ones among them, and
+                            the pool row a seed picks (rvz_opening_index); Engine.openings starts
+                            games from such a pool, Arena.play_openings plays a match over one
     policy_value_loss, full_policy_loss   the loss on the full policy target, weighted per row,
                             with its gradients in one deterministic float64 call
                             (rvz_policy_value_loss), and its differentiable torch form
@@ -49,8 +53,8 @@ from .loss import full_policy_loss, policy_value_loss  # noqa: F401
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)
-from .records import (board_symmetry, merge_positions, records_games,  # noqa: F401
-                      replay_batch, replay_batch_weighted, replay_cdf, replay_is_weight,
+from .records import (board_symmetry, merge_positions, opening_index,  # noqa: F401
+                      opening_suite, openings, records_games, replay_batch, replay_batch_weighted, replay_cdf, replay_is_weight,
                       replay_priority, symmetry_compose, symmetry_inverse, training_rows)
 from .replay import ReplayBuffer  # noqa: F401
 from .selfplay import LaneRunner, SelfPlay, SelfPlayRunner  # noqa: F401

@@ -119,6 +119,10 @@ SIGNATURES = {
     "rvz_records_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_records_games": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rvz_openings_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rvz_openings": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "rvz_env_openings": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_uint32]),
+    "rvz_opening_index": (C.c_int, [C.c_int32, C.c_int32, _P, C.c_uint32, _P, _P]),
     "rvz_loss_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_policy_value_loss": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_double,
                                         C.c_double, _P, _P, _P, _P, _P, _P]),

@@ -267,10 +267,15 @@ class Arena:
 
     # ------------------------------------------------------------------ batched games
     def play_games(self, black_ids: Sequence[str], white_ids: Sequence[str],
-                   draw_order: Optional[str] = None) -> List[float]:
+                   openings=None, draw_order: Optional[str] = None) -> List[float]:
         """Play len(black_ids) games in lockstep; game g has black_ids[g] (moves first) against
         white_ids[g]. Returns each game's result for its black player: 1.0 / 0.5 / 0.0
         (arena.py:264-282). Every player that appears gets one engine over all games.
+
+        openings: None (every game from the start position) or (black, white, side): int64 [G],
+        int64 [G] bit patterns and [G] integers (rvz.opening_suite's three): game g starts from
+        row g, side 2 meaning that white_ids[g] moves first. The result is still black's. It is
+        the lockstep loop's starting state, so it holds in both draw orders.
 
         draw_order (default: the arena's): "reference" draws exactly what the reference's
         sequential loop draws (game after game from the global streams, arena.py:175-188,
@@ -285,11 +290,50 @@ class Arena:
         for pid in set(black_ids) | set(white_ids):
             if pid not in self.players:
                 raise ValueError(f"One or both players not found: {pid}")
+        if openings is not None:
+            openings = self._opening_rows(openings, G)
         if order == "batched":
-            return self._lockstep(black_ids, white_ids, range(G), _BatchedDraws(self))
-        return self._play_reference_order(black_ids, white_ids)
+            start = {} if openings is None else {"openings": openings}
+            return self._lockstep(black_ids, white_ids, range(G), _BatchedDraws(self), **start)
+        return self._play_reference_order(black_ids, white_ids, openings)
 
-    def _play_reference_order(self, black_ids, white_ids) -> List[float]:
+    @staticmethod
+    def _opening_rows(openings, G: int):
+        """(black, white, side) of play_games as (int64 [G], int64 [G], int32 status [G, 4])."""
+        if len(openings) != 3:
+            raise ValueError("openings is None or (black, white, side)")
+        b, w, side = (torch.as_tensor(t) for t in openings)
+        if b.shape != (G,) or w.shape != (G,) or side.shape != (G,) or \
+                b.dtype != torch.int64 or w.dtype != torch.int64 or \
+                side.dtype.is_floating_point or side.dtype == torch.bool:
+            raise ValueError(f"openings holds one row per game: black / white int64 [{G}], "
+                             f"side [{G}] integers")
+        sd = side.to(torch.int32)
+        if not bool(((sd == 1) | (sd == 2)).all()):
+            raise ValueError("openings: side is 1 (black to move) or 2 (white)")
+        st = torch.stack([sd, torch.zeros_like(sd), torch.full_like(sd, -1),
+                          torch.zeros_like(sd)], dim=1)
+        return b, w, st
+
+    def play_openings(self, a_id: str, b_id: str, openings,
+                      draw_order: Optional[str] = None) -> List[Tuple[float, float]]:
+        """A match over an opening suite: every opening (black, white, side), n rows, is played
+        twice with colours swapped, a_id as black then b_id as black, all 2n games in one
+        lockstep batch. Returns n pairs (a_id's result as black, a_id's result as white), each
+        1.0 / 0.5 / 0.0 from a_id's side, and folds the 2n games into the ratings in game order
+        (opening 0 both colours, opening 1, ...), as run_tournament does with play_games'
+        results."""
+        b, w, side = (torch.as_tensor(t) for t in openings)
+        n = b.numel()
+        twice = tuple(t.repeat_interleave(2) for t in (b, w, side))
+        blacks = [a_id, b_id] * n
+        whites = [b_id, a_id] * n
+        res = self.play_games(blacks, whites, openings=twice, draw_order=draw_order)
+        for pb, pw, r in zip(blacks, whites, res):
+            self.elo.update_ratings(pb, pw, r)
+        return [(res[2 * k], 1.0 - res[2 * k + 1]) for k in range(n)]
+
+    def _play_reference_order(self, black_ids, white_ids, openings=None) -> List[float]:
         """The reference plays its games one after another, and every MCTS move draws one
         random_sample() from NumPy's global stream (np.random.choice, mcts.py:684; none when all
         visits are 0, mcts.py:679, which the engine refuses anyway), every random-player move one
@@ -356,7 +400,8 @@ class Arena:
             if not todo:
                 break
             draws = _ReferenceDraws(stream, offsets, states)
-            res = self._lockstep(black_ids, white_ids, todo, draws, cache=cache)
+            start = {} if openings is None else {"openings": openings}
+            res = self._lockstep(black_ids, white_ids, todo, draws, cache=cache, **start)
             for g in todo:
                 results[g] = res[g]
                 n_mcts[g] = draws.n_mcts[g]
@@ -378,11 +423,12 @@ class Arena:
             raise ValueError(f"players of one batch play on one board size, got {sorted(sizes)}")
         return sizes.pop() if sizes else 8
 
-    def _lockstep(self, black_ids, white_ids, games, draws,
-                  cache: Optional[Dict] = None) -> List[Optional[float]]:
+    def _lockstep(self, black_ids, white_ids, games, draws, cache: Optional[Dict] = None,
+                  openings=None) -> List[Optional[float]]:
         """Play `games` (indices into black_ids / white_ids) to their end in lockstep; the other
         games start finished. draws supplies each MCTS move's uniform and each random move.
-        cache: a dict that keeps the engines between calls over the same schedule."""
+        cache: a dict that keeps the engines between calls over the same schedule. openings:
+        None or _opening_rows' (black, white, status): the games' starting state."""
         G = len(black_ids)
         ids = sorted(set(black_ids) | set(white_ids))
         dev = next(iter(self.players[p].device for p in ids))
@@ -399,6 +445,8 @@ class Arena:
         engines = {pid: e for pid, e in cache.items() if pid is not None}
         env = cache[None]
         env.reset(range(G))
+        if openings is not None:
+            env.set_state(*openings)
         active = np.zeros(G, bool)
         active[list(games)] = True
         if not active.all():

@@ -419,6 +419,38 @@ class Engine:
         self._call("rvz_search_root_noise", float(alpha), float(epsilon), int(salt) & 0xFFFFFFFF)
         self.noise = (float(alpha), float(epsilon), int(salt) & 0xFFFFFFFF)
 
+    def openings(self, black: Optional[torch.Tensor], white: Optional[torch.Tensor] = None,
+                 side: Optional[torch.Tensor] = None, salt: int = 0):
+        """rvz_env_openings: games start from a pool of positions. black / white int64 [n] (bit
+        patterns) and side [n] integers (1 black, 2 white to move), e.g. rvz.opening_suite's
+        three; the engine keeps a copy of its own. From then on every reset (reset(),
+        autoreset(), play()'s autoreset) with seed s puts the game on pool row
+        rvz.opening_index(n, s, salt) with status {side, 0, -1, 0}; nothing else about the reset
+        changes and no draw is consumed. openings(None) turns the pool off (the default: the
+        start position). A row with overlapping discs, a bit off the board, a side other than
+        1 | 2 or no legal square for the mover raises RvzError naming the first such row. The
+        games already on the boards stay until they are reset. Not inside a search; it allocates
+        and synchronises: set it before capturing a graph (a captured launch keeps the setting of
+        its capture)."""
+        self._stream()
+        if black is None:
+            self._call("rvz_env_openings", 0, None, None, None, 0)
+            self.pool = None
+            return
+        if white is None or side is None:
+            raise RvzError("openings: black, white and side, or None for off")
+        n = black.numel()
+        if n < 1 or black.dim() != 1 or white.shape != (n,) or side.shape != (n,) or \
+                black.dtype != torch.int64 or white.dtype != torch.int64 or \
+                side.dtype.is_floating_point or side.dtype == torch.bool:
+            raise RvzError("openings: black / white int64 [n], side [n] integers, n >= 1")
+        b = black.to(self.device).contiguous()
+        w = white.to(self.device).contiguous()
+        sd = side.to(self.device, torch.int32).contiguous()
+        self._call("rvz_env_openings", n, b.data_ptr(), w.data_ptr(), sd.data_ptr(),
+                   int(salt) & 0xFFFFFFFF)             # synchronises: b, w, sd may go
+        self.pool = (n, int(salt) & 0xFFFFFFFF)
+
     def temperature_schedule(self, moves: Optional[int], late_temperature: float = 0.0):
         """rvz_act_schedule: a game's first `moves` moves are chosen at the temperature of the
         call (act() / play()), every later one at late_temperature (0: the most visited move, no

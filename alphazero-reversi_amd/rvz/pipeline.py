@@ -53,8 +53,17 @@ class SelfPlayTrainer:
                  policy_target: str = "argmax", count_weights: bool = False,
                  replay_sampling: str = "uniform", replay_recency_decay: float = 1.0,
                  replay_priority_alpha: float = 0.6, replay_priority_beta=0.4,
-                 continuous_plies: Optional[int] = None):
-        """continuous_plies: None (off: the keys and bytes of before) or K >= 1: continuous
+                 continuous_plies: Optional[int] = None, openings=None):
+        """openings: None (off: every game starts from the start position) or (black, white,
+        side[, salt]): a pool of start positions (Engine.openings; rvz.opening_suite builds one),
+        set before any graph is captured. Every self-play game, in lockstep and with
+        continuous_plies alike, starts from the pool row its seed picks (rvz.opening_index); the
+        record side needs nothing else, a game's rows and value targets being functions of its
+        records alone. ValueError together with adjudicate_empties, whose stopping ply assumes 4
+        discs at the start. With a pool on, records_headless_games (continuous_plies) counts the
+        emitted games that started from a pool position other than the start position: they are
+        whole games, not games whose head was lost.
+        continuous_plies: None (off: the keys and bytes of before) or K >= 1: continuous
         self-play, the operating point bench.py measures. An iteration is ONE rvz_play launch of K
         plies with autoreset (a finished game restarts at once with its slot's next seed, so no
         slot idles and the games spread over all move numbers) into the runner's window, behind a
@@ -235,6 +244,11 @@ class SelfPlayTrainer:
             if symmetries is not None:
                 raise ValueError("continuous_plies leaves the symmetry to the replay buffer's "
                                  f"draw: symmetries must be None, not {symmetries!r}")
+        if openings is not None and adjudicate_empties:
+            raise ValueError("openings start games with more than 4 discs, and adjudication's "
+                             "stopping ply assumes 4: adjudicate_empties must be 0")
+        if openings is not None and not 3 <= len(openings) <= 4:
+            raise ValueError("openings is None or (black, white, side[, salt])")
         self.continuous_plies = None if continuous_plies is None else int(continuous_plies)
         self.model = model.eval()
         self.device = next(model.parameters()).device
@@ -282,6 +296,8 @@ class SelfPlayTrainer:
             self.eng.root_noise(*root_noise)
         if temperature_schedule is not None:
             self.eng.temperature_schedule(*temperature_schedule)
+        if openings is not None:
+            self.eng.openings(*openings)
         self.max_plies = bs * bs - 4
         if self.adjudicate_empties and not (1 <= self.adjudicate_empties <= SOLVE_MAX_EMPTIES and
                                             self.adjudicate_empties < self.max_plies):
@@ -460,7 +476,11 @@ class SelfPlayTrainer:
         return out
 
     def run_iteration(self) -> Dict[str, float]:
-        """generate + train; wall times of both phases (device-synchronised) in the result."""
+        """generate + train; wall times of both phases (device-synchronised) in the result. With
+        continuous_plies it reports records_headless_games (rvz_records_games' out_stats[5]): the
+        emitted games whose first record is not the start position. With an opening pool on
+        (openings=...) those are the games that started from a pool position other than the
+        start position: whole games, not games whose head was lost."""
         dev = self.device
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()

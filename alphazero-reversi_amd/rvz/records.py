@@ -414,6 +414,111 @@ def records_games(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: to
     return out
 
 
+# ------------------------------------------------------------------ opening pools
+# The default max_rows of openings(): the bound is the largest level's candidate count, which
+# grows with the level, so ply 8's. By the level rule on the CPU oracle (tests/openings_ref.py)
+# level 8 has 303,386 candidates on 8x8 and 266,062 on 6x6 (270,319 and 235,673 distinct rows);
+# 2^19 = 524,288 holds both (a scratch of 32 MB). Level 9 has 1,703,146 on 6x6: deeper calls pass
+# their own max_rows.
+OPENINGS_DEFAULT_MAX_ROWS = 1 << 19
+
+
+def check_openings_args(board_size, plies, max_rows, who: str = "openings") -> int:
+    """The argument rules of openings, checked before any device call; returns max_rows."""
+    check_board_size(board_size, who)
+    _ints(who, plies=plies)
+    if not 0 <= plies <= board_size * board_size - 4:
+        raise RvzError(f"{who}: plies = {plies} must be in [0, S*S - 4]")
+    if max_rows is None:
+        if plies > 8:
+            raise RvzError(f"{who}: the default max_rows holds plies <= 8; pass max_rows")
+        return OPENINGS_DEFAULT_MAX_ROWS
+    _ints(who, max_rows=max_rows)
+    if not 1 <= max_rows < 2 ** 29:
+        raise RvzError(f"{who}: max_rows = {max_rows} must be >= 1 and max_rows * 4 fit int32")
+    return int(max_rows)
+
+
+def openings(board_size: int, plies: int, max_rows: Optional[int] = None, device="cuda"):
+    """rvz_openings: the distinct positions after `plies` plies from the start position under the
+    engine's own rules (include/rvz.h has the level rule), in order of first occurrence. Returns
+    a dict: "black" / "white" int64 [m] (bit patterns), "status" int32 [m, 4], each row
+    {side, 0, -1, 0} (what Engine.set_state and Engine.openings take), "stats" int64 [8]: rows, the
+    last level's candidates before de-duplication, finished children dropped, duplicates removed,
+    the largest level's candidates, 0, 0, 0. max_rows: the rows the scratch holds per level
+    (default OPENINGS_DEFAULT_MAX_ROWS = 2^19, enough for plies <= 8 on either board; deeper
+    calls pass their own); a level with more candidates raises RvzError, and the result does not
+    depend on max_rows otherwise. Reading the row count is the call's one synchronisation."""
+    who = "openings"
+    R = check_openings_args(board_size, plies, max_rows, who)
+    lib = _lib.load()
+    dev = torch.device(device)
+    m = torch.zeros((), dtype=torch.int32, device=dev)
+    b, w = (torch.empty(R, dtype=torch.int64, device=dev) for _ in range(2))
+    st = torch.empty(R, 4, dtype=torch.int32, device=dev)
+    stats = torch.zeros(8, dtype=torch.int64, device=dev)
+    scratch = torch.empty(lib.rvz_openings_scratch_size(board_size, R), dtype=torch.uint8,
+                          device=dev)
+    check(lib.rvz_openings(board_size, int(plies), R, ptr(scratch), _addr(m), _addr(b), _addr(w),
+                           _addr(st), _addr(stats), _lib.stream_handle(dev)), None, "rvz_openings")
+    n = int(m.item())
+    if n < 0:
+        raise RvzError(f"{who}: a level has {int(stats[4].item())} candidates, more than "
+                       f"max_rows = {R}")
+    return {"black": b[:n].clone(), "white": w[:n].clone(), "status": st[:n].clone(),
+            "stats": stats}
+
+
+def opening_index(n_pool: int, seed32: torch.Tensor, salt: int = 0) -> torch.Tensor:
+    """rvz_opening_index: the pool row a game reset with each seed starts from, with a pool of
+    n_pool rows set by Engine.openings(..., salt=salt) (the same device function). seed32 [n]
+    integers (taken mod 2^32), a device tensor. Returns int32 [n]."""
+    who = "opening_index"
+    _ints(who, n_pool=n_pool, salt=salt)
+    if not 1 <= n_pool < 2 ** 31:
+        raise RvzError(f"{who}: n_pool must be in [1, 2^31)")
+    if not isinstance(seed32, torch.Tensor) or seed32.dim() != 1 or \
+            seed32.dtype.is_floating_point or seed32.dtype == torch.bool:
+        raise RvzError(f"{who}: seed32 holds one integer per game")
+    lib = _lib.load()
+    dev = seed32.device
+    n = seed32.numel()
+    # the low 32 bits as an int32 bit pattern, as Engine.reset passes its seeds
+    s64 = seed32.to(torch.int64).bitwise_and(0xFFFFFFFF)
+    sd = torch.where(s64 >= 2 ** 31, s64 - 2 ** 32, s64).to(torch.int32).contiguous()
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        check(lib.rvz_opening_index(int(n_pool), n, _addr(sd), int(salt) & 0xFFFFFFFF, _addr(out),
+                                    _lib.stream_handle(dev)), None, "rvz_opening_index")
+    return out
+
+
+def opening_suite(board_size: int, plies: int, depth: Optional[int] = None,
+                  max_abs_score: Optional[int] = None, max_rows: Optional[int] = None,
+                  device="cuda"):
+    """The opening suite of an engine match: openings(board_size, plies), and with depth set only
+    the balanced ones: the rows whose rvz.alphabeta score at that depth (default weights, from
+    the mover's side) has absolute value at most max_abs_score. There is no default threshold:
+    depth and max_abs_score are given together. Returns (black, white, side): int64 [m], int64
+    [m], int32 [m], in openings' order."""
+    who = "opening_suite"
+    if (depth is None) != (max_abs_score is None):
+        raise RvzError(f"{who}: depth and max_abs_score are given together (there is no default "
+                       "threshold)")
+    o = openings(board_size, plies, max_rows, device)
+    b, w, st = o["black"], o["white"], o["status"]
+    if depth is not None:
+        _ints(who, depth=depth, max_abs_score=max_abs_score)
+        if max_abs_score < 0:
+            raise RvzError(f"{who}: max_abs_score must be >= 0")
+        from .engine import alphabeta
+        if b.numel():
+            score, _, _ = alphabeta(b, w, st, board_size, int(depth))
+            keep = score.to(torch.int64).abs() <= int(max_abs_score)
+            b, w, st = b[keep], w[keep], st[keep]
+    return b, w, st[:, 0].contiguous()
+
+
 # ------------------------------------------------------------------ prioritized replay
 PRIORITY_MIN_FLOOR, PRIORITY_MAX_CAP = 2.0 ** -16, 65536.0
 

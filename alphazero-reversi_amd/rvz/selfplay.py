@@ -33,8 +33,14 @@ class SelfPlayRunner:
                  record: bool = False, max_plies: int = 60, seed_stride: int = None,
                  skip_last_eval: bool = False, fused_bookkeeping: bool = True,
                  fused: bool = False, temperature_schedule=None, skip_forced_roots=None,
-                 carry_plies: int = 0):
+                 carry_plies: int = 0, openings=None):
         self.eng = engine
+        # openings: None (the engine's setting stays as it is) or (black, white, side[, salt]): a
+        # pool of start positions (Engine.openings; rvz.opening_suite builds one). Every game,
+        # the first of a slot and each autoreset restart alike, starts from the pool row its seed
+        # picks; set here, before any capture
+        if openings is not None:
+            engine.openings(*openings)
         # carry_plies = C > 0 (fused and record): the records are a window of C + max_plies
         # plies for continuous play with autoreset. A launch records behind a carry of the C
         # plies before it, roll() moves the window on, and rvz.records_games(emit_from=C) cuts

@@ -790,6 +790,63 @@ int rvz_records_games(int32_t board_size, int32_t plies, int32_t n_games,
                       int32_t *out_state /* [plies][n_games], nullable */,
                       int64_t *out_stats /* [8] */, void *hip_stream);
 
+/* ---- opening pools: the positions after d plies, and games that start from them --------------
+ * rvz_openings (csrc/rvz_openings.hip) enumerates the distinct positions after `plies` plies
+ * under the engine's own rules (the make_move of csrc/rvz_rules.hip.h: the wrap-around quirk, the
+ * auto-pass, the game end). It is stateless, on caller arrays (device pointers), asynchronous on
+ * hip_stream and graph-capturable: no allocation, no copy, no memset, no synchronisation; the
+ * scratch needs no preparation; no workgroup waits on another (1 + 5 * plies consecutive
+ * launches, each reading the level's size from the scratch, so the host never learns a count);
+ * every output element below is written exactly once. Integer atomics only: the outputs are a
+ * pure function of (board_size, plies), independent of max_rows (while no level overflows),
+ * timing and launch geometry.
+ * Level 0 is the start position with black to move. Level k + 1 from level k: for every row of
+ * level k in order and every square of its legal mask in increasing index, the child make_move
+ * produces. A child that is over is dropped and counted; the others are the level's candidates,
+ * in (parent order, square order). Two candidates are the same position iff (black, white, side)
+ * are equal; the level keeps each distinct position once, in order of first occurrence.
+ * Row j of level `plies`: out_black[j], out_white[j], out_status[j] = {side, 0, -1, 0} (a fresh
+ * start with no passes behind it, as rvz_records_games assumes when a segment opens). *out_m is
+ * the row count; rows at and above it are not written.
+ * out_stats: [0] rows, [1] the last level's candidates before de-duplication, [2] finished
+ * children dropped over all levels, [3] candidates removed as duplicates over all levels, [4] the
+ * largest level's candidate count, [5..7] 0. Level 0 counts as one candidate.
+ * A level with more than max_rows candidates: *out_m = -1 and out_stats[0] = -1 (checked on the
+ * device; the later launches are no-ops), out_stats[4] is that level's candidate count, the row
+ * outputs are unspecified.
+ * rvz_openings_scratch_size: the scratch's bytes (64 + 52 per row + 4 per table slot, the table a
+ * power of two >= 2 * max_rows, each part rounded up to 16); negative for bad arguments.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, plies < 0 or > S*S - 4, max_rows < 1,
+ * max_rows * 4 >= 2^31, a null pointer, or a scratch that is not 16-byte aligned. */
+int64_t rvz_openings_scratch_size(int32_t board_size, int32_t max_rows);
+int rvz_openings(int32_t board_size, int32_t plies, int32_t max_rows,
+                 void *scratch /* 16-byte aligned */, int32_t *out_m /* [1] */,
+                 uint64_t *out_black, uint64_t *out_white /* [max_rows] */,
+                 int32_t *out_status /* [max_rows][4] */, int64_t *out_stats /* [8] */,
+                 void *hip_stream);
+
+/* rvz_env_openings: games start from a pool of n positions (n = 0: off, the copy is freed;
+ * nothing set: every game, counter and output byte is what it is without the pool). black /
+ * white / side [n] are device pointers; the engine copies them into memory of its own. Like
+ * rvz_search_memo it allocates and synchronises: call it before any graph is captured. Every row
+ * is checked in a kernel: no overlapping discs, no bit at or above S*S, side 1 | 2, and the mover
+ * has at least one legal square; a pool with a bad row is refused with RVZ_EINVAL (the setting
+ * stays as it was) and rvz_last_error names the first such row. RVZ_EINVAL also inside a search.
+ * The pool, n and salt travel with each launch: launches already issued keep their setting.
+ * With a pool on, wherever a game is reset with seed32 = s (rvz_env_reset, rvz_env_autoreset,
+ * rvz_play's autoreset), its position becomes pool row i with status {side[i], 0, -1, 0}:
+ *   x = Philox4x32-10(key (s, salt), counter (0, 0, 0, 1))      i = (uint32) ((x.0 * n) >> 32)
+ * (counter word 3 = 1 keeps the block apart from the root noise's, whose word 3 is 0). Everything
+ * else about the reset (the MT19937 seeding, the draws, the carried link, seed32) is unchanged:
+ * picking an opening consumes none of the game's draws, and i is a pure function of (s, salt, n).
+ * rvz_opening_index: out_index[k] = i for seed32[k], by the same device function; stateless, on
+ * device pointers, asynchronous on hip_stream. RVZ_EINVAL: n_pool < 1, n < 0, a null pointer with
+ * n > 0; n = 0 returns RVZ_OK without a launch. */
+int rvz_env_openings(rvz_engine *e, int32_t n, const uint64_t *black, const uint64_t *white,
+                     const int32_t *side /* [n] */, uint32_t salt);
+int rvz_opening_index(int32_t n_pool, int32_t n, const uint32_t *seed32 /* [n] */, uint32_t salt,
+                      int32_t *out_index /* [n] */, void *hip_stream);
+
 /* ---- policy/value loss on the full policy target -------------------------------------------
  * AlphaZero's own loss, -pi . log p + (y - t)^2, on the whole target distribution (a merged
  * position's mean search policy, the uniform distribution over the proven-optimal moves, a visit
