@@ -1,13 +1,14 @@
 // rvz_dirichlet.hip.h — Dirichlet noise for the priors of a search root (rvz_search_root_noise,
-// rvz_dirichlet_noise). Included by csrc/rvz_engine.hip inside its anonymous namespace, after the
-// wave primitives (wave_max_f, wave_sum_f).
+// rvz_dirichlet_noise): dirichlet_eta, the device function of the search's root noise (k_step,
+// k_play) and of k_dirichlet (csrc/rvz_engine.hip). Needs the wave reductions wave_max_f and
+// wave_sum_f (rvz_wave_dpp.hip.h) and the generator (rvz_philox.hip.h).
 //
 // eta ~ Dirichlet(alpha, ..., alpha) over the k legal squares of a root, one lane per square and
 // one wave per game, as a pure function of (seed32, salt, tag, alpha, legal mask): a counter-based
 // generator, so no state is carried and the values do not depend on the launch geometry, the
 // schedule or which kernel asks.
-//  * Philox4x32-10 (Salmon et al., SC'11; rvz_philox.hip.h, included by the translation unit
-//    before this file), key (seed32, salt), counter (attempt, square, tag, 0).
+//  * Philox4x32-10 (Salmon et al., SC'11; rvz_philox.hip.h), key (seed32, salt), counter
+//    (attempt, square, tag, 0).
 //  * Gamma(alpha) per legal square by Marsaglia-Tsang rejection (ACM TOMS 26(3), 2000): the normal
 //    by Box-Muller from words 0 and 1 of the attempt's block, the acceptance uniform from word 2;
 //    every attempt is a new block (the attempt index is a counter word). alpha < 1 samples
@@ -20,6 +21,16 @@
 //    float32, so no log(0).
 //  * The rejection loop is bounded (NOISE_ATTEMPTS; the expected count is about 1.05): on
 //    exhaustion the lane takes its last positive proposal (or v = 1) and ERR_NOISE is raised.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "rvz_philox.hip.h"
+#include "rvz_wave_dpp.hip.h"
+
+namespace rvz {
+namespace {
 
 constexpr int32_t ERR_NOISE = 32;   // a Gamma rejection loop ran out of attempts (device error word)
 constexpr int NOISE_ATTEMPTS = 64;
@@ -69,27 +80,5 @@ __device__ __forceinline__ float dirichlet_eta(uint32_t seed32, uint32_t salt, u
     return ex / wave_sum_f(ex);
 }
 
-// rvz_dirichlet_noise's exhaustion flag: the call has no engine, so its ERR_NOISE goes to this
-// word of the device, which rvz_check of any engine of the device reports and clears
-__device__ int32_t g_noise_err;
-
-// rvz_dirichlet_noise: one wave per row, WPB rows per workgroup
-template <int BS>
-__global__ __launch_bounds__(256) void k_dirichlet(int n, const uint64_t* __restrict__ legal,
-                                                   const uint32_t* __restrict__ seed32,
-                                                   const int32_t* __restrict__ tag, uint32_t salt,
-                                                   float alpha, float* __restrict__ out,
-                                                   uint32_t* __restrict__ out_bits) {
-    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
-    const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * WPB + (threadIdx.x >> 6);
-    if (r >= n) return;
-    const uint64_t V = legal[r] & Geo<BS>::FULL;
-    const uint32_t sd = seed32[r], tg = (uint32_t)tag[r];
-    const float eta = dirichlet_eta(sd, salt, tg, alpha, V, lane, &g_noise_err);
-    if (lane < NSQ) out[(size_t)r * NPOL + lane] = eta;
-    if (lane == 0) out[(size_t)r * NPOL + NSQ] = 0.0f;
-    if (out_bits && lane < NSQ)
-        reinterpret_cast<uint4*>(out_bits)[(size_t)r * NSQ + lane] =
-            philox4x32_10(sd, salt, 0u, (uint32_t)lane, tg, 0u);
-}
+}  // namespace
+}  // namespace rvz

@@ -2,7 +2,7 @@
 // cores) as device functions: one pass of a workgroup over NBOARD boards (h2_pass) — stem,
 // residual tower and the 1x1 head convs, activations resident in LDS. Used by the trunk kernel
 // (csrc/rvz_resnet.hip, k_resnet_h2: one pass per workgroup over a leaf batch) and by the fused
-// self-play kernel (csrc/rvz_engine.hip, k_play: a workgroup's own games' leaves, pass after pass).
+// self-play kernel (csrc/rvz_play.hip.h, k_play: a workgroup's own games' leaves, pass after pass).
 #pragma once
 #include "rvz_resnet_common.hip.h"
 

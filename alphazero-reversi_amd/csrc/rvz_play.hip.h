@@ -1,8 +1,8 @@
 // rvz_play.hip.h — fused self-play (rvz_play): a workgroup plays its own games, search and leaf
-// evaluation in one persistent launch. Included by csrc/rvz_engine.hip inside its anonymous
-// namespace, after the search device functions (select_phase, expand_backup_phase, act_game,
-// reset_game); the evaluator device functions come from rvz_h2.hip.h (h2_pass) and
-// rvz_resnet_common.hip.h (heads_fc16).
+// evaluation in one persistent launch: k_play and its device code. Needs the search device
+// functions (rvz_search.hip.h: View, ExpIn, select_phase, expand_backup_phase, act_game,
+// reset_game and the WT_* / FT_* instrumentation) and the evaluator device functions of
+// rvz_h2.hip.h (h2_pass) and rvz_resnet_common.hip.h (heads_fc16).
 //
 // The ply loop of SelfPlayRunner (per batch: k_step, the h2 trunk, the FC heads; then k_act and
 // k_autoreset, self_play.py:80-101 with mcts.py:322-407 and :642-694) as one launch:
@@ -20,6 +20,16 @@
 // root has at least E - 1 legal moves evaluates the root's row only (the unread rows, DESIGN
 // §2.13; tests/test_gpu_unread_rows.py). Inside a ply there is no kernel boundary, launch ramp or tail: the
 // two workgroups on a CU overlap one's search phase with the other's trunk passes.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rvz_h2.hip.h"
+#include "rvz_resnet_common.hip.h"
+#include "rvz_search.hip.h"
+
+namespace rvz {
+namespace {
 
 struct PlayArgs {
     const float* prm;
@@ -854,3 +864,6 @@ void k_play(PlayCtx ctx0) {
     unsigned long long* ur = play_ctx().a.roots_unread;
     if (ur && tid == 0 && s_cnt[4]) atomicAdd(ur, (unsigned long long)s_cnt[4]);
 }
+
+}  // namespace
+}  // namespace rvz

@@ -1,7 +1,7 @@
 // rvz_solve.hip — exact endgame solver: batched negamax over the reference's rules for gfx950
 // (MI355X), exported as rvz_solve, rvz_solve_window and rvz_solve_moves (include/rvz.h). Its own
 // translation unit:
-// the code objects of rvz_engine.hip (k_play, k_step, k_act) do not depend on it.
+// the code objects of rvz_play.hip (k_play) and rvz_engine.hip (k_step, k_act) do not depend on it.
 //
 // Definition (DESIGN.md §Exact endgame solver): solve(g) = the disc difference at the end of the
 // game from g's side to move, both sides playing the maximum, the children made by make_move<BS>

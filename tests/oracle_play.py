@@ -1,7 +1,7 @@
 """The literal CPU oracle (oracle/, reference semantics) driven like the fused self-play launch:
 for a sample of games, one MCTS search per ply (mcts.py:322-407) whose leaves are evaluated by
 the same h2 LeafEvaluator on the GPU and softmaxed by rvz.policy_softmax — bitwise the softmax
-the expand inside rvz_play applies to its logits (one device function, csrc/rvz_engine.hip) —
+the expand inside rvz_play applies to its logits (one device function, csrc/rvz_search.hip.h) —
 then get_action_probs' tail (mcts.py:642-694) with each game's numpy MT19937 stream and
 make_move. Test infrastructure only: the checker of tests/ and __graft_entry__.smoke()."""
 from __future__ import annotations

@@ -237,6 +237,37 @@ def test_stagger_then_pull_style_equals_fused():
     assert all(torch.equal(x, y) for x, y in zip(sa, sb)) and torch.equal(pa, pb)
 
 
+def test_pull_style_ply_then_fused_ply_on_one_engine():
+    """The other order, at the smallest shape that runs both paths (6x6, one 64-filter block, 8
+    games, two batches of 8, 2 plies): a pull-style ply (k_step, k_act, k_autoreset) and then a
+    fused one (k_play) on the same engine play the pull-style runner's two plies. The two paths
+    are two translation units over one struct rvz_engine and one tree."""
+    import rvz
+    net = _net(6, 1, 64, seed=2)
+    G, S = 8, 16
+    outs = []
+    for fused_second in (True, False):
+        eng = rvz.Engine(G, S, 8, board_size=6, compact_leaves=True, memo=True)
+        run = rvz.SelfPlayRunner(eng, rvz.LeafEvaluator(net), autoreset=True, seed_base=3)
+        run.start()
+        run.ply()
+        moves = [eng.idx_buf.clone()]
+        if fused_second:
+            hist = torch.full((1, G), -9, dtype=torch.int32, device="cuda")
+            eng.play(run.evaluator, 1, 1.0, run.seeds, run.seed_stride, run._plies, run._done,
+                     reset=True, hist=hist)
+            moves.append(hist[0].clone())
+        else:
+            run.ply()
+            moves.append(eng.idx_buf.clone())
+        eng.check()
+        outs.append((torch.stack(moves), [t.clone() for t in eng.get_state()],
+                     run._plies.clone()))
+    (ma, sa, pa), (mb, sb, pb) = outs
+    assert (ma >= 0).all() and torch.equal(ma, mb)
+    assert all(torch.equal(x, y) for x, y in zip(sa, sb)) and torch.equal(pa, pb)
+
+
 def test_queue_wait_timeout_drains_and_reports():
     """The bounded queue wait: a wait that times out sets device error 16; the other
     workgroups stop drawing tasks and the launch ends (no hang); after a reset the engine plays

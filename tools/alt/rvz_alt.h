@@ -40,7 +40,7 @@ int rvz_alt_heads_valu(int32_t board, const float *work, int32_t n, const float 
                        int32_t filters, int32_t blocks, float *logits, float *value,
                        void *hip_stream);
 
-/* out[i] = the engine's sqrt_count(i) (csrc/rvz_engine.hip) for i < n, same compile flags. */
+/* out[i] = the engine's sqrt_count(i) (csrc/rvz_search.hip.h) for i < n, same compile flags. */
 int rvz_alt_sqrt_count(int32_t n, float *out, void *hip_stream);
 /* out[i] = x[i] ** e[i] in float64: mode 1 = k_act's correctly rounded power (csrc/rvz_pow.hip.h),
  * mode 0 = the device library's pow; rvz_alt_pow_host = the same pow_cr compiled for the host. */

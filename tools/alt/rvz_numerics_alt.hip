@@ -1,6 +1,6 @@
 // rvz_numerics_alt.hip (tools/alt/librvz_alt.so) — the engine's scalar numerics as standalone
 // kernels, compiled with the product's flags, so tests/test_gpu_numerics.py can check them
-// against NumPy element by element: sqrt_count (csrc/rvz_engine.hip) = np.float32(math.sqrt(n)),
+// against NumPy element by element: sqrt_count (csrc/rvz_search.hip.h) = np.float32(math.sqrt(n)),
 // and k_act's power (csrc/rvz_pow.hip.h pow_cr, on the device and on the host; mode 0 = the device
 // library's pow, for comparison).
 #include <hip/hip_runtime.h>
@@ -11,7 +11,7 @@
 #include "rvz_alt.h"
 
 namespace {
-// the same expression as csrc/rvz_engine.hip sqrt_count
+// the same expression as csrc/rvz_search.hip.h sqrt_count
 __device__ __forceinline__ float sqrt_count(int n) { return __builtin_sqrtf((float)n); }
 
 __global__ void k_sqrt_count(int n, float* __restrict__ out) {

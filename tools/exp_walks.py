@@ -3,7 +3,8 @@ walks from the root, tree levels read, known-terminal hits (memory / register fa
 terminals, per game and launch; with k_step's mean launch time beside them.
 
     RVZ_LIB=tools/_ab/librvz_walks.so CONFIG=c2 python tools/exp_walks.py
-(build: hipcc ... -DRVZ_WALK_STATS -shared -o tools/_ab/librvz_walks.so csrc/*.hip)"""
+(build: make -C alphazero-reversi_amd EXTRA=-DRVZ_WALK_STATS BUILD=build/ab_walks
+ OUT=$PWD/tools/_ab/librvz_walks.so; k_step's counters are read in csrc/rvz_engine.hip)"""
 import ctypes as C
 import json
 import os
