@@ -16,7 +16,7 @@
 // the scratch; k_pri_rows, a thread per row, computes the row's priority, keeps it in the
 // scratch and, for a valid row, enters (slot -> max r) into the table (the key claimed by an
 // integer compare-and-swap, r by an integer atomicMax: where a key lands depends on arrival, what
-// a lookup returns does not); k_pri_write, a thread per row, looks its slot up, and the row whose
+// a lookup returns does not; rvz_slot_table.hip.h, shared with rvz_reanalyse.hip); k_pri_write, a thread per row, looks its slot up, and the row whose
 // r the table holds is the slot's winner and stores the weight. No workgroup waits on another.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -25,6 +25,7 @@
 #include "../../include/rvz.h"
 #include "rvz_host.hip.h"
 #include "rvz_pow.hip.h"
+#include "rvz_slot_table.hip.h"
 #include "rvz_wave.hip.h"
 
 namespace {
@@ -82,11 +83,10 @@ __global__ __launch_bounds__(PRI_THREADS) void k_isw_weight(int nb, const float*
 // the scratch: the header, pri [nb], the table's key [T] and, right behind it, val [T]; T: the
 // power of two >= max(2 nb, 64)
 struct Layout {
-    int64_t T = 64, bytes;
+    int64_t T, bytes;
     uint32_t *head, *key, *val;
     float* pri;
-    Layout(int32_t nb, void* scratch) {
-        while (T < 2 * (int64_t)nb) T <<= 1;
+    Layout(int32_t nb, void* scratch) : T(slot_table_entries(nb)) {
         Carver c(scratch);
         head = c.take<uint32_t>(PRI_HEAD / 4);
         pri = c.take<float>(nb);
@@ -95,14 +95,6 @@ struct Layout {
         bytes = c.at;
     }
 };
-
-__device__ __forceinline__ uint32_t slot_hash(uint32_t s) {             // murmur3's finaliser
-    s ^= s >> 16;
-    s *= 0x85ebca6bu;
-    s ^= s >> 13;
-    s *= 0xc2b2ae35u;
-    return s ^ (s >> 16);
-}
 
 __global__ __launch_bounds__(PRI_THREADS) void k_pri_clear(uint32_t* __restrict__ head,
                                                            uint32_t* __restrict__ table,
@@ -138,15 +130,7 @@ __global__ __launch_bounds__(PRI_THREADS) void k_pri_rows(
             x = x < cap ? x : cap;
             p = (float)x;
             bits = __float_as_uint(p);
-            const uint32_t want = (uint32_t)s + 1u;
-            uint32_t h = slot_hash((uint32_t)s) & mask;
-            for (uint32_t tries = 0; tries <= mask; ++tries, h = (h + 1u) & mask) {
-                const uint32_t old = atomicCAS(&key[h], 0u, want);     // <= nb keys, T >= 2 nb
-                if (old == 0u || old == want) {
-                    atomicMax(&val[h], (uint32_t)r + 1u);
-                    break;
-                }
-            }
+            slot_table_enter(key, val, mask, s, r);
         }
         pri[r] = p;                              // 0: an invalid row (a valid one is >= floor > 0)
     }
@@ -170,17 +154,7 @@ __global__ __launch_bounds__(PRI_THREADS) void k_pri_write(
     int state = -1;
     if (p > 0.0f) {                              // valid: its slot is in range and in the table
         const int s = slot[r];
-        const uint32_t want = (uint32_t)s + 1u;
-        uint32_t h = slot_hash((uint32_t)s) & mask;
-        state = 0;
-        for (uint32_t tries = 0; tries <= mask; ++tries, h = (h + 1u) & mask) {
-            const uint32_t k = key[h];
-            if (k == want) {
-                state = val[h] == (uint32_t)r + 1u ? 1 : 0;
-                break;
-            }
-            if (k == 0u) break;                  // not reached: k_pri_rows entered every valid slot
-        }
+        state = slot_table_wins(key, val, mask, s, r);     // k_pri_rows entered every valid slot
         if (state == 1) weight[s] = p;
     }
     if (out_priority) out_priority[r] = p;

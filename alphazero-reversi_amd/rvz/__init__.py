@@ -32,6 +32,10 @@ Batched core:
                             back as the rows' sampling weights (rvz_replay_priority) and the
                             importance weights of a drawn batch (rvz_replay_is_weight):
                             ReplayBuffer(prioritized=True)
+    replay_stale, replay_roots, replay_refresh   replay reanalysis: the stalest rows chosen on
+                            the device (rvz_replay_stale), ring rows as engine roots
+                            (rvz_replay_roots) and the new search's policy rows written over the
+                            old targets (rvz_replay_refresh): ReplayBuffer(stamps=True).reanalyse
     records_games           a window of autoreset self-play records cut into finished games:
                             compact rows with value targets, open games held back
                             (rvz_records_games); SelfPlayRunner(carry_plies=...) keeps the window
@@ -55,7 +59,8 @@ from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa:
                       load_reference_state_dict)
 from .records import (board_symmetry, merge_positions, opening_index,  # noqa: F401
                       opening_suite, openings, records_games, replay_batch, replay_batch_weighted, replay_cdf, replay_is_weight,
-                      replay_priority, symmetry_compose, symmetry_inverse, training_rows)
+                      replay_priority, replay_refresh, replay_roots, replay_stale,
+                      symmetry_compose, symmetry_inverse, training_rows)
 from .replay import ReplayBuffer  # noqa: F401
 from .selfplay import LaneRunner, SelfPlay, SelfPlayRunner  # noqa: F401
 

@@ -116,6 +116,14 @@ SIGNATURES = {
     "rvz_replay_priority": (C.c_int, [C.c_int32, _P, C.c_int32, _P, _P, C.c_double, C.c_double,
                                       C.c_int32, C.c_double, C.c_double, C.c_double, _P, _P, _P,
                                       _P, _P]),
+    "rvz_replay_stale_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rvz_replay_stale": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, _P, C.c_int64, _P, _P, _P]),
+    "rvz_replay_roots": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P, _P,
+                                   _P]),
+    "rvz_replay_refresh_scratch_size": (C.c_int64, [C.c_int32]),
+    "rvz_replay_refresh": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P,
+                                     C.c_int32, _P, C.c_int64, _P, _P]),
     "rvz_records_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_records_games": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

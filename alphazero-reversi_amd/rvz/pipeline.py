@@ -53,8 +53,31 @@ class SelfPlayTrainer:
                  policy_target: str = "argmax", count_weights: bool = False,
                  replay_sampling: str = "uniform", replay_recency_decay: float = 1.0,
                  replay_priority_alpha: float = 0.6, replay_priority_beta=0.4,
-                 continuous_plies: Optional[int] = None, openings=None):
-        """openings: None (off: every game starts from the start position) or (black, white,
+                 continuous_plies: Optional[int] = None, openings=None,
+                 reanalyse_rows: int = 0, reanalyse_age: int = 0):
+        """reanalyse_rows: 0 (off: the code and the keys of before) or N: replay reanalysis
+        (MuZero's Reanalyse in this loop; ReplayBuffer(stamps=True).reanalyse, the
+        rvz_replay_stale / rvz_replay_roots / rvz_replay_refresh HIP kernels). After iteration t's
+        weight update, up to N of the stalest rows of the replay buffer whose policy target comes
+        from iteration t - reanalyse_age or earlier are searched again with the new net, on an
+        engine of their own (made once: `games` roots a chunk, the self-play simulation count and
+        batch, no root noise, pool or schedule, temperature 1) and their policy targets are
+        overwritten in place and stamped t; the value targets stay, the outcome of a game not
+        depending on the net. The rows that iteration t + 1's append will drop from the window
+        (ReplayBuffer.rows_leaving: those of iteration t - replay_iterations + 1 and earlier) are
+        left out of the selection: no training step would read them again. Every refreshed row
+        is therefore trained on for at least one more iteration, which needs
+        replay_iterations >= reanalyse_age + 2 for any row to qualify (ValueError otherwise).
+        The re-search's engine is checked (Engine.check) after every pass. It needs replay_iterations > 0, and reanalyse_age needs
+        reanalyse_rows > 0, ValueError otherwise. train() then also reports reanalyse/rows (the
+        rows rewritten), reanalyse/skipped (selected rows that were not: none is expected),
+        reanalyse/policy_kl (the mean over the rewritten rows of KL(new target || old target), the
+        old one floored at 1e-8: how far the new net's search has moved from the search that
+        played the row) and reanalyse_s (its wall time, device-synchronised; run_iteration's
+        train_s does not include it). The ring's sampling weights are not touched
+        (ReplayBuffer.reanalyse says what that means for merged and prioritized rows). Whether
+        this improves playing strength has not been measured.
+        openings: None (off: every game starts from the start position) or (black, white,
         side[, salt]): a pool of start positions (Engine.openings; rvz.opening_suite builds one),
         set before any graph is captured. Every self-play game, in lockstep and with
         continuous_plies alike, starts from the pool row its seed picks (rvz.opening_index); the
@@ -172,6 +195,19 @@ class SelfPlayTrainer:
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
         on 6x6): 2^20 slots = 608 MB, 2^12 = 2.4 MB."""
+        for name, x in (("reanalyse_rows", reanalyse_rows), ("reanalyse_age", reanalyse_age)):
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral) or x < 0:
+                raise ValueError(f"{name} must be an int >= 0, not {x!r}")
+        if reanalyse_rows and not replay_iterations:
+            raise ValueError("reanalyse_rows needs replay_iterations > 0: it refreshes the "
+                             "replay buffer's rows")
+        if reanalyse_age and not reanalyse_rows:
+            raise ValueError("reanalyse_age needs reanalyse_rows > 0")
+        if reanalyse_rows and replay_iterations < reanalyse_age + 2:
+            raise ValueError("reanalyse_rows needs replay_iterations >= reanalyse_age + 2: a row "
+                             "aged reanalyse_age iterations must stay in the window for the next "
+                             "iteration's training steps")
+        self.reanalyse_rows, self.reanalyse_age = int(reanalyse_rows), int(reanalyse_age)
         if policy_target not in ("argmax", "full"):
             raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
         if count_weights and policy_target != "full":
@@ -339,7 +375,12 @@ class SelfPlayTrainer:
                                        **(priority or
                                           ({"weighted": True,
                                             "recency_decay": self.replay_recency_decay}
-                                           if weighted else {})))
+                                           if weighted else {})),
+                                       **({"stamps": True} if self.reanalyse_rows else {}))
+        if self.reanalyse_rows:
+            # the re-search's own engine: the plain search, whatever self-play's engine has set
+            self.reanalyse_eng = Engine(games, num_simulations, batch_size, c_puct, board_size=bs,
+                                        device=self.device, compact_leaves=compact_leaves)
         self.iteration = 0
 
     def _seeds(self):
@@ -473,7 +514,39 @@ class SelfPlayTrainer:
         self.trainer.scheduler_step()          # pipeline.py:131, once per iteration
         self.model.eval()
         self.evaluator.refresh()               # also drops the engine's memo (the old net's outputs)
+        if self.reanalyse_rows:
+            out.update(self._reanalyse())
         return out
+
+    def _reanalyse(self) -> Dict[str, float]:
+        """Up to reanalyse_rows rows stamped iteration - reanalyse_age or earlier, searched again
+        with the net train() has just refreshed and stamped with this iteration."""
+        dev, t = self.device, self.iteration
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        below = t - self.reanalyse_age + 1
+        rows = skipped = 0
+        kl = 0.0
+        buf = self.buffer
+        if below > 0 and len(buf) > buf.rows_leaving(t + 1):
+            got = buf.reanalyse(self.reanalyse_eng, self.evaluator, self.reanalyse_rows,
+                                max(0, below - 65536), below, t, with_old=True,
+                                first=buf.rows_leaving(t + 1))
+            self.reanalyse_eng.check()          # the re-search's device error word
+            sel = got["slot"] >= 0
+            new = buf.policy[got["slot"].clamp(min=0).long()].double()
+            old = got["old_policy"].double().clamp(min=1e-8)
+            # a row that was not rewritten still holds its old target and adds 0 (but for the floor)
+            terms = torch.where(new > 0, new * (new.clamp(min=1e-300).log() - old.log()),
+                                torch.zeros_like(new))
+            total = (terms.sum(1) * sel).sum()
+            rows, skipped = (int(x) for x in got["counts"].tolist())
+            skipped -= got["slot"].numel() - int(got["selected"][0].item())   # not the padding
+            skipped -= (-got["slot"].numel()) % self.reanalyse_eng.n_games
+            kl = float(total.item()) / max(rows, 1)
+        torch.cuda.synchronize(dev)
+        return {"reanalyse/rows": rows, "reanalyse/skipped": skipped, "reanalyse/policy_kl": kl,
+                "reanalyse_s": time.perf_counter() - t0}
 
     def run_iteration(self) -> Dict[str, float]:
         """generate + train; wall times of both phases (device-synchronised) in the result. With
@@ -493,7 +566,8 @@ class SelfPlayTrainer:
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
         self.iteration += 1
-        out.update({"selfplay_s": t1 - t0, "train_s": t2 - t1, "board_steps": plies,
+        out.update({"selfplay_s": t1 - t0, "train_s": t2 - t1 - out.get("reanalyse_s", 0.0),
+                    "board_steps": plies,
                     "samples": int(data["policy_targets"].shape[0]),
                     "exact_rows": int(data.get("exact_rows", 0)),
                     "exact_unsolved": int(data.get("exact_unsolved", 0)),

@@ -641,3 +641,143 @@ def replay_priority(weight: torch.Tensor, slot: torch.Tensor, rows: torch.Tensor
                                       _addr(state), _lib.stream_handle(dev)), None,
               "rvz_replay_priority")
     return pri, state
+
+
+# ------------------------------------------------------------------ replay reanalysis
+STALE_MAX_CLASSES = 65536
+
+
+def check_stale_args(stamp, start, live, n, lo, below, who: str = "replay_stale") -> int:
+    """The argument rules of replay_stale, checked before any device call (the CPU tests' NumPy
+    restatement calls it too); returns the capacity."""
+    if not isinstance(stamp, torch.Tensor) or stamp.dim() != 1 or stamp.dtype != torch.int32 or \
+            not stamp.is_contiguous():
+        raise RvzError(f"{who}: stamp must be a contiguous int32 [capacity]")
+    _ints(who, start=start, live=live, n=n, lo=lo, below=below)
+    cap = stamp.numel()
+    _ring(who, cap, start, live, 1)
+    if not 0 <= n < 2 ** 31:
+        raise RvzError(f"{who}: n = {n} must be in [0, 2^31)")
+    if not (0 <= lo < below < 2 ** 31 and below - lo <= STALE_MAX_CLASSES):
+        raise RvzError(f"{who}: (lo, below) = ({lo}, {below}) must have 0 <= lo < below and "
+                       f"below - lo <= {STALE_MAX_CLASSES}")
+    return cap
+
+
+def check_roots_args(mover, opponent, slot, board_size, who: str = "replay_roots") -> int:
+    """The argument rules of replay_roots, checked before any device call; returns n."""
+    check_board_size(board_size, who)
+    if not all(isinstance(t, torch.Tensor) for t in (mover, opponent, slot)):
+        raise RvzError(f"{who}: mover, opponent and slot are tensors")
+    cap = _bitboards(who, mover, opponent, "mover and opponent", "slot")
+    if not 1 <= cap < 2 ** 31:
+        raise RvzError(f"{who}: the ring holds between 1 and 2^31 - 1 slots")
+    if slot.dim() != 1:
+        raise RvzError(f"{who}: slot holds one integer per row")
+    _given(who, slot.numel(), "row", optional=False, slot=slot)
+    return slot.numel()
+
+
+def check_refresh_args(policy, stamp, slot, p, idx, new_stamp, who: str = "replay_refresh"):
+    """The argument rules of replay_refresh, checked before any device call (the CPU tests'
+    NumPy restatement calls it too); returns (board_size, n)."""
+    if not isinstance(policy, torch.Tensor) or policy.dim() != 2 or \
+            policy.dtype != torch.float32 or not policy.is_contiguous() or \
+            policy.shape[1] not in (65, 37) or not 1 <= policy.shape[0] < 2 ** 31:
+        raise RvzError(f"{who}: policy must be a contiguous float32 [capacity, S*S+1] (it is "
+                       "written in place), S 8 or 6")
+    cap, npol = policy.shape
+    if not isinstance(stamp, torch.Tensor) or stamp.shape != (cap,) or \
+            stamp.dtype != torch.int32 or not stamp.is_contiguous() or \
+            stamp.device != policy.device:
+        raise RvzError(f"{who}: stamp must be a contiguous int32 [capacity] on the policy's device "
+                       "(it is written in place)")
+    if not isinstance(p, torch.Tensor) or p.dim() != 2 or p.shape[1] != npol or \
+            p.dtype != torch.float64:
+        raise RvzError(f"{who}: p must be float64 [n, {npol}], the act's probability rows")
+    n = p.shape[0]
+    if n > 2 ** 30:
+        raise RvzError(f"{who}: n must be at most 2^30")
+    if not isinstance(slot, torch.Tensor) or not isinstance(idx, torch.Tensor):
+        raise RvzError(f"{who}: slot and idx hold one integer per row of p")
+    _given(who, n, "row of p", optional=False, slot=slot, idx=idx)
+    _ints(who, new_stamp=new_stamp)
+    if not 0 <= new_stamp < 2 ** 31:
+        raise RvzError(f"{who}: new_stamp = {new_stamp} must be in [0, 2^31)")
+    return (8 if npol == 65 else 6), n
+
+
+def replay_stale(stamp: torch.Tensor, start: int, live: int, n: int, lo: int, below: int):
+    """rvz_replay_stale: the stalest rows of a ring, chosen on the device (include/rvz.h has the
+    rule). stamp int32 [capacity], contiguous, a device tensor: the iteration whose net produced
+    each slot's policy; the ring's `live` rows start at slot `start`, oldest first, and wrap. A
+    live row is eligible iff 0 <= stamp < below, its age class is max(stamp - lo, 0), and the
+    min(n, eligible) rows of the smallest classes are selected, ties in the last class going to
+    the older row. 0 <= lo < below, below - lo <= 65536. Returns (slot int32 [n]: the selected
+    slots in logical-row order, oldest first, then -1; count int32 [2]: the rows selected and the
+    live rows whose stamp is negative, which are never selected). Asynchronous on the current
+    stream; nothing synchronises. n = 0 launches nothing."""
+    cap = check_stale_args(stamp, start, live, n, lo, below)
+    lib = _lib.load()
+    dev = stamp.device
+    out = torch.empty(int(n), dtype=torch.int32, device=dev)
+    count = torch.zeros(2, dtype=torch.int32, device=dev)
+    if n:
+        size = lib.rvz_replay_stale_scratch_size(cap, int(below) - int(lo))
+        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
+        check(lib.rvz_replay_stale(cap, _addr(stamp), int(start), int(live), int(n), int(lo),
+                                   int(below), ptr(scratch), size, _addr(out), _addr(count),
+                                   _lib.stream_handle(dev)), None, "rvz_replay_stale")
+    return out, count
+
+
+def replay_roots(mover: torch.Tensor, opponent: torch.Tensor, slot: torch.Tensor,
+                 board_size: int = 8):
+    """rvz_replay_roots: ring rows as the arrays Engine.set_state takes. mover / opponent int64
+    [capacity] (bit patterns), slot [n] integers (replay_stale's), device tensors. Returns (black
+    int64 [n], white int64 [n], status int32 [n, 4], bad int32 [1]): for a slot in [0, capacity)
+    the mover as black, the opponent as white and {1, 0, -1, 0}, a live game with black to move;
+    for -1 empty boards and {1, 1, 0, 0}, a game that is over, which the engine does not search;
+    for any other slot, or a row whose bitboards overlap or leave the board, the same finished
+    row and one count in bad. Asynchronous on the current stream; nothing synchronises."""
+    n = check_roots_args(mover, opponent, slot, board_size)
+    lib = _lib.load()
+    dev = mover.device
+    mv, op = mover.contiguous(), opponent.to(dev).contiguous()
+    sl = _i32(slot, dev)
+    b = torch.empty(n, dtype=torch.int64, device=dev)
+    w = torch.empty(n, dtype=torch.int64, device=dev)
+    st = torch.empty(n, 4, dtype=torch.int32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n:
+        check(lib.rvz_replay_roots(board_size, mv.numel(), _addr(mv), _addr(op), n, _addr(sl),
+                                   _addr(b), _addr(w), ptr(st), _addr(bad),
+                                   _lib.stream_handle(dev)), None, "rvz_replay_roots")
+    return b, w, st, bad
+
+
+def replay_refresh(policy: torch.Tensor, stamp: torch.Tensor, slot: torch.Tensor,
+                   p: torch.Tensor, idx: torch.Tensor, new_stamp: int) -> torch.Tensor:
+    """rvz_replay_refresh: the act's rows written over a ring's policy targets (include/rvz.h has
+    the definition). policy float32 [capacity, S*S+1] and stamp int32 [capacity], contiguous,
+    written in place; slot [n] integers (what replay_roots took), p float64 [n, S*S+1] and idx [n]
+    integers: Engine.act(1.0, apply=False)'s rows and indices; device tensors. A row is skipped,
+    and its slot keeps its bytes, if its slot is outside [0, capacity) (the -1 padding), its idx is
+    -2 (the engine treated the game as over), it holds a negative or non-finite entry or its sum
+    is off 1 by more than 1e-9; any other row becomes policy[slot] = p.float() and stamp[slot] =
+    new_stamp, the last such row where several name one slot. Returns counts int32 [2]: the slots
+    written and the rows skipped. The ring's value, mover and opponent are no arguments.
+    Asynchronous on the current stream; nothing synchronises."""
+    board_size, n = check_refresh_args(policy, stamp, slot, p, idx, new_stamp)
+    lib = _lib.load()
+    dev = policy.device
+    sl, ix, pp = _i32(slot, dev), _i32(idx, dev), p.to(dev).contiguous()
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    if n:
+        size = lib.rvz_replay_refresh_scratch_size(n)
+        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
+        check(lib.rvz_replay_refresh(board_size, policy.shape[0], _addr(policy), _addr(stamp), n,
+                                     _addr(sl), _addr(pp), _addr(ix), int(new_stamp),
+                                     ptr(scratch), size, _addr(counts),
+                                     _lib.stream_handle(dev)), None, "rvz_replay_refresh")
+    return counts

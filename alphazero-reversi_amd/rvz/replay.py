@@ -18,6 +18,11 @@ that: new rows enter at the running maximum priority, ``update_priorities`` writ
 batch's losses back as the rows' weights (``rvz.replay_priority`` / rvz_replay_priority) and
 ``is_weights`` corrects the sampling bias in the loss (``rvz.replay_is_weight`` /
 rvz_replay_is_weight).
+
+``ReplayBuffer(stamps=True)`` adds a stamp per row, the iteration whose net produced the row's
+policy target, and ``reanalyse``: the stalest rows are searched again with the current net and
+their policy targets overwritten in place (MuZero's Reanalyse in an AlphaZero loop;
+``rvz.replay_stale`` / ``rvz.replay_roots`` / ``rvz.replay_refresh``, csrc/rvz_reanalyse.hip).
 """
 from __future__ import annotations
 
@@ -29,7 +34,8 @@ import torch
 from . import _lib
 from ._lib import RvzError
 from .records import (check_priority_args, replay_batch, replay_batch_weighted, replay_cdf,
-                      replay_is_weight, replay_priority)
+                      replay_is_weight, replay_priority, replay_refresh, replay_roots,
+                      replay_stale)
 
 
 class ReplayBuffer:
@@ -38,7 +44,8 @@ class ReplayBuffer:
                  recency_decay: float = 1.0, weighted_batcher=None, cdf_builder=None,
                  prioritized: bool = False, priority_alpha: float = 0.6,
                  priority_floor: float = 2.0 ** -8, priority_cap: float = 2.0 ** 8,
-                 subtract_entropy: bool = True, priority_updater=None, is_weighter=None):
+                 subtract_entropy: bool = True, priority_updater=None, is_weighter=None,
+                 stamps: bool = False):
         """capacity: the ring's rows. window_iterations = K > 0: an append of iteration t also
         drops every row of an iteration before t - K + 1 (0: rows leave only when overwritten).
         batcher(mover, opponent, policy, value, start, live, nb, seed, step, random_sym, idx, sym,
@@ -77,7 +84,11 @@ class ReplayBuffer:
         priority_updater(weight, slot, rows, policy_coef, value_coef, subtract_entropy, alpha,
         floor, cap, max_priority) -> (priority, state), writing weight and max_priority in place:
         default rvz.replay_priority. is_weighter(prob, slot, beta) -> weight: default
-        rvz.replay_is_weight."""
+        rvz.replay_is_weight.
+        stamps=True: the ring also holds `stamp` int32 [capacity], the iteration whose net
+        produced each row's policy target: append's `stamp` (default: its iteration), and what
+        reanalyse() selects by and rewrites. Without it the buffer allocates nothing more and
+        behaves exactly as before."""
         for name, x in (("capacity", capacity), ("window_iterations", window_iterations)):
             if isinstance(x, bool) or not isinstance(x, numbers.Integral):
                 raise ValueError(f"ReplayBuffer: {name} is an int, not {x!r}")
@@ -115,6 +126,9 @@ class ReplayBuffer:
         self.start = 0                  # the slot of the oldest row
         self._live = 0
         self._ledger: List[List[int]] = []      # [iteration, rows], oldest first
+        self.stamps = bool(stamps)
+        if self.stamps:
+            self.stamp = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
         if self.weighted:
             self.recency_decay = float(recency_decay)
             self.weighted_batcher = (replay_batch_weighted if weighted_batcher is None
@@ -160,12 +174,14 @@ class ReplayBuffer:
 
     def append(self, mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
                value: torch.Tensor, iteration: int,
-               weight: Optional[torch.Tensor] = None) -> None:
+               weight: Optional[torch.Tensor] = None, stamp: Optional[int] = None) -> None:
         """n <= capacity rows of `iteration` at the head of the ring (at most two slice copies per
         tensor), over the oldest rows once the ring is full. mover / opponent int64 [n], policy
         float32 [n, S*S+1], value float32 [n] or [n, 1]. Iterations are appended in
         non-decreasing order. weight (weighted=True only): float32 [n], the rows' sampling
-        weights; None: 1.0 each (prioritized=True: the running maximum priority each)."""
+        weights; None: 1.0 each (prioritized=True: the running maximum priority each). stamp
+        (stamps=True only): the iteration whose net produced the rows' policy targets, an int in
+        [0, 2^31); None: `iteration`."""
         if isinstance(iteration, bool) or not isinstance(iteration, numbers.Integral):
             raise ValueError(f"ReplayBuffer.append: iteration is an int, not {iteration!r}")
         n = mover.numel()
@@ -183,6 +199,14 @@ class ReplayBuffer:
                 raise ValueError("ReplayBuffer.append: weight needs ReplayBuffer(weighted=True)")
             if weight.shape != (n,) or weight.dtype != torch.float32:
                 raise ValueError("ReplayBuffer.append: weight is float32 [n]")
+        if stamp is not None and not self.stamps:
+            raise ValueError("ReplayBuffer.append: stamp needs ReplayBuffer(stamps=True)")
+        if self.stamps:
+            stamp = iteration if stamp is None else stamp
+            if isinstance(stamp, bool) or not isinstance(stamp, numbers.Integral) or \
+                    not 0 <= stamp < 2 ** 31:
+                raise ValueError(f"ReplayBuffer.append: stamp is an int in [0, 2^31), not "
+                                 f"{stamp!r}")
         if n > self.capacity:
             raise ValueError(f"ReplayBuffer.append: {n} rows do not fit a ring of {self.capacity}")
         if self._ledger and iteration < self._ledger[-1][0]:
@@ -209,6 +233,10 @@ class ReplayBuffer:
                 ring[head:head + first].copy_(rows[:first])
                 if first < n:
                     ring[:n - first].copy_(rows[first:])
+            if self.stamps:
+                self.stamp[head:head + first] = int(stamp)
+                if first < n:
+                    self.stamp[:n - first] = int(stamp)
             if self._ledger and self._ledger[-1][0] == iteration:
                 self._ledger[-1][1] += n
             else:
@@ -302,3 +330,99 @@ class ReplayBuffer:
         """The running maximum priority: what the next appended row enters at. Synchronises."""
         self._need_priorities("max_priority")
         return float(self._max_priority.item())
+
+    def rows_leaving(self, iteration: int) -> int:
+        """The oldest rows held that an append of `iteration` would drop through
+        window_iterations (0 without a window): the rows of every iteration before
+        iteration - window_iterations + 1. Rows that leave because the head runs over them in a
+        full ring are not counted: that depends on the size of the append."""
+        if not self.window_iterations:
+            return 0
+        return sum(rows for it, rows in self._ledger
+                   if it < iteration - self.window_iterations + 1)
+
+    def reanalyse(self, engine, evaluator, rows: int, lo: int, below: int, new_stamp: int,
+                  with_old: bool = False, first: int = 0):
+        """Replay reanalysis: up to `rows` of the stalest rows held (stamp below `below`, the
+        stamps at or below `lo` counting as equally stale; rvz.replay_stale) are searched again by
+        `engine` with `evaluator`, the current net, and their policy targets and stamps are
+        overwritten in place with the new search's visit distributions and new_stamp. In chunks
+        of engine.n_games rows, the last one padded with -1: rvz.replay_roots, engine.set_state,
+        engine.memo_reset() where the memo is on, engine.search(evaluator), engine.act(1.0,
+        apply=False) with a given draw (the act's probability rows do not depend on it, and the
+        engine's own draw streams stay where they are), rvz.replay_refresh. The pull-style search
+        is the one that runs, not the fused rvz_play. value, mover and opponent are not touched:
+        the outcome of the game does not depend on the net.
+        The ring's sampling weights are not touched either. A merged row's fresh policy replaces
+        the mean policy of its records, and the row keeps its record count as its weight. In a
+        prioritized ring the row keeps its priority, and the next training step that draws it sets
+        a new one from its loss against the fresh target.
+        Returns a dict of device tensors, nothing synchronised beyond set_state's own wait:
+        first: the selection leaves out the `first` oldest rows held (0 <= first <= len(self)):
+        rows_leaving(t + 1) of them when the rows are next trained on after an append of
+        iteration t + 1, which drops those rows unread.
+        "slot" int32 [rows] (the selected slots, oldest first, then -1), "selected" int32 [2]
+        (replay_stale's count: the rows selected, the held rows with a negative stamp), "counts"
+        int64 [2] (the slots written, the rows skipped, padding included), "bad" int64 [1]
+        (replay_roots' count), and with with_old=True "old_policy" float32 [rows, S*S+1]: the
+        selected rows' targets before the refresh (a row of slot -1 holds slot 0's).
+        ValueError: a buffer without stamps=True, an engine with root noise, an opening pool or a
+        temperature schedule set (the re-search must be the plain search at temperature 1), or
+        one whose board size differs from the ring's."""
+        who = "ReplayBuffer.reanalyse"
+        if not self.stamps:
+            raise ValueError(f"{who} needs ReplayBuffer(stamps=True)")
+        noise = getattr(engine, "noise", None)
+        if noise is not None and noise[1] != 0.0:
+            raise ValueError(f"{who}: the engine has root noise set")
+        if getattr(engine, "pool", None) is not None:
+            raise ValueError(f"{who}: the engine has an opening pool set")
+        if getattr(engine, "schedule", None) is not None:
+            raise ValueError(f"{who}: the engine has a temperature schedule set")
+        if engine.board_size != self.board_size:
+            raise ValueError(f"{who}: the engine plays {engine.board_size}x{engine.board_size}, "
+                             f"the ring holds {self.board_size}x{self.board_size}")
+        for name, x in (("rows", rows), ("lo", lo), ("below", below), ("new_stamp", new_stamp)):
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+                raise ValueError(f"{who}: {name} is an int, not {x!r}")
+        if isinstance(first, bool) or not isinstance(first, numbers.Integral) or \
+                not 0 <= first <= self._live:
+            raise ValueError(f"{who}: first = {first!r} must be an int in [0, {self._live}]")
+        rows, G, first = int(rows), engine.n_games, int(first)
+        out = {"slot": torch.full((max(rows, 0),), -1, dtype=torch.int32, device=self.device),
+               "selected": torch.zeros(2, dtype=torch.int32, device=self.device),
+               "counts": torch.zeros(2, dtype=torch.int64, device=self.device),
+               "bad": torch.zeros(1, dtype=torch.int64, device=self.device)}
+        if with_old:
+            out["old_policy"] = torch.zeros(max(rows, 0), self.policy.shape[1],
+                                            dtype=torch.float32, device=self.device)
+        if self._live == first or rows <= 0:
+            if rows < 0:
+                raise ValueError(f"{who}: rows must be >= 0")
+            return out
+        try:
+            slot, out["selected"] = replay_stale(self.stamp, (self.start + first) % self.capacity,
+                                                 self._live - first, rows, lo, below)
+        except RvzError as err:
+            raise ValueError(str(err)) from None
+        out["slot"] = slot
+        if with_old:
+            out["old_policy"] = self.policy[slot.clamp(min=0).long()]
+        pad = (-rows) % G
+        if pad:
+            slot = torch.cat([slot, torch.full((pad,), -1, dtype=torch.int32,
+                                               device=self.device)])
+        u = torch.full((G,), 0.5, dtype=torch.float64, device=self.device)
+        for at in range(0, rows, G):
+            chunk = slot[at:at + G]
+            black, white, status, bad = replay_roots(self.mover, self.opponent, chunk,
+                                                     self.board_size)
+            engine.set_state(black, white, status)
+            if engine.memo_on:
+                engine.memo_reset()
+            engine.search(evaluator)
+            idx, p = engine.act(1.0, u=u, apply=False)
+            counts = replay_refresh(self.policy, self.stamp, chunk, p, idx, new_stamp)
+            out["counts"] += counts
+            out["bad"] += bad
+        return out

@@ -721,6 +721,106 @@ int rvz_replay_priority(int32_t capacity, float *weight /* [capacity], in/out */
                         float *out_priority /* [nb], nullable */,
                         int32_t *out_state /* [nb], nullable */, void *hip_stream);
 
+/* ---- replay reanalysis: stale policy targets refreshed by a new search ----------------------
+ * With a window of K iterations the trainer learns from rows whose policy target is the visit
+ * distribution of the net that played them, up to K checkpoints ago. The ring stores positions as
+ * (mover, opponent) bitboards, so a row can be searched again: MuZero's Reanalyse (Schrittwieser
+ * et al., 2020) in an AlphaZero loop. The three calls below (csrc/rvz_reanalyse.hip) are the record
+ * side of that loop; the search between the last two is the engine's own (rvz_env_set,
+ * rvz_search_*, rvz_act at temperature 1 with apply = 0). The ring gains stamp int32 [capacity]:
+ * the iteration whose net produced the slot's policy. The outcome `value` does not depend on the
+ * net and is no argument of any of the three: they cannot touch it.
+ * All three are stateless, on caller arrays (device pointers), asynchronous on hip_stream and
+ * graph-capturable: no allocation, no copy, no memset, no synchronisation; the scratch needs no
+ * preparation; no workgroup waits on another (consecutive launches); rows are checked in the
+ * kernel, no host synchronisation. Only integer atomics are used and nothing floating-point is
+ * reduced across rows, so equal inputs give equal bytes.
+ *
+ * rvz_replay_stale: the request (n, lo, below), 0 <= lo < below, below - lo <= 65536, over the
+ * ring's live rows (capacity, start, live as in rvz_replay_batch; logical row i, oldest first, in
+ * slot (start + i) % capacity; slots outside the live rows are never read).
+ *   A live row is eligible iff 0 <= stamp < below; its age class is max(stamp - lo, 0), so every
+ *   stamp at or below lo shares class 0. A negative stamp is out of range: the row is ineligible
+ *   and counted in out_count[1].
+ *   The call selects min(n, eligible) rows with the smallest age classes; ties in the last class
+ *   taken go to the older logical row (the smaller i).
+ *   out_slot int32 [n]: the selected rows' slots in logical-row order, oldest first, then -1 up
+ *   to n; every element is written exactly once. out_count int32 [2]: the rows selected, and the
+ *   live rows with a stamp out of range.
+ * The computation: a class histogram in the scratch (cleared, then integer atomicAdd, once per
+ * distinct class of a wavefront, through a histogram per workgroup in LDS up to 2,048 classes); one workgroup scans the classes to the threshold class T and
+ * the rows `take` wanted from it; a tiled stable compaction in consecutive launches (tiles of 1,024
+ * rows): per-tile counts of the rows below T and of the rows in T, one scan of the pairs, then the
+ * write, a selected row going to (rows below T before it) + min(rows of T before it, take).
+ * rvz_replay_stale_scratch_size(capacity, classes): the scratch's bytes for a ring of `capacity`
+ * slots and classes = below - lo (16 + 4 per class + 8 per tile of the capacity, each part rounded
+ * up to 16), non-decreasing in both; negative for capacity < 1 or classes outside [1, 65536].
+ * RVZ_EINVAL (before any HIP call): capacity < 1, live outside [1, capacity], start outside
+ * [0, capacity), n < 0, lo < 0, below <= lo, below - lo > 65536, and with n > 0 a null stamp /
+ * out_slot / out_count / scratch, a scratch that is not 16-byte aligned or scratch_bytes below
+ * what the size function reports. n = 0 returns RVZ_OK without a launch, and then nothing is
+ * written.
+ *
+ * rvz_replay_roots: n ring rows as the arrays rvz_env_set takes, one lane per row.
+ *   0 <= slot[r] < capacity: out_black[r] = mover[slot], out_white[r] = opponent[slot] and
+ *     out_status[r] = {1, 0, -1, 0}: a live game with black to move, no winner, no pass behind
+ *     it, as rvz_replay_batch also treats the mover as black.
+ *   slot[r] == -1: empty boards and out_status[r] = {1, 1, 0, 0}, a game that is over: the engine
+ *     searches nothing for it and rvz_act answers -2.
+ *   Any other slot, or a row whose two bitboards overlap or hold a bit at or above S*S: the same
+ *     finished row, and one count in out_bad int32 [1] (cleared by the call's first launch).
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, capacity < 1, n < 0 or n > 2^30, and with
+ * n > 0 a null pointer or an out_status that is not 16-byte aligned. n = 0 returns RVZ_OK without a
+ * launch.
+ *
+ * rvz_replay_refresh: the act's rows written over the old targets. slot int32 [n] (what
+ * rvz_replay_roots took), p float64 [n][S*S+1] and idx int32 [n]: rvz_act's out_p and out_idx at
+ * temperature 1. One wavefront per row. Row r is skipped, and writes nothing, iff
+ *   slot[r] is outside [0, capacity) (the -1 padding among them), or idx[r] == -2 (the engine
+ *   treated the game as over), or the row holds a negative or non-finite entry, or its float64
+ *   sum s has |s - 1| > 1e-9; s is defined as: x_l = p[r][l] for l < min(S*S+1, 64), 0 for the
+ *   other l < 64; x_0 += p[r][64] on 8x8; then for d = 32, 16 .. 1: x_l = x_l + x_(l ^ d).
+ * A row that is not skipped sums to 1 by construction: it is the act's pairwise sum
+ * (rvz_action_probs). policy float32 [capacity][S*S+1] and stamp int32 [capacity] (in/out) become
+ * what the sequential loop
+ *   for r in 0 .. n - 1: if not skipped(r): policy[slot[r]][j] = (float) p[r][j] for every j
+ *                                           stamp[slot[r]] = new_stamp
+ * leaves: where several rows name one slot the one with the highest r wins (the slot table of
+ * rvz_replay_priority, csrc/rvz_slot_table.hip.h), and a slot no unskipped row names keeps its
+ * bytes. The result does not depend on timing. Offsets into the ring are 64-bit.
+ *   out_counts int32 [2] (cleared by the call's first launch) = {the slots written, the rows
+ *   skipped}; n less both is the rows a later row superseded.
+ * The caller guarantees that no append has overwritten the slots since rvz_replay_stale chose
+ * them. policy, stamp, slot, p, idx, the scratch and out_counts must not overlap.
+ * rvz_replay_refresh_scratch_size(n): the scratch's bytes (4 per row + a hash table of the power
+ * of two >= max(2 n, 64) entries of 8 bytes), non-decreasing in n; negative for n < 0 or n > 2^30.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, capacity < 1, n < 0 or n > 2^30,
+ * new_stamp < 0, and with n > 0 a null policy / stamp / slot / p / idx / out_counts / scratch, a
+ * scratch that is not 16-byte aligned or scratch_bytes below what the size function reports.
+ * n = 0 returns RVZ_OK without a launch, and then nothing is written.
+ *
+ * Not done: a value refresh (blending z with the search's root Q: rvz_play's forced searches and
+ * its deferred last batch rely on W staying unread), and the fused rvz_play path for the
+ * re-search: the pull-style search ships. */
+int64_t rvz_replay_stale_scratch_size(int32_t capacity, int32_t classes);
+int rvz_replay_stale(int32_t capacity, const int32_t *stamp /* [capacity] */, int32_t start,
+                     int32_t live, int32_t n, int32_t lo, int32_t below,
+                     void *scratch /* 16-byte aligned */, int64_t scratch_bytes,
+                     int32_t *out_slot /* [n] */, int32_t *out_count /* [2] */, void *hip_stream);
+int rvz_replay_roots(int32_t board_size, int32_t capacity, const uint64_t *mover,
+                     const uint64_t *opponent /* [capacity] */, int32_t n,
+                     const int32_t *slot /* [n] */, uint64_t *out_black, uint64_t *out_white,
+                     int32_t *out_status /* [n][4], 16-byte aligned */,
+                     int32_t *out_bad /* [1] */, void *hip_stream);
+int64_t rvz_replay_refresh_scratch_size(int32_t n);
+int rvz_replay_refresh(int32_t board_size, int32_t capacity,
+                       float *policy /* [capacity][S*S+1], in/out */,
+                       int32_t *stamp /* [capacity], in/out */, int32_t n,
+                       const int32_t *slot /* [n] */, const double *p /* [n][S*S+1] */,
+                       const int32_t *idx /* [n] */, int32_t new_stamp,
+                       void *scratch /* 16-byte aligned */, int64_t scratch_bytes,
+                       int32_t *out_counts /* [2] */, void *hip_stream);
+
 /* ---- continuous self-play records: a window of autoreset play cut into finished games -------
  * rvz_play with reset = 1 keeps every slot busy: a finished game restarts at once, and a slot's
  * column of the records (rec_black / rec_white / rec_side / rec_p / hist at [ply][game]) holds
