@@ -19,6 +19,8 @@
 //   k_loss_grads   (with gradients) one wavefront per row: p = exp(z - lse) again from the saved
 //                  lse, then the two gradients, scaled by w / W.
 // No floating-point atomics anywhere; every output element is written by exactly one lane.
+// rvz_ownership_loss (the auxiliary ownership head's loss) runs its own two row kernels around the
+// same k_loss_reduce, on the same scratch.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -250,7 +252,97 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_loss_grads(
         grad_value[r] = (float)(cv * 2.0 * ((double)value[r] - (double)value_target[r]));
 }
 
+// ---------------------------------------------------------------- the ownership loss
+// rvz_ownership_loss: the same three kinds of launch on the same scratch. A row is S*S squares,
+// lane = square; its terms go into the six arrays of the tree in the policy loss's places (w,
+// w L, 0, 0, w agree, malformed), so k_loss_reduce sums and finishes them as it is, with the
+// weights 1 and 0: out_loss = {L, L, 0, 0, W, agreement, malformed, 0}.
+template <int BS>
+__global__ __launch_bounds__(LOSS_THREADS) void k_own_rows(
+    int n, const float* __restrict__ logits, const float* __restrict__ target,
+    const float* __restrict__ weight, double* __restrict__ term, double* __restrict__ out_row) {
+    constexpr int NSQ = BS * BS;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int r = blockIdx.x * LOSS_WAVES + wave;        // n * (NSQ + 1) fits int32
+    if (r >= n) return;                                  // wave-uniform
+    const bool in = lane < NSQ;
+    const float o = in ? logits[(size_t)r * NSQ + lane] : 0.0f;
+    const float t = in ? target[(size_t)r * NSQ + lane] : 0.0f;
+    const float wf = weight ? weight[r] : 1.0f;
+    const bool bad = !finite32(o) || !(t == -1.0f || t == 0.0f || t == 1.0f) ||
+                     !(wf >= 0.0f && wf <= FLT_MAX);
+    const bool ok = __ballot(bad) == 0;
+    double L = 0.0, w = 0.0, agree = 0.0;
+    if (ok) {                                            // wave-uniform
+        const double d = in ? tanh((double)o) - (double)t : 0.0;
+        L = wave_sum(d * d) / (double)NSQ;
+        const int labelled = __popcll(__ballot(t != 0.0f));
+        const int hits = __popcll(__ballot((t > 0.0f && o > 0.0f) || (t < 0.0f && o < 0.0f)));
+        agree = labelled ? (double)hits / (double)labelled : 0.0;
+        w = (double)wf;
+    }
+    if (lane == 0) {
+        term[r] = w;
+        term[(size_t)n + r] = w * L;
+        term[2 * (size_t)n + r] = 0.0;
+        term[3 * (size_t)n + r] = 0.0;
+        term[4 * (size_t)n + r] = w * agree;
+        term[5 * (size_t)n + r] = ok ? 0.0 : 1.0;
+        if (out_row) {
+            out_row[2 * (size_t)r] = L;
+            out_row[2 * (size_t)r + 1] = agree;
+        }
+    }
+}
+
+template <int BS>
+__global__ __launch_bounds__(LOSS_THREADS) void k_own_grads(
+    int n, const float* __restrict__ logits, const float* __restrict__ target,
+    const double* __restrict__ term, const double* __restrict__ hdr,
+    float* __restrict__ grad_logits) {
+    constexpr int NSQ = BS * BS;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int r = blockIdx.x * LOSS_WAVES + wave;
+    if (r >= n || lane >= NSQ) return;
+    const double W = hdr[0], w = term[r];                // w: 0 for a malformed row
+    const size_t at = (size_t)r * NSQ + lane;
+    if (!(W > 0.0) || !(w > 0.0)) {                      // wave-uniform: nothing of the row is read
+        grad_logits[at] = 0.0f;
+        return;
+    }
+    const double th = tanh((double)logits[at]);
+    grad_logits[at] =
+        (float)((w / W) * (2.0 / (double)NSQ) * (th - (double)target[at]) * (1.0 - th * th));
+}
+
 }  // namespace
+
+extern "C" int64_t rvz_ownership_loss_scratch_size(int32_t bs, int32_t n) {
+    return Layout(bs, n, nullptr).total;                 // the policy loss's scratch, as it is
+}
+
+extern "C" int rvz_ownership_loss(int32_t bs,int32_t n, const float* logits, const float* target,
+                                  const float* weight, void* scratch, double* out_loss,
+                                  double* out_row, float* grad_logits, void* stream) {
+    const Layout L(bs, n, scratch);
+    if (L.total < 0) return RVZ_EINVAL;
+    if (n > 0 && (!logits || !target || !scratch_ok(scratch) || !out_loss)) return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const Geometry rows = wave_per_row(n, LOSS_WAVES);
+    launch_bs_unchecked(bs, k_own_rows<8>, k_own_rows<6>, rows.grid, rows.block, s, n, logits,
+                        target, weight, L.level[0], out_row);
+    for (int k = 0; k < L.levels; ++k) {
+        double* dst = k + 1 < L.levels ? L.level[k + 1] : nullptr;
+        hipLaunchKernelGGL(k_loss_reduce, dim3(L.count[k + 1]), dim3(RED_THREADS), 0, s,
+                           L.count[k], (const double*)L.level[k], dst, 1.0, 0.0, L.hdr, out_loss);
+    }
+    if (!grad_logits) return last_launch();
+    return launch_bs(bs, k_own_grads<8>, k_own_grads<6>, rows.grid, rows.block, s, n, logits,
+                     target, (const double*)L.level[0], (const double*)L.hdr, grad_logits);
+}
 
 extern "C" int64_t rvz_loss_scratch_size(int32_t bs, int32_t n) {
     return Layout(bs, n, nullptr).total;

@@ -1,5 +1,6 @@
 // rvz_records.hip — a window of autoreset self-play records cut into finished games
-// (rvz_records_games; contract in include/rvz.h).
+// (rvz_records_games; contract in include/rvz.h), and the final position of the game a record
+// belongs to (rvz_records_final, the ownership target; its kernels stand before the entry points).
 //
 // rvz_play with reset = 1 writes one record per ply and slot, a slot's games one after another.
 // Three consecutive launches on one stream turn a window [plies][n_games] of such records into the
@@ -225,6 +226,86 @@ __global__ __launch_bounds__(ROWS_THREADS) void k_rec_rows(
     }
 }
 
+// rvz_records_final, a lane per row: the walk of the contract from the row's own record down its
+// slot's column to the end of its game. The wave's four counts go to out_stats as 64-bit integer
+// adds (k_final_clear zeroed them in the launch before), so their sums depend on no order.
+constexpr int FINAL_THREADS = 64;                // one wave a workgroup: the ballots below are its own
+constexpr int FIN_OK = 1, FIN_OPEN = 2, FIN_OTHER = 3;
+
+__global__ void k_final_clear(int64_t* __restrict__ out_stats) {
+    if (threadIdx.x < 4) out_stats[threadIdx.x] = 0;
+}
+
+template <int BS>
+__global__ __launch_bounds__(FINAL_THREADS) void k_rec_final(
+    int plies, int n_games, const uint64_t* __restrict__ rec_black,
+    const uint64_t* __restrict__ rec_white, const int32_t* __restrict__ rec_side,
+    const int32_t* __restrict__ rec_idx, int n, const int32_t* __restrict__ src,
+    const int32_t* __restrict__ count, uint64_t* __restrict__ out_final_mover,
+    uint64_t* __restrict__ out_final_opponent, int32_t* __restrict__ out_ok,
+    int64_t* __restrict__ out_stats) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    const int64_t j = (int64_t)blockIdx.x * FINAL_THREADS + threadIdx.x;
+    int bound = n;
+    if (count) {
+        const int c = *count;
+        bound = c < n ? (c < 0 ? 0 : c) : n;
+    }
+    const bool handled = j < bound;
+    int code = 0;
+    if (handled) {
+        code = FIN_OTHER;
+        const int s = src[j];
+        const int records = plies * n_games;                            // fits: shape_ok
+        uint64_t fm = 0ull, fo = 0ull;
+        if (s >= 0 && s < records && rec_idx[s] >= 0) {
+            const size_t G = (size_t)n_games;
+            const int g = s % n_games;
+            GameS cur = {0ull, 0ull, 1, 0, -1, 0};
+            int mover = 0;                                              // the row's own side
+            code = FIN_OPEN;
+            for (int p = s / n_games; p < plies; ++p) {
+                const size_t at = (size_t)p * G + g;
+                const int idx = rec_idx[at];
+                if (idx < 0) continue;                                  // a ply without a record
+                const uint64_t b = rec_black[at], w = rec_white[at];
+                const int side = rec_side[at];
+                bool ok = !(b & w) && !((b | w) & ~Geo<BS>::FULL) && (side == 1 || side == 2) &&
+                          idx <= NSQ;
+                if (ok && mover) ok = b == cur.black && w == cur.white && side == cur.side;
+                if (ok) {
+                    if (!mover) {
+                        cur = GameS{b, w, side, 0, -1, 0};
+                        mover = side;
+                    }
+                    ok = make_move<BS>(cur, idx == NSQ ? -1 : idx);
+                }
+                if (!ok) {                                              // malformed, refused, broken
+                    code = FIN_OTHER;
+                    break;
+                }
+                if (cur.over) {
+                    code = FIN_OK;
+                    break;
+                }
+            }
+            if (code == FIN_OK) {
+                fm = mover == 1 ? cur.black : cur.white;
+                fo = mover == 1 ? cur.white : cur.black;
+            }
+        }
+        out_final_mover[j] = fm;
+        out_final_opponent[j] = fo;
+        out_ok[j] = code == FIN_OK ? 1 : 0;
+    }
+    const int c0 = __popcll(__ballot(handled)), c1 = __popcll(__ballot(code == FIN_OK)),
+              c2 = __popcll(__ballot(code == FIN_OPEN)), c3 = __popcll(__ballot(code == FIN_OTHER));
+    if (threadIdx.x < 4) {
+        const int c = threadIdx.x == 0 ? c0 : (threadIdx.x == 1 ? c1 : (threadIdx.x == 2 ? c2 : c3));
+        if (c) atomicAdd((unsigned long long*)out_stats + threadIdx.x, (unsigned long long)c);
+    }
+}
+
 inline bool shape_ok(int64_t plies, int64_t n_games, int npol) {
     return plies >= 1 && n_games >= 1 && plies <= INT32_MAX / n_games &&
            plies * n_games <= INT32_MAX / npol;     // plies * n_games * npol < 2^31
@@ -265,4 +346,23 @@ extern "C" int rvz_records_games(int32_t bs, int32_t plies, int32_t n_games,
                      rec_black, rec_white, rec_p, (const int32_t*)l.info, (const int32_t*)l.rank,
                      (const int64_t*)l.offset, out_mover, out_opponent, out_policy, out_value,
                      out_src, out_state);
+}
+
+extern "C" int rvz_records_final(int32_t bs, int32_t plies, int32_t n_games,
+                                 const uint64_t* rec_black, const uint64_t* rec_white,
+                                 const int32_t* rec_side, const int32_t* rec_idx, int32_t n,
+                                 const int32_t* src, const int32_t* count,
+                                 uint64_t* out_final_mover, uint64_t* out_final_opponent,
+                                 int32_t* out_ok, int64_t* out_stats, void* stream) {
+    if (!board_ok(bs) || !shape_ok(plies, n_games, bs * bs + 1) || n < 0) return RVZ_EINVAL;
+    if (!rec_black || !rec_white || !rec_side || !rec_idx || !out_stats) return RVZ_EINVAL;
+    if (n > 0 && (!src || !out_final_mover || !out_final_opponent || !out_ok)) return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_final_clear, dim3(1), dim3(64), 0, s, out_stats);
+    return launch_bs(bs, k_rec_final<8>, k_rec_final<6>,
+                     dim3((unsigned)(((int64_t)n + FINAL_THREADS - 1) / FINAL_THREADS)),
+                     dim3(FINAL_THREADS), s, plies, n_games, rec_black, rec_white, rec_side,
+                     rec_idx, n, src, count, out_final_mover, out_final_opponent, out_ok,
+                     out_stats);
 }

@@ -22,6 +22,9 @@
 // rvz_replay_batch_weighted is k_replay_batch with another draw: t = mulhi64(u, total) of a
 // uniform 64-bit word u, and the row is the first i with C[i] > t, found 64 pivots at a time (a
 // load per lane and one ballot per round, 4 rounds at 2^21 rows).
+//
+// rvz_replay_ownership: a drawn batch's final-ownership targets from two more bitboards a slot, a
+// second small kernel on the draw's own out_slot / out_sym (k_replay_ownership).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -257,7 +260,51 @@ int batch(int bs, int capacity, const uint64_t* mover, const uint64_t* opponent,
                      out_slot, out_sym);
 }
 
+// The ownership target of a drawn row (rvz_replay_ownership): one wavefront per output row, lane =
+// output square. The slot and the symmetry are those k_replay_batch reported for the row, so the
+// source square is the one its state planes were read from (sym_src).
+template <int BS>
+__global__ __launch_bounds__(SYM_THREADS) void k_replay_ownership(
+    int capacity, const uint64_t* __restrict__ final_mover,
+    const uint64_t* __restrict__ final_opponent, int nb, const int32_t* __restrict__ slot,
+    const int32_t* __restrict__ sym, float* __restrict__ out_own, float* __restrict__ out_margin) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int stride = gridDim.x * SYM_WAVES;       // nb * NPOL fits int32, so r + stride does too
+    for (int r = blockIdx.x * SYM_WAVES + wave; r < nb; r += stride) {  // wave-uniform trip count
+        const int s = slot[r], k = sym[r];
+        uint64_t P = 0ull, O = 0ull;
+        if (s >= 0 && s < capacity && k >= 0 && k < 8) {                // wave-uniform
+            P = final_mover[s];
+            O = final_opponent[s];
+            if ((P & O) || ((P | O) & ~Geo<BS>::FULL)) P = O = 0ull;
+        }
+        if (lane < NSQ) {
+            const int from = sym_src<BS>(lane, k & 7);
+            out_own[(size_t)r * NSQ + lane] =
+                (float)((int)((P >> from) & 1ull) - (int)((O >> from) & 1ull));
+        }
+        if (lane == 0) out_margin[r] = (float)((int)__popcll(P) - (int)__popcll(O));
+    }
+}
+
 }  // namespace
+
+extern "C" int rvz_replay_ownership(int32_t bs, int32_t capacity, const uint64_t* final_mover,
+                                    const uint64_t* final_opponent, int32_t nb,
+                                    const int32_t* slot, const int32_t* sym, float* out_own,
+                                    float* out_margin, void* stream) {
+    if (!board_ok(bs) || capacity < 1 || nb < 0) return RVZ_EINVAL;
+    if ((int64_t)nb * (bs * bs + 1) > INT32_MAX) return RVZ_EINVAL;
+    if (nb > 0 && (!final_mover || !final_opponent || !slot || !sym || !out_own || !out_margin))
+        return RVZ_EINVAL;
+    if (nb == 0) return RVZ_OK;
+    const Geometry g = strided(nb, SYM_WAVES, SYM_THREADS);
+    return launch_bs(bs, k_replay_ownership<8>, k_replay_ownership<6>, g.grid, g.block,
+                     (hipStream_t)stream, capacity, final_mover, final_opponent, nb, slot, sym,
+                     out_own, out_margin);
+}
 
 extern "C" int rvz_replay_batch(int32_t bs, int32_t capacity, const uint64_t* mover,
                                 const uint64_t* opponent, const float* policy, const float* value,

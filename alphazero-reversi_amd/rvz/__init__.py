@@ -39,6 +39,12 @@ Batched core:
     records_games           a window of autoreset self-play records cut into finished games:
                             compact rows with value targets, open games held back
                             (rvz_records_games); SelfPlayRunner(carry_plies=...) keeps the window
+    records_final, replay_ownership, ownership_loss, full_ownership_loss   the auxiliary
+                            final-ownership target: the final position of each record's game
+                            (rvz_records_final), a drawn batch's +1 / -1 / 0 targets under its
+                            own symmetries (rvz_replay_ownership; ReplayBuffer(ownership=True)),
+                            and the deterministic float64 loss of an ownership head
+                            (rvz_ownership_loss); AlphaZeroNetwork(ownership_head=True)
     openings, opening_suite, opening_index   the distinct positions after d plies under the
                             engine's own rules (rvz_openings), the balanced ones among them, and
                             the pool row a seed picks (rvz_opening_index); Engine.openings starts
@@ -53,12 +59,14 @@ from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa
                      best_moves, board_apply, board_canonical, board_legal, dirichlet_noise,
                      policy_softmax, solve, solve_moves, solve_moves_wld, solve_window, solve_wld)
 from .game import Board, ReversiGame  # noqa: F401
-from .loss import full_policy_loss, policy_value_loss  # noqa: F401
+from .loss import (full_ownership_loss, full_policy_loss, ownership_loss,  # noqa: F401
+                   policy_value_loss)
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)
 from .records import (board_symmetry, merge_positions, opening_index,  # noqa: F401
-                      opening_suite, openings, records_games, replay_batch, replay_batch_weighted, replay_cdf, replay_is_weight,
+                      opening_suite, openings, records_final, records_games, replay_batch,
+                      replay_batch_weighted, replay_cdf, replay_is_weight, replay_ownership,
                       replay_priority, replay_refresh, replay_roots, replay_stale,
                       symmetry_compose, symmetry_inverse, training_rows)
 from .replay import ReplayBuffer  # noqa: F401

@@ -105,6 +105,8 @@ SIGNATURES = {
     "rvz_replay_batch": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32,
                                    C.c_int32, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P,
                                    _P, _P, _P, _P]),
+    "rvz_replay_ownership": (C.c_int, [C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, _P, _P,
+                                       _P]),
     "rvz_replay_cdf_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_replay_cdf": (C.c_int, [C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "rvz_replay_batch_weighted": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
@@ -127,6 +129,8 @@ SIGNATURES = {
     "rvz_records_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_records_games": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32,
                                     _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rvz_records_final": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32,
+                                    _P, _P, _P, _P, _P, _P, _P]),
     "rvz_openings_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_openings": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "rvz_env_openings": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_uint32]),
@@ -134,6 +138,8 @@ SIGNATURES = {
     "rvz_loss_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_policy_value_loss": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_double,
                                         C.c_double, _P, _P, _P, _P, _P, _P]),
+    "rvz_ownership_loss_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rvz_ownership_loss": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),

@@ -167,3 +167,109 @@ def full_policy_loss(logits: torch.Tensor, value: torch.Tensor, policy_targets: 
                      value_weight, board_size, rows=True)
     return _full(logits, value, policy_targets, value_targets, weights, policy_weight,
                  value_weight, board_size)
+
+
+# ------------------------------------------------------------------ the ownership loss
+OWN_LOSS = {"loss": 0, "weight_sum": 4, "agreement": 5, "malformed": 6}    # out_loss's entries
+
+
+def check_ownership_loss_args(logits, targets, weights, board_size) -> int:
+    """The shape and dtype rules of ownership_loss, checked before any device call; returns n."""
+    _lib.check_board_size(board_size)
+    nsq = board_size * board_size
+    for name, t in (("logits", logits), ("targets", targets)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise RvzError(f"ownership_loss: {name} must be a float32 tensor")
+    if logits.dim() != 2 or logits.shape[1] != nsq:
+        raise RvzError(f"ownership_loss: logits must be [n, {nsq}]")
+    n = logits.shape[0]
+    if targets.shape != (n, nsq):
+        raise RvzError(f"ownership_loss: targets must be [n, {nsq}]")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or
+                                weights.dtype != torch.float32 or weights.shape != (n,)):
+        raise RvzError("ownership_loss: weights must be None or float32 [n]")
+    if n * (nsq + 1) >= 2 ** 31:
+        raise RvzError("ownership_loss: n * (S*S + 1) does not fit int32")
+    return n
+
+
+def ownership_loss(logits: torch.Tensor, targets: torch.Tensor,
+                   weights: Optional[torch.Tensor] = None, board_size: int = 8,
+                   rows: bool = False, grads: bool = True) -> Dict[str, torch.Tensor]:
+    """rvz_ownership_loss: the weighted loss of an ownership head on a batch's final-ownership
+    targets, mean_a (tanh(o_a) - t_a)^2 per row, with its gradient, in float64 (include/rvz.h has
+    the definition). logits and targets float32 [n, S*S] (targets: replay_ownership's, every
+    entry -1, 0 or +1), weights None (every row 1) or float32 [n], device tensors. Returns a dict
+    of device tensors: "out_loss" float64 [8] and 0-d views of its entries "loss", "weight_sum",
+    "agreement" (the weighted mean over rows of the share of the owned squares whose logit has
+    the owner's sign) and "malformed" (the rows dropped with weight 0: a non-finite logit, a
+    target that is not -1, 0 or +1, a negative or non-finite weight); with rows=True "rows"
+    float64 [n, 2], each row's {L, agree}; with grads=True "grad_logits" float32 [n, S*S], the
+    derivative of "loss". The call runs on the current stream, allocates its scratch and outputs,
+    and never synchronises with the host; n = 0 launches nothing and returns zeros."""
+    n = check_ownership_loss_args(logits, targets, weights, board_size)
+    lib = _lib.load()
+    dev = logits.device
+    o = logits.detach().contiguous()
+    t = targets.detach().to(dev).contiguous()
+    w = None if weights is None else weights.detach().to(dev).contiguous()
+    f64 = {"dtype": torch.float64, "device": dev}
+    out_loss = torch.empty(8, **f64) if n else torch.zeros(8, **f64)
+    out = {"out_loss": out_loss}
+    out.update({name: out_loss[i] for name, i in OWN_LOSS.items()})
+    if rows:
+        out["rows"] = torch.empty(n, 2, **f64)
+    if grads:
+        out["grad_logits"] = torch.empty(n, logits.shape[1], dtype=torch.float32, device=dev)
+    if n:
+        size = lib.rvz_ownership_loss_scratch_size(board_size, n)
+        if size < 0:
+            raise RvzError(f"ownership_loss: no scratch for n = {n}")
+        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
+        check(lib.rvz_ownership_loss(board_size, n, _addr(o), _addr(t), _addr(w), ptr(scratch),
+                                     _addr(out_loss), _addr(out.get("rows")),
+                                     _addr(out.get("grad_logits")), _lib.stream_handle(dev)),
+              None, "rvz_ownership_loss")
+    return out
+
+
+class _OwnLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, kernel, args):
+        out = kernel(logits.detach(), *args, grads=True)
+        ctx.save_for_backward(out["grad_logits"])
+        ctx.shape = logits.shape
+        return out["loss"].to(logits.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (gl,) = ctx.saved_tensors
+        return (grad_output.to(gl.dtype) * gl).reshape(ctx.shape), None, None
+
+
+def differentiable_ownership(kernel):
+    """A function of full_ownership_loss's signature around any `kernel` of ownership_loss's
+    signature and results (tests on a host without a GPU wrap the NumPy reference)."""
+    def loss_fn(logits, targets, weights=None, board_size=8):
+        holder = {}
+
+        def call(*a, **k):
+            holder["out"] = kernel(*a, **k)
+            return holder["out"]
+        loss = _OwnLoss.apply(logits, call, (targets, weights, board_size))
+        out = holder["out"]
+        return loss, {k: out[k] for k in ("agreement", "weight_sum", "malformed")}
+    return loss_fn
+
+
+_full_own = differentiable_ownership(ownership_loss)
+
+
+def full_ownership_loss(logits: torch.Tensor, targets: torch.Tensor,
+                        weights: Optional[torch.Tensor] = None, board_size: int = 8):
+    """ownership_loss as a differentiable torch function (one rvz_ownership_loss call in the
+    forward, which also computes the gradient; the backward multiplies the saved gradient by the
+    upstream factor). Returns (loss, stats): loss a 0-d tensor of logits' dtype, differentiable
+    with respect to logits; stats the 0-d float64 device tensors "agreement", "weight_sum" and
+    "malformed". Nothing synchronises with the host."""
+    return _full_own(logits, targets, weights, board_size)

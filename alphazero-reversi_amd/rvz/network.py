@@ -37,9 +37,16 @@ class _Residual(nn.Module):
 
 
 class AlphaZeroNetwork(nn.Module):
-    """3 -> F stem, N residual blocks, 2-plane policy head (S*S+1 logits), 1-plane value head."""
+    """3 -> F stem, N residual blocks, 2-plane policy head (S*S+1 logits), 1-plane value head.
+    ownership_head=True adds a training-only auxiliary head, own_conv, a 1x1 convolution from the
+    trunk output to one logit per square (forward_aux returns it; tanh of it is the predicted
+    final ownership of the square from the mover's side). forward, the packed parameters and the
+    evaluators do not read it: self-play with and without the head is the same computation. It
+    is created last, so the other parameters' initial values do not depend on it, and with
+    the head off the state_dict keys are those of before."""
 
-    def __init__(self, board_size: int = 8, num_res_blocks: int = 5, num_filters: int = 128):
+    def __init__(self, board_size: int = 8, num_res_blocks: int = 5, num_filters: int = 128,
+                 ownership_head: bool = False):
         super().__init__()
         self.board_size = board_size
         self.num_filters = num_filters
@@ -55,6 +62,11 @@ class AlphaZeroNetwork(nn.Module):
         self.value_fc1 = nn.Linear(cells, 256)
         self.value_fc2 = nn.Linear(256, 1)
         self.reset_parameters()
+        self.ownership_head = bool(ownership_head)
+        if self.ownership_head:                     # created and initialised after the others
+            self.own_conv = nn.Conv2d(num_filters, 1, 1)
+            nn.init.kaiming_normal_(self.own_conv.weight, mode="fan_out", nonlinearity="relu")
+            nn.init.zeros_(self.own_conv.bias)
 
     def reset_parameters(self):
         """Kaiming-normal fan-out for conv/linear weights, BN affine = (1, 0) (network.py:71-78)."""
@@ -71,13 +83,26 @@ class AlphaZeroNetwork(nn.Module):
             x = blk(x)
         return x
 
-    def forward(self, x) -> Tuple[torch.Tensor, torch.Tensor]:
-        h = self.trunk(x)
+    def _heads(self, h):
         n = h.shape[0]
         pol = F.relu(self.policy_bn(self.policy_conv(h))).reshape(n, -1)
         val = F.relu(self.value_bn(self.value_conv(h))).reshape(n, -1)
         val = torch.tanh(self.value_fc2(F.relu(self.value_fc1(val))))
         return self.policy_fc(pol), val.squeeze(1)
+
+    def forward(self, x, aux: bool = False):
+        """(policy logits, value); with aux=True forward_aux's three outputs (the form a
+        DistributedDataParallel wrapper, which only forwards `forward`, is called in)."""
+        h = self.trunk(x)
+        if not aux:
+            return self._heads(h)
+        if not self.ownership_head:
+            raise ValueError("forward_aux needs AlphaZeroNetwork(ownership_head=True)")
+        return (*self._heads(h), self.own_conv(h).reshape(h.shape[0], -1))
+
+    def forward_aux(self, x) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(policy logits, value, ownership logits [n, S*S]); needs ownership_head=True."""
+        return self.forward(x, aux=True)
 
     def predict(self, board_state, valid_moves=None):
         """network.py:136-158: adds the batch dim for a single [3,S,S] state."""

@@ -54,8 +54,20 @@ class SelfPlayTrainer:
                  replay_sampling: str = "uniform", replay_recency_decay: float = 1.0,
                  replay_priority_alpha: float = 0.6, replay_priority_beta=0.4,
                  continuous_plies: Optional[int] = None, openings=None,
-                 reanalyse_rows: int = 0, reanalyse_age: int = 0):
-        """reanalyse_rows: 0 (off: the code and the keys of before) or N: replay reanalysis
+                 reanalyse_rows: int = 0, reanalyse_age: int = 0, ownership_coef: float = 0.0):
+        """ownership_coef: 0 (off: the code and the keys of before) or c > 0: the auxiliary
+        final-ownership target. The model has the ownership head
+        (AlphaZeroNetwork(ownership_head=True); ValueError otherwise, as DDPTrainer's); every
+        compact row carries the final position of its game from its mover's side
+        (records_to_training / games_to_training(ownership=True): rvz.records_final), the replay
+        buffer holds it (ReplayBuffer(ownership=True)) and every training step adds c times the
+        head's loss on the drawn rows' ownership targets (DDPTrainer(ownership_coef=c)); the loss
+        dict gains "train/ownership_loss" and "train/ownership_agreement" and run_iteration
+        "ownership_dropped". Self-play does not read the head. It needs replay_iterations >= 1
+        (the targets live in the ring), and raises ValueError with merge_positions (a merged row
+        has no single final position) or adjudicate_empties > 0 (the final position is never
+        played), under the lockstep path and continuous_plies alike.
+        reanalyse_rows: 0 (off: the code and the keys of before) or N: replay reanalysis
         (MuZero's Reanalyse in this loop; ReplayBuffer(stamps=True).reanalyse, the
         rvz_replay_stale / rvz_replay_roots / rvz_replay_refresh HIP kernels). After iteration t's
         weight update, up to N of the stalest rows of the replay buffer whose policy target comes
@@ -195,6 +207,21 @@ class SelfPlayTrainer:
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
         on 6x6): 2^20 slots = 608 MB, 2^12 = 2.4 MB."""
+        if isinstance(ownership_coef, bool) or not isinstance(ownership_coef, numbers.Real) or \
+                not 0.0 <= float(ownership_coef) < float("inf"):
+            raise ValueError(f"ownership_coef must be a finite number >= 0, not "
+                             f"{ownership_coef!r}")
+        self.ownership_coef = float(ownership_coef)
+        if self.ownership_coef > 0.0:
+            if not replay_iterations or replay_iterations < 1:
+                raise ValueError("ownership_coef > 0 needs replay_iterations >= 1: the ownership "
+                                 "targets are held by the replay buffer")
+            if merge_positions:
+                raise ValueError("ownership_coef > 0 keeps one final position per row: "
+                                 "merge_positions must be False")
+            if adjudicate_empties:
+                raise ValueError("ownership_coef > 0 needs every game played to its end: "
+                                 "adjudicate_empties must be 0")
         for name, x in (("reanalyse_rows", reanalyse_rows), ("reanalyse_age", reanalyse_age)):
             if isinstance(x, bool) or not isinstance(x, numbers.Integral) or x < 0:
                 raise ValueError(f"{name} must be an int >= 0, not {x!r}")
@@ -319,7 +346,8 @@ class SelfPlayTrainer:
                                   gradient_clip=gradient_clip, batch_size=train_batch,
                                   lr_milestones=lr_milestones, lr_gamma=lr_gamma,
                                   policy_target=policy_target,
-                                  count_weights=bool(count_weights))
+                                  count_weights=bool(count_weights),
+                                  ownership_coef=self.ownership_coef)
         # the h2 kernels when they cover the net, else the module itself on the GPU
         # (ModuleEvaluator: pull-style, eager plies; it reads the live module, so refresh() only
         # drops the memo)
@@ -376,7 +404,9 @@ class SelfPlayTrainer:
                                           ({"weighted": True,
                                             "recency_decay": self.replay_recency_decay}
                                            if weighted else {})),
-                                       **({"stamps": True} if self.reanalyse_rows else {}))
+                                       **({"stamps": True} if self.reanalyse_rows else {}),
+                                       **({"ownership": True} if self.ownership_coef > 0.0
+                                          else {}))
         if self.reanalyse_rows:
             # the re-search's own engine: the plain search, whatever self-play's engine has set
             self.reanalyse_eng = Engine(games, num_simulations, batch_size, c_puct, board_size=bs,
@@ -398,7 +428,8 @@ class SelfPlayTrainer:
         return {"merge_positions": True} if self.merge_positions else {}
 
     def _compact_args(self) -> dict:
-        return {"compact": True} if self.replay_iterations else {}
+        own = {"ownership": True} if self.ownership_coef > 0.0 else {}
+        return {"compact": True, **own} if self.replay_iterations else {}
 
     def generate(self) -> Dict[str, torch.Tensor]:
         """One iteration's self-play: every game of this rank from the start to its end.
@@ -443,7 +474,11 @@ class SelfPlayTrainer:
         out = games_to_training(rows, self.eng.board_size, exact_endgame=self.exact_endgame,
                                 exact_node_limit=self.exact_node_limit,
                                 exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                **self._merge_args(), compact=True)
+                                **self._merge_args(), compact=True,
+                                **({"ownership": True,
+                                    "window": (run.rec_black, run.rec_white, run.rec_side,
+                                               run.rec_idx)}
+                                   if self.ownership_coef > 0.0 else {}))
         run.roll()
         out["records_stats"] = rows["stats"]
         return out
@@ -487,8 +522,10 @@ class SelfPlayTrainer:
         rows its running maximum priority)."""
         counts = ({"weight": data["position_counts"].to(torch.float32)}
                   if self.replay_sampling == "counts" else {})
+        own = ({"final_mover": data["final_mover"], "final_opponent": data["final_opponent"]}
+               if "final_mover" in data else {})       # ownership_coef > 0
         self.buffer.append(data["mover"], data["opponent"], data["policy_targets"],
-                           data["value_targets"], self.iteration, **counts)
+                           data["value_targets"], self.iteration, **counts, **own)
 
     def train(self, data: Dict[str, torch.Tensor]) -> Dict[str, float]:
         """_train_epoch over this iteration's data (each rank walks its own games; DDP averages
@@ -583,6 +620,8 @@ class SelfPlayTrainer:
                     "replay_rows": len(self.buffer) if self.buffer is not None else 0,
                     "replay_iterations_held": (len(self.buffer.rows_by_iteration())
                                                if self.buffer is not None else 0)})
+        if self.ownership_coef > 0.0:
+            out["ownership_dropped"] = int(data["ownership_dropped"])
         if self.replay_sampling == "priority":
             out["replay_priority_max"] = self.buffer.max_priority()
         if self.continuous_plies:

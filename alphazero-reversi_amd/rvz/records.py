@@ -414,6 +414,112 @@ def records_games(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: to
     return out
 
 
+# ------------------------------------------------------------------ final-ownership targets
+def check_final_args(rec_black, rec_white, rec_side, rec_idx, src, count, board_size,
+                     who: str = "records_final"):
+    """The argument rules of records_final, checked before any device call (the CPU tests' NumPy
+    restatement calls it too); returns (plies, n_games, n)."""
+    check_board_size(board_size, who)
+    npol = board_size * board_size + 1
+    if not all(isinstance(t, torch.Tensor) for t in (rec_black, rec_white, rec_side, rec_idx,
+                                                     src)):
+        raise RvzError(f"{who}: the four record arrays and src are tensors")
+    if rec_idx.dim() != 2 or any(t.shape != rec_idx.shape for t in (rec_black, rec_white,
+                                                                     rec_side)):
+        raise RvzError(f"{who}: rec_black, rec_white, rec_side and rec_idx are [plies, n_games]")
+    P, G = rec_idx.shape
+    _bitboards(who, rec_black.reshape(-1), rec_white.reshape(-1), "rec_black and rec_white",
+               "record")
+    _given(who, P * G, "record", optional=False, rec_side=rec_side.reshape(-1),
+           rec_idx=rec_idx.reshape(-1))
+    if P < 1 or G < 1:
+        raise RvzError(f"{who}: the window holds at least one ply and one slot")
+    _fits_int32(who, P * G, npol, "plies * n_games")
+    if src.dim() != 1:
+        raise RvzError(f"{who}: src holds one integer per row")
+    _given(who, src.numel(), "row", optional=False, src=src)
+    if src.numel() >= 2 ** 31:
+        raise RvzError(f"{who}: n must be below 2^31")
+    if count is not None and (not isinstance(count, torch.Tensor) or count.numel() != 1 or
+                              count.dtype != torch.int32):
+        raise RvzError(f"{who}: count is None or one int32 tensor (records_games' m)")
+    return P, G, src.numel()
+
+
+def records_final(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
+                  rec_idx: torch.Tensor, src: torch.Tensor, count: Optional[torch.Tensor] = None,
+                  board_size: int = 8):
+    """rvz_records_final: the final position of the game each of n records belongs to, from the
+    record's mover's side (include/rvz.h has the walk): the ownership target of a training row.
+    rec_black / rec_white int64 [plies, n_games] (bit patterns), rec_side / rec_idx
+    [plies, n_games] integers: records_games' window; src [n] integers, each ply * n_games + slot
+    (records_games' "src"); count None or one int32 device tensor (records_games' "m"): only the
+    rows below min(n, count) are handled, read on the device. Returns a dict: "final_mover" /
+    "final_opponent" int64 [n] and "ok" int32 [n] (zeros beyond the bound; ok = 0 and two empty
+    boards for a row whose game does not end inside the window, or whose walk meets a malformed
+    record, a refused move or a broken chain), "stats" int64 [4]: rows handled, rows with ok = 1,
+    rows whose game is still open at the window's end, every other row. Asynchronous on the
+    current stream; nothing synchronises. n = 0 launches nothing."""
+    P, G, n = check_final_args(rec_black, rec_white, rec_side, rec_idx, src, count, board_size)
+    lib = _lib.load()
+    dev = rec_black.device
+    b, w = rec_black.contiguous(), rec_white.to(dev).contiguous()
+    sd, ix, sr = _i32(rec_side, dev), _i32(rec_idx, dev), _i32(src, dev)
+    ct = None if count is None else count.to(dev).reshape(1).contiguous()
+    out = {"final_mover": torch.zeros(n, dtype=torch.int64, device=dev),
+           "final_opponent": torch.zeros(n, dtype=torch.int64, device=dev),
+           "ok": torch.zeros(n, dtype=torch.int32, device=dev),
+           "stats": torch.zeros(4, dtype=torch.int64, device=dev)}
+    if n:
+        check(lib.rvz_records_final(board_size, P, G, _addr(b), _addr(w), _addr(sd), _addr(ix), n,
+                                    _addr(sr), _addr(ct), _addr(out["final_mover"]),
+                                    _addr(out["final_opponent"]), _addr(out["ok"]),
+                                    _addr(out["stats"]), _lib.stream_handle(dev)), None,
+              "rvz_records_final")
+    return out
+
+
+def check_ownership_args(final_mover, final_opponent, slot, sym, board_size,
+                         who: str = "replay_ownership") -> int:
+    """The argument rules of replay_ownership, checked before any device call; returns nb."""
+    check_board_size(board_size, who)
+    if not all(isinstance(t, torch.Tensor) for t in (final_mover, final_opponent, slot, sym)):
+        raise RvzError(f"{who}: final_mover, final_opponent, slot and sym are tensors")
+    cap = _bitboards(who, final_mover, final_opponent, "final_mover and final_opponent", "slot")
+    if not 1 <= cap < 2 ** 31:
+        raise RvzError(f"{who}: the ring holds between 1 and 2^31 - 1 slots")
+    if slot.dim() != 1:
+        raise RvzError(f"{who}: slot holds one integer per output row")
+    nb = slot.numel()
+    _given(who, nb, "output row", optional=False, slot=slot, sym=sym)
+    _fits_int32(who, nb, board_size * board_size + 1, "nb")
+    return nb
+
+
+def replay_ownership(final_mover: torch.Tensor, final_opponent: torch.Tensor, slot: torch.Tensor,
+                     sym: torch.Tensor, board_size: int = 8):
+    """rvz_replay_ownership: the ownership targets of a drawn batch (include/rvz.h has the
+    definition). final_mover / final_opponent int64 [capacity] (bit patterns): the ring's final
+    positions; slot / sym [nb] integers: replay_batch's fourth and fifth outputs; device tensors.
+    Returns (ownership float32 [nb, S*S]: +1 where the row's mover holds the square at the end of
+    its game, -1 where the opponent does, 0 where it stays empty, under the row's own symmetry;
+    margin float32 [nb]: the final disc margin, the sum of the row). A row with a slot outside
+    [0, capacity), a sym outside [0, 8) or bitboards that overlap or leave the board is all
+    zero. Asynchronous on the current stream; nothing synchronises."""
+    nb = check_ownership_args(final_mover, final_opponent, slot, sym, board_size)
+    lib = _lib.load()
+    dev = final_mover.device
+    fm, fo = final_mover.contiguous(), final_opponent.to(dev).contiguous()
+    sl, sy = _i32(slot, dev), _i32(sym, dev)
+    own = torch.empty(nb, board_size * board_size, dtype=torch.float32, device=dev)
+    margin = torch.empty(nb, dtype=torch.float32, device=dev)
+    if nb:
+        check(lib.rvz_replay_ownership(board_size, fm.numel(), _addr(fm), _addr(fo), nb, _addr(sl),
+                                       _addr(sy), _addr(own), _addr(margin),
+                                       _lib.stream_handle(dev)), None, "rvz_replay_ownership")
+    return own, margin
+
+
 # ------------------------------------------------------------------ opening pools
 # The default max_rows of openings(): the bound is the largest level's candidate count, which
 # grows with the level, so ply 8's. By the level rule on the CPU oracle (tests/openings_ref.py)

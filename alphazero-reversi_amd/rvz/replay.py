@@ -34,18 +34,20 @@ import torch
 from . import _lib
 from ._lib import RvzError
 from .records import (check_priority_args, replay_batch, replay_batch_weighted, replay_cdf,
-                      replay_is_weight, replay_priority, replay_refresh, replay_roots,
-                      replay_stale)
+                      replay_is_weight, replay_ownership, replay_priority, replay_refresh,
+                      replay_roots, replay_stale)
 
 
 class ReplayBuffer:
+    ownership = False       # an instance attribute only with ownership=True
+
     def __init__(self, capacity: int, board_size: int = 8, device=None,
                  window_iterations: int = 0, batcher=None, weighted: bool = False,
                  recency_decay: float = 1.0, weighted_batcher=None, cdf_builder=None,
                  prioritized: bool = False, priority_alpha: float = 0.6,
                  priority_floor: float = 2.0 ** -8, priority_cap: float = 2.0 ** 8,
                  subtract_entropy: bool = True, priority_updater=None, is_weighter=None,
-                 stamps: bool = False):
+                 stamps: bool = False, ownership: bool = False, ownership_batcher=None):
         """capacity: the ring's rows. window_iterations = K > 0: an append of iteration t also
         drops every row of an iteration before t - K + 1 (0: rows leave only when overwritten).
         batcher(mover, opponent, policy, value, start, live, nb, seed, step, random_sym, idx, sym,
@@ -88,7 +90,17 @@ class ReplayBuffer:
         stamps=True: the ring also holds `stamp` int32 [capacity], the iteration whose net
         produced each row's policy target: append's `stamp` (default: its iteration), and what
         reanalyse() selects by and rewrites. Without it the buffer allocates nothing more and
-        behaves exactly as before."""
+        behaves exactly as before.
+        ownership=True: the ring also holds `final_mover` and `final_opponent` int64 [capacity],
+        the final position of each row's game from the row's mover's side (16 B a row; append's
+        arguments of those names, rvz.records_final's outputs), and sample returns two more
+        outputs at its end: ownership float32 [nb, S*S] (+1 / -1 / 0: who holds each square at the
+        end of the game, under the drawn row's own symmetry) and margin float32 [nb] (the final
+        disc margin), under the uniform, weighted and prioritized draws alike.
+        ownership_batcher(final_mover, final_opponent, slot, sym, board_size) -> (ownership,
+        margin): default rvz.replay_ownership (the rvz_replay_ownership HIP kernel), called on
+        the draw's own slot and sym. reanalyse leaves the two columns alone. Without it the buffer
+        allocates nothing more and behaves exactly as before."""
         for name, x in (("capacity", capacity), ("window_iterations", window_iterations)):
             if isinstance(x, bool) or not isinstance(x, numbers.Integral):
                 raise ValueError(f"ReplayBuffer: {name} is an int, not {x!r}")
@@ -129,6 +141,15 @@ class ReplayBuffer:
         self.stamps = bool(stamps)
         if self.stamps:
             self.stamp = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
+        if ownership_batcher is not None and not ownership:
+            raise ValueError("ReplayBuffer: ownership_batcher needs ownership=True")
+        if ownership:
+            self.ownership = True
+            self.ownership_batcher = (replay_ownership if ownership_batcher is None
+                                      else ownership_batcher)
+            self.final_mover = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
+            self.final_opponent = torch.zeros(self.capacity, dtype=torch.int64,
+                                              device=self.device)
         if self.weighted:
             self.recency_decay = float(recency_decay)
             self.weighted_batcher = (replay_batch_weighted if weighted_batcher is None
@@ -174,14 +195,17 @@ class ReplayBuffer:
 
     def append(self, mover: torch.Tensor, opponent: torch.Tensor, policy: torch.Tensor,
                value: torch.Tensor, iteration: int,
-               weight: Optional[torch.Tensor] = None, stamp: Optional[int] = None) -> None:
+               weight: Optional[torch.Tensor] = None, stamp: Optional[int] = None,
+               final_mover: Optional[torch.Tensor] = None,
+               final_opponent: Optional[torch.Tensor] = None) -> None:
         """n <= capacity rows of `iteration` at the head of the ring (at most two slice copies per
         tensor), over the oldest rows once the ring is full. mover / opponent int64 [n], policy
         float32 [n, S*S+1], value float32 [n] or [n, 1]. Iterations are appended in
         non-decreasing order. weight (weighted=True only): float32 [n], the rows' sampling
         weights; None: 1.0 each (prioritized=True: the running maximum priority each). stamp
         (stamps=True only): the iteration whose net produced the rows' policy targets, an int in
-        [0, 2^31); None: `iteration`."""
+        [0, 2^31); None: `iteration`. final_mover / final_opponent (ownership=True only, and
+        required then): int64 [n], the rows' final positions."""
         if isinstance(iteration, bool) or not isinstance(iteration, numbers.Integral):
             raise ValueError(f"ReplayBuffer.append: iteration is an int, not {iteration!r}")
         n = mover.numel()
@@ -199,6 +223,14 @@ class ReplayBuffer:
                 raise ValueError("ReplayBuffer.append: weight needs ReplayBuffer(weighted=True)")
             if weight.shape != (n,) or weight.dtype != torch.float32:
                 raise ValueError("ReplayBuffer.append: weight is float32 [n]")
+        if (final_mover is not None or final_opponent is not None) and not self.ownership:
+            raise ValueError("ReplayBuffer.append: final_mover and final_opponent need "
+                             "ReplayBuffer(ownership=True)")
+        if self.ownership:
+            for t in (final_mover, final_opponent):
+                if not isinstance(t, torch.Tensor) or t.shape != (n,) or t.dtype != torch.int64:
+                    raise ValueError("ReplayBuffer.append: a ReplayBuffer(ownership=True) takes "
+                                     "final_mover and final_opponent, int64 [n]")
         if stamp is not None and not self.stamps:
             raise ValueError("ReplayBuffer.append: stamp needs ReplayBuffer(stamps=True)")
         if self.stamps:
@@ -217,6 +249,8 @@ class ReplayBuffer:
             first = min(n, self.capacity - head)
             fields = [(self.mover, mover), (self.opponent, opponent), (self.policy, policy),
                       (self.value, value.reshape(n))]
+            if self.ownership:
+                fields += [(self.final_mover, final_mover), (self.final_opponent, final_opponent)]
             if self.weighted:
                 if self._ledger and iteration > self._ledger[-1][0] and self.recency_decay != 1.0:
                     # the held rows age by the iterations that passed (slots that hold no row too:
@@ -264,7 +298,17 @@ class ReplayBuffer:
         symmetries are the same draws). word [nb] int64 (uint64 bit patterns): the uniform 64-bit
         words to draw with in place of the generator's. with_prob=True: a sixth output, prob
         float32 [nb], each taken row's probability. With every weight 0 or invalid all drawn rows
-        are zero rows with slot -1 and sym -1."""
+        are zero rows with slot -1 and sym -1.
+        ownership=True: two more outputs after those, ownership float32 [nb, S*S] and margin
+        float32 [nb], the drawn rows' ownership targets under their own symmetries (zero for a
+        zero row)."""
+        out = self._draw(nb, seed, step, symmetries, idx, sym, word, with_prob)
+        if self.ownership:
+            out = (*out, *self.ownership_batcher(self.final_mover, self.final_opponent, out[3],
+                                                 out[4], self.board_size))
+        return out
+
+    def _draw(self, nb, seed, step, symmetries, idx, sym, word, with_prob):
         if not self._live:
             raise ValueError("ReplayBuffer.sample: the buffer is empty")
         if self.weighted:

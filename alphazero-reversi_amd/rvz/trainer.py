@@ -17,6 +17,7 @@ optimizer step. Differences by design:
 """
 from __future__ import annotations
 
+import numbers
 from typing import Dict, Optional
 
 import torch
@@ -26,8 +27,8 @@ import torch.nn.functional as F
 
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
                      solve_moves, solve_moves_wld, solve_wld)
-from .loss import full_policy_loss
-from .records import merge_positions as _merge_positions, training_rows
+from .loss import full_ownership_loss, full_policy_loss
+from .records import merge_positions as _merge_positions, records_final, training_rows
 
 
 def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_side: torch.Tensor,
@@ -37,7 +38,8 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
                         exact_wld: bool = False, exact_policy: int = 0,
                         moves_solver=None, symmetries: Optional[str] = None,
                         symmetry_seed: int = 0, augment=None, merge_positions: bool = False,
-                        merger=None, compact: bool = False) -> Dict[str, torch.Tensor]:
+                        merger=None, compact: bool = False, ownership: bool = False,
+                        finaler=None) -> Dict[str, torch.Tensor]:
     """Self-play records [plies, G] -> training arrays in the reference's layout and order.
 
     states f32 [n,3,S,S] (get_canonical_state of the position before each move), policy_targets
@@ -108,16 +110,41 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     alike (with merging, the bitboards are those of each group's first record). compact=True
     together with `symmetries` raises ValueError: a compact row's symmetry is drawn every time it
     is sampled.
+    ownership = True (the default False is off: the keys and bytes of before; needs compact=True):
+    two more row keys, "final_mover" and "final_opponent" int64 [n]: the final position of each
+    row's game from the row's mover's side (rvz.records_final, the engine's own make_move down the
+    records), what a rvz.ReplayBuffer(ownership=True) holds as the row's ownership target. A row
+    whose walk does not reach the end of its game (ok = 0: the game is still open at the last
+    ply, or a record does not follow from the one before) is dropped from every key, before the
+    exact targets are computed, and counted in "ownership_dropped", a 0-d int64 device tensor;
+    reading the kept rows is this option's one host synchronisation. ValueError together with
+    merge_positions (a merged row would need the mean ownership of its records, which two
+    bitboards cannot hold) or with compact=False.
+    finaler(rec_black, rec_white, rec_side, rec_idx, src, count, board_size) -> dict with
+    "final_mover", "final_opponent", "ok": default rvz.records_final (the rvz_records_final HIP
+    kernel).
     """
     if symmetries not in (None, "all", "random"):
         raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
     if compact and symmetries is not None:
         raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
                          f"symmetries must be None, not {symmetries!r}")
+    _check_ownership(ownership, merge_positions, compact)
     if canonical is None:
         canonical = board_canonical
     P, G = rec_idx.shape
     live = (rec_idx >= 0).t().reshape(-1)                    # game-major order
+    fin = None
+    if ownership:
+        # record (p, g) is window index p * G + g; the kept rows are game-major
+        src = torch.arange(P * G, device=rec_idx.device).reshape(P, G).t().reshape(-1)[live]
+        fin = (records_final if finaler is None else finaler)(
+            rec_black, rec_white, rec_side, rec_idx, src.to(torch.int32), None, board_size)
+        ok = fin["ok"].to(live.device) != 0
+        live = live.clone()
+        live[live.nonzero().reshape(-1)[~ok]] = False
+        fin = {"final_mover": fin["final_mover"][ok], "final_opponent": fin["final_opponent"][ok],
+               "ownership_dropped": (~ok).sum()}
     black = rec_black.t().reshape(-1)[live].contiguous()
     white = rec_white.t().reshape(-1)[live].contiguous()
     side = rec_side.t().reshape(-1)[live]
@@ -131,10 +158,22 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     v = torch.where(winner == side.to(torch.int32), 1.0, -1.0)
     v = torch.where(winner == 0, torch.zeros_like(v), v)
     v = torch.where(over != 0, v, -torch.ones_like(v))      # winner None -> -1 (self_play.py:121-126)
-    return _training_tail(black, white, st, states, policy, v, board_size, canonical,
-                          exact_endgame, solver, exact_node_limit, exact_wld, exact_policy,
-                          moves_solver, symmetries, symmetry_seed, augment, merge_positions,
-                          merger, compact)
+    out = _training_tail(black, white, st, states, policy, v, board_size, canonical,
+                         exact_endgame, solver, exact_node_limit, exact_wld, exact_policy,
+                         moves_solver, symmetries, symmetry_seed, augment, merge_positions,
+                         merger, compact)
+    if fin is not None:
+        out.update(fin)
+    return out
+
+
+def _check_ownership(ownership, merge_positions, compact) -> None:
+    if ownership and merge_positions:
+        raise ValueError("ownership=True keeps one final position per row: merge_positions must "
+                         "be False (a merged row would need the mean ownership of its records)")
+    if ownership and not compact:
+        raise ValueError("ownership=True adds the final bitboards to the compact rows a replay "
+                         "buffer holds: compact must be True")
 
 
 def _training_tail(black, white, st, states, policy, v, board_size, canonical, exact_endgame,
@@ -217,7 +256,8 @@ def games_to_training(rows: Dict[str, torch.Tensor], board_size: int = 8, canoni
                       exact_wld: bool = False, exact_policy: int = 0, moves_solver=None,
                       symmetries: Optional[str] = None, symmetry_seed: int = 0, augment=None,
                       merge_positions: bool = False, merger=None,
-                      compact: bool = True) -> Dict[str, torch.Tensor]:
+                      compact: bool = True, ownership: bool = False, window=None,
+                      finaler=None) -> Dict[str, torch.Tensor]:
     """rvz.records_games' rows -> training arrays: records_to_training for continuous self-play.
 
     rows: records_games' dict; its first m rows ("m": an int, or the 0-d device tensor, whose
@@ -230,25 +270,45 @@ def games_to_training(rows: Dict[str, torch.Tensor], board_size: int = 8, canoni
     symmetry_seed) and compact, which defaults to True here: "mover" and "opponent" in place of
     "states", the rows a rvz.ReplayBuffer holds (compact=False calls `canonical` for the planes).
     Every target those options compute is relative to the mover, so they compose with the value
-    targets rows carries."""
+    targets rows carries.
+    ownership = True: records_to_training's option of that name, with `window` = (rec_black,
+    rec_white, rec_side, rec_idx), the window records_games cut (rows["src"] indexes it):
+    "final_mover" / "final_opponent" per row and "ownership_dropped". Every emitted row belongs
+    to a game that ended inside the window, so nothing is dropped unless the window changed."""
     if symmetries not in (None, "all", "random"):
         raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
     if compact and symmetries is not None:
         raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
                          f"symmetries must be None, not {symmetries!r}")
+    _check_ownership(ownership, merge_positions, compact)
+    if ownership and (window is None or len(window) != 4):
+        raise ValueError("ownership=True needs window=(rec_black, rec_white, rec_side, rec_idx), "
+                         "the records rows was cut from")
     if canonical is None:
         canonical = board_canonical
     m = int(rows["m"])
+    fin = None
+    if ownership:
+        fin = (records_final if finaler is None else finaler)(*window, rows["src"][:m], None,
+                                                              board_size)
+        ok = fin["ok"] != 0
+        fin = {"final_mover": fin["final_mover"][ok], "final_opponent": fin["final_opponent"][ok],
+               "ownership_dropped": (~ok).sum()}
+        rows = {k: rows[k][:m][ok] for k in ("mover", "opponent", "policy", "value")}
+        m = rows["mover"].numel()
     black, white = rows["mover"][:m].contiguous(), rows["opponent"][:m].contiguous()
     side = torch.ones(m, dtype=torch.int32, device=black.device)
     st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
                       torch.zeros_like(side)], dim=1).contiguous()
     states = (canonical(black, white, st, board_size)
               if symmetries is None and not merge_positions and not compact else None)
-    return _training_tail(black, white, st, states, rows["policy"][:m],
-                          rows["value"][:m].reshape(-1), board_size, canonical, exact_endgame,
-                          solver, exact_node_limit, exact_wld, exact_policy, moves_solver,
-                          symmetries, symmetry_seed, augment, merge_positions, merger, compact)
+    out = _training_tail(black, white, st, states, rows["policy"][:m],
+                         rows["value"][:m].reshape(-1), board_size, canonical, exact_endgame,
+                         solver, exact_node_limit, exact_wld, exact_policy, moves_solver,
+                         symmetries, symmetry_seed, augment, merge_positions, merger, compact)
+    if fin is not None:
+        out.update(fin)
+    return out
 
 
 def adjudicate(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int,
@@ -298,7 +358,8 @@ class DDPTrainer:
                  gradient_clip: float = 1.0, policy_loss_weight: float = 1.0,
                  value_loss_weight: float = 1.0, batch_size: int = 64, bucket_cap_mb: int = 25,
                  lr_milestones=(), lr_gamma: float = 0.1, policy_target: str = "argmax",
-                 count_weights: bool = False, loss_fn=None):
+                 count_weights: bool = False, loss_fn=None, ownership_coef: float = 0.0,
+                 ownership_loss_fn=None):
         """Defaults = the reference's TrainingConfig (config.py:46-60): AdamW(lr 1e-3, weight decay
         1e-4), clip 1.0, loss weights 1, batch 64, MultiStepLR(milestones [], gamma 0.1)
         (pipeline.py:91-105), stepped once per iteration (scheduler_step, pipeline.py:131).
@@ -313,7 +374,29 @@ class DDPTrainer:
         the records a merged row stands for (records_to_training(merge_positions=True)).
         loss_fn(logits, value, policy_targets, value_targets, weights, policy_weight,
         value_weight, board_size) -> (loss, policy_loss, value_loss, stats): default
-        rvz.full_policy_loss (tests on a host without a GPU pass the NumPy reference)."""
+        rvz.full_policy_loss (tests on a host without a GPU pass the NumPy reference).
+        ownership_coef = c > 0 (0, the default, is off: the steps and the loss dict of before):
+        train_replay, on a ReplayBuffer(ownership=True), adds c * L_own to every step's loss,
+        L_own the ownership head's loss on the drawn rows' final-ownership targets
+        (rvz.full_ownership_loss; the rvz_ownership_loss HIP kernels, float64, deterministic),
+        with the rows' weights of the policy term. The loss dict then gains
+        "train/ownership_loss" and "train/ownership_agreement". c > 0 exactly when the model has
+        the head (AlphaZeroNetwork(ownership_head=True)), ValueError otherwise: a head that no
+        loss reads leaves DistributedDataParallel's reducer waiting for its gradient.
+        ownership_loss_fn(logits, targets, weights, board_size) -> (loss, stats): default
+        rvz.full_ownership_loss."""
+        if isinstance(ownership_coef, bool) or not isinstance(ownership_coef, numbers.Real) or \
+                not 0.0 <= float(ownership_coef) < float("inf"):
+            raise ValueError(f"ownership_coef must be a finite number >= 0, not "
+                             f"{ownership_coef!r}")
+        if (float(ownership_coef) > 0.0) != bool(getattr(model, "ownership_head", False)):
+            raise ValueError("ownership_coef > 0 goes with a model that has the ownership head "
+                             "(AlphaZeroNetwork(ownership_head=True)) and 0 with one that has "
+                             "none: an unused head breaks DistributedDataParallel's reducer")
+        self.ownership_coef = float(ownership_coef)
+        self.ownership_loss_fn = (full_ownership_loss if ownership_loss_fn is None
+                                  else ownership_loss_fn)
+        self.last_ownership = None  # the (loss, stats) of the last step's ownership term
         if policy_target not in ("argmax", "full"):
             raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
         if count_weights and policy_target != "full":
@@ -356,16 +439,26 @@ class DDPTrainer:
     def rank_world(self):
         return (dist.get_rank(), dist.get_world_size()) if self.distributed else (0, 1)
 
-    def train_step(self, states, policy_targets, value_targets, weights=None, rows=False):
+    def train_step(self, states, policy_targets, value_targets, weights=None, rows=False,
+                   ownership=None):
         """One optimizer step (pipeline.py:297-340); returns (loss, policy_loss, value_loss).
         weights (policy_target="full" only): float32 [n], each row's weight in the batch's mean;
         None weights every row 1. In "full" mode last_stats holds the step's loss_fn stats; with
-        rows=True ("full" only) loss_fn is asked for its per-row losses, last_stats["rows"]."""
+        rows=True ("full" only) loss_fn is asked for its per-row losses, last_stats["rows"].
+        ownership (ownership_coef > 0 only, and required then): float32 [n, S*S], the rows'
+        final-ownership targets; ownership_coef times the head's loss on them, under the same
+        weights, is added to the loss, and last_ownership holds that term's (loss, stats)."""
         if (weights is not None or rows) and self.policy_target != "full":
             raise ValueError("train_step: weights and rows need policy_target='full'")
+        if (ownership is not None) != (self.ownership_coef > 0.0):
+            raise ValueError("train_step: ownership targets go with ownership_coef > 0 (they "
+                             "come from train_replay on a ReplayBuffer(ownership=True))")
         self.net.train()
         self.opt.zero_grad()
-        logits, value = self.net(states)
+        if ownership is not None:
+            logits, value, own_logits = self.net(states, aux=True)
+        else:
+            logits, value = self.net(states)
         if self.policy_target == "full":
             board = int(getattr(self.model, "board_size", 8))
             loss, policy_loss, value_loss, self.last_stats = self.loss_fn(
@@ -377,6 +470,11 @@ class DDPTrainer:
                                           policy_targets.argmax(dim=1))
             value_loss = F.mse_loss(value.squeeze(-1), value_targets.reshape(-1))
             loss = self.wp * policy_loss + self.wv * value_loss
+        if ownership is not None:
+            board = int(getattr(self.model, "board_size", 8))
+            own_loss, own_stats = self.ownership_loss_fn(own_logits, ownership, weights, board)
+            self.last_ownership = (own_loss.detach(), own_stats)
+            loss = loss + self.ownership_coef * own_loss
         loss.backward()                      # DDP: bucketed RCCL all-reduce during backward
         if self.clip > 0:
             torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
@@ -391,7 +489,13 @@ class DDPTrainer:
             st = self.last_stats
             vals += [losses[1].double() - st["target_entropy"].double(),
                      st["agreement"].double()]
+        if self.ownership_coef > 0.0:
+            own_loss, own_stats = self.last_ownership
+            vals += [own_loss.double(), own_stats["agreement"].double().to(own_loss.device)]
         return torch.stack(vals)
+
+    def _n_totals(self) -> int:
+        return (5 if self.policy_target == "full" else 3) + 2 * (self.ownership_coef > 0.0)
 
     def _loss_dict(self, tot, steps):
         out = {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
@@ -400,6 +504,10 @@ class DDPTrainer:
         if self.policy_target == "full":
             out["train/policy_kl"] = float(tot[3])
             out["train/policy_agreement"] = float(tot[4])
+        if self.ownership_coef > 0.0:
+            at = 5 if self.policy_target == "full" else 3
+            out["train/ownership_loss"] = float(tot[at])
+            out["train/ownership_agreement"] = float(tot[at + 1])
         return out
 
     def train_epoch(self, data: Dict[str, torch.Tensor], seed: int = 0,
@@ -417,6 +525,9 @@ class DDPTrainer:
         drop_last) does; across ranks every step is a full world x batch_size batch.
         With count_weights every row is weighted by data["position_counts"] (ValueError when the
         key is missing)."""
+        if self.ownership_coef > 0.0:
+            raise ValueError("train_epoch: ownership_coef > 0 trains through train_replay (the "
+                             "ownership targets are a ReplayBuffer(ownership=True)'s)")
         if self.count_weights and "position_counts" not in data:
             raise ValueError("train_epoch: count_weights=True needs data['position_counts'] "
                              "(records_to_training(merge_positions=True))")
@@ -442,8 +553,7 @@ class DDPTrainer:
                              device=self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             steps = int(t.item())
-        tot = torch.zeros(5 if self.policy_target == "full" else 3, dtype=torch.float64,
-                          device=self.device)
+        tot = torch.zeros(self._n_totals(), dtype=torch.float64, device=self.device)
         for s in range(steps):
             idx = order[s * per_step + rank * self.batch_size:
                         s * per_step + (rank + 1) * self.batch_size].to(self.device)
@@ -483,8 +593,16 @@ class DDPTrainer:
         weights). That needs policy_target="full", whose loss takes the weights and returns the
         rows: ValueError otherwise. The loss dict then gains "train/is_weight_mean" (the mean
         importance weight of the drawn rows) and "train/priority_mean" (the mean priority
-        written, over the rows that had one). priority_beta is ignored by any other buffer."""
+        written, over the rows that had one). priority_beta is ignored by any other buffer.
+        With ownership_coef > 0 the buffer is a ReplayBuffer(ownership=True) (ValueError
+        otherwise, and for such a buffer with ownership_coef = 0, whose sample has two outputs
+        more): every step also draws the rows' ownership targets and adds the head's loss on them
+        (train_step's `ownership`), under the importance weights where there are any."""
         prioritized = bool(getattr(buffer, "prioritized", False))
+        own = self.ownership_coef > 0.0
+        if own != bool(getattr(buffer, "ownership", False)):
+            raise ValueError("train_replay: ownership_coef > 0 goes with a "
+                             "ReplayBuffer(ownership=True), and 0 with one without")
         if prioritized and self.policy_target != "full":
             raise ValueError("train_replay: a ReplayBuffer(prioritized=True) needs "
                              "policy_target='full' (the importance weights and the loss rows "
@@ -496,23 +614,26 @@ class DDPTrainer:
                              device=self.device if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MIN)
             steps = int(t.item())
-        tot = torch.zeros((5 if self.policy_target == "full" else 3) + 2 * prioritized,
-                          dtype=torch.float64, device=self.device)
+        tot = torch.zeros(self._n_totals() + 2 * prioritized, dtype=torch.float64,
+                          device=self.device)
         for s in range(steps):
             if prioritized:
-                states, policy, value, slot, _, prob = buffer.sample(
-                    self.batch_size, seed * world + rank, s, symmetries, with_prob=True)
+                drawn = buffer.sample(self.batch_size, seed * world + rank, s, symmetries,
+                                      with_prob=True)
+                states, policy, value, slot, _, prob = drawn[:6]
                 weights = buffer.is_weights(prob, slot, priority_beta)
-                losses = self.train_step(states, policy, value, weights, rows=True)
+                losses = self.train_step(states, policy, value, weights, rows=True,
+                                         **({"ownership": drawn[6]} if own else {}))
                 priority, state = buffer.update_priorities(slot, self.last_stats["rows"],
                                                            self.wp, self.wv)
                 valid = (state >= 0).sum().clamp(min=1)
                 extra = torch.stack([weights.double().mean(), priority.double().sum() / valid])
                 tot += torch.cat([self._step_totals(losses), extra.to(tot.device)])
                 continue
-            states, policy, value = buffer.sample(self.batch_size, seed * world + rank, s,
-                                                  symmetries)[:3]
-            losses = self.train_step(states, policy, value)
+            drawn = buffer.sample(self.batch_size, seed * world + rank, s, symmetries)
+            states, policy, value = drawn[:3]
+            losses = self.train_step(states, policy, value,
+                                     **({"ownership": drawn[5]} if own else {}))
             tot += self._step_totals(losses)
         tot /= max(1, steps)
         if self.distributed and world > 1:   # the job's loss: the mean over ranks

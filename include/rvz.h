@@ -571,6 +571,26 @@ int rvz_replay_batch(int32_t board_size, int32_t capacity, const uint64_t *mover
                      float *out_policy /* [nb][S*S+1] */, float *out_value /* [nb] */,
                      int32_t *out_slot /* [nb] */, int32_t *out_sym /* [nb] */, void *hip_stream);
 
+/* rvz_replay_ownership (csrc/rvz_replay.hip): the ownership targets of a drawn batch. A ring that
+ * also holds each row's final position (rvz_records_final's two bitboards, 16 B a row) passes the
+ * draw's own out_slot and out_sym; one wavefront per output row, lane = output square. With
+ * P = final_mover[slot[r]], O = final_opponent[slot[r]] and x the S x S array that is +1 where P
+ * has a disc, -1 where O has one and 0 elsewhere:
+ *   out_own[r] = T_sym[r](x), the numbering and direction of rvz_replay_batch's state planes
+ *                (T_k(x) = fliplr^f(rot90^r(x)), k = 4f + r, as NumPy defines them)
+ *   out_margin[r] = popcount(P) - popcount(O), which is also the sum of out_own[r].
+ * A slot[r] outside [0, capacity), a sym[r] outside [0, 8), or a slot whose two bitboards overlap
+ * or have a bit at or above S*S: an all-zero row with margin 0 (so rvz_replay_batch's -1 / -1
+ * rows give zero rows). Every output element is written by exactly one lane. Stateless,
+ * asynchronous on hip_stream, graph-capturable.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, capacity < 1, nb < 0, nb * (S*S + 1)
+ * not fitting in int32, and with nb > 0 a null pointer. nb = 0 returns RVZ_OK without a launch. */
+int rvz_replay_ownership(int32_t board_size, int32_t capacity,
+                         const uint64_t *final_mover, const uint64_t *final_opponent, /* [capacity] */
+                         int32_t nb, const int32_t *slot, const int32_t *sym,          /* [nb] */
+                         float *out_own /* [nb][S*S] */, float *out_margin /* [nb] */,
+                         void *hip_stream);
+
 /* ---- weighted replay sampling: rows drawn in proportion to a per-row weight ----------------
  * The ring gains weight float32 [capacity], one sampling weight per slot (a merged position's
  * record count, a recency factor, a priority). rvz_replay_cdf turns the live rows' weights into a
@@ -890,6 +910,39 @@ int rvz_records_games(int32_t board_size, int32_t plies, int32_t n_games,
                       int32_t *out_state /* [plies][n_games], nullable */,
                       int64_t *out_stats /* [8] */, void *hip_stream);
 
+/* rvz_records_final (csrc/rvz_records.hip): the final position of the game a record belongs to,
+ * from the mover's side: the ownership target of a training row (who holds every square when the
+ * game ends; the sum over the squares is the final disc margin). Stateless, on caller arrays
+ * (device pointers), asynchronous on hip_stream and graph-capturable: no allocation, no copy, no
+ * memset, no synchronisation, no scratch; two consecutive launches (out_stats zeroed, then a lane
+ * per row); every row output of a handled row is written exactly once; out_stats is summed with
+ * 64-bit integer atomics, so the outputs are a pure function of the inputs.
+ * Rows j < min(n, *count) are handled (count null: j < n; a negative *count: none), so a caller
+ * passes rvz_records_games' out_m and out_src straight through without a host read; rows at and
+ * above the bound are not written. Row j, with src[j] = p * n_games + g: the walk starts at the
+ * record at (p, g) with no passes in a row behind it and goes down column g through the plies p,
+ * p + 1, ... A ply whose rec_idx < 0 is skipped. Every other record is checked as
+ * rvz_records_games checks it (no overlapping discs, no bit at or above S*S, side 1 | 2,
+ * idx <= S*S), every record after the first must equal the position the previous make_move left
+ * (black, white and side), and its move is applied with the make_move of csrc/rvz_rules.hip.h
+ * (idx == S*S the pass). When the game ends with boards (B, W), for the row's own side:
+ *   out_final_mover[j] = side == 1 ? B : W, out_final_opponent[j] the other, out_ok[j] = 1.
+ * In every other case the two boards are 0 and out_ok[j] = 0: src[j] outside
+ * [0, plies * n_games), rec_idx < 0 at src[j], a malformed record, a refused move, a broken chain
+ * (unlike rvz_records_games, no new segment starts), or the window ends with the game still open.
+ * out_stats: [0] rows handled, [1] rows with ok = 1, [2] rows whose game is still open at the
+ * window's end, [3] every other row with ok = 0. A row costs at most S*S - 4 make_move calls.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, plies < 1, n_games < 1,
+ * plies * n_games * (S*S + 1) >= 2^31, n < 0, a null record array or out_stats, and with n > 0 a
+ * null src or row output. n = 0 returns RVZ_OK without a launch, and then nothing is written. */
+int rvz_records_final(int32_t board_size, int32_t plies, int32_t n_games,
+                      const uint64_t *rec_black, const uint64_t *rec_white,
+                      const int32_t *rec_side, const int32_t *rec_idx,   /* [plies][n_games] */
+                      int32_t n, const int32_t *src /* [n] */,
+                      const int32_t *count /* [1], nullable, device */,
+                      uint64_t *out_final_mover, uint64_t *out_final_opponent, /* [n] */
+                      int32_t *out_ok /* [n] */, int64_t *out_stats /* [4] */, void *hip_stream);
+
 /* ---- opening pools: the positions after d plies, and games that start from them --------------
  * rvz_openings (csrc/rvz_openings.hip) enumerates the distinct positions after `plies` plies
  * under the engine's own rules (the make_move of csrc/rvz_rules.hip.h: the wrap-around quirk, the
@@ -1000,6 +1053,38 @@ int rvz_policy_value_loss(int32_t board_size, int32_t n, const float *logits /* 
                           double *out_row /* [n][3], nullable */,
                           float *grad_logits /* [n][A] */, float *grad_value /* [n] */,
                           void *hip_stream);
+
+/* rvz_ownership_loss (csrc/rvz_loss.hip): the loss of an auxiliary ownership head against
+ * rvz_replay_ownership's targets, on rvz_policy_value_loss's row wave (lane = square), cross-row
+ * tree and scratch, with its weighting, normalisation, determinism and float64 arithmetic. With
+ * o = logits and t = target, both float32 [n][S*S], per row r:
+ *   L = (1 / S*S) * sum_a (tanh(o[a]) - t[a])^2
+ *   agree = the share of the squares with t[a] != 0 where o[a] has the sign of t[a] (0 for a row
+ *           without such a square)
+ *   w = weight[r], or 1 with a null weight
+ * A row is malformed if a logit is not finite, a target is not -1, 0 or +1, or its weight is
+ * negative or not finite: it gets w = 0, a zero out_row, a zero gradient, and is counted.
+ *   W = sum_r w
+ *   out_loss = { sum_r w L / W, the same, 0, 0, W, sum_r w agree / W, malformed rows, 0 }
+ *              (rvz_policy_value_loss's layout: the loss, the first term, no second term, no
+ *              entropy)
+ *   out_row[r] = { L, agree }
+ *   grad_logits[r][a] = (float) ((w / W) * (2 / S*S) * (tanh(o[a]) - t[a]) * (1 - tanh(o[a])^2))
+ * With W == 0 every mean and every gradient is 0; no NaN is written anywhere. The same inputs
+ * give the same bytes on every call; every output element is written exactly once; out_row and
+ * grad_logits may each be null and are then not computed.
+ * rvz_ownership_loss_scratch_size: rvz_loss_scratch_size's bytes, non-decreasing in n; negative
+ * for bad arguments.
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, n * (S*S + 1) >= 2^31, and with
+ * n > 0 a null logits / target / scratch / out_loss or a scratch that is not 16-byte aligned.
+ * n = 0 returns RVZ_OK without a launch, and then nothing is written. */
+int64_t rvz_ownership_loss_scratch_size(int32_t board_size, int32_t n);
+int rvz_ownership_loss(int32_t board_size, int32_t n, const float *logits /* [n][S*S] */,
+                       const float *target /* [n][S*S] */,
+                       const float *weight /* [n], nullable: every row 1 */,
+                       void *scratch /* 16-byte aligned */, double *out_loss /* [8] */,
+                       double *out_row /* [n][2], nullable */,
+                       float *grad_logits /* [n][S*S], nullable */, void *hip_stream);
 
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
