@@ -7,6 +7,8 @@ the noise is mixed here, in NumPy float32, into the softmaxed row of each search
 
 eps = float32(epsilon), 1 - eps = float32(1) - eps, eta from rvz.dirichlet_noise (the engine's own
 device function) for the root's legal mask, the game's seed and the root's disc count.
+The softmaxed row is rvz.policy_softmax's by default: borrowing it is licensed by
+tests/test_gpu_policy_softmax.py, which holds it to a float64 reference at every output.
 Test infrastructure only (the pattern of tests/oracle_play.py)."""
 from __future__ import annotations
 

@@ -3,7 +3,9 @@ for a sample of games, one MCTS search per ply (mcts.py:322-407) whose leaves ar
 the same h2 LeafEvaluator on the GPU and softmaxed by rvz.policy_softmax — bitwise the softmax
 the expand inside rvz_play applies to its logits (one device function, csrc/rvz_search.hip.h) —
 then get_action_probs' tail (mcts.py:642-694) with each game's numpy MT19937 stream and
-make_move. Test infrastructure only: the checker of tests/ and __graft_entry__.smoke()."""
+make_move. Borrowing rvz.policy_softmax here is licensed by tests/test_gpu_policy_softmax.py,
+which holds that function to a float64 reference at every output. Test infrastructure only: the
+checker of tests/ and __graft_entry__.smoke()."""
 from __future__ import annotations
 
 import numpy as np
