@@ -198,6 +198,18 @@ def load() -> C.CDLL:
     return _lib
 
 
+def is_int(x) -> bool:
+    """An int (any numbers.Integral) that is not a bool."""
+    return isinstance(x, numbers.Integral) and not isinstance(x, bool)
+
+
+def is_number(x, lo: float, hi: float, lo_open: bool = False, hi_open: bool = False) -> bool:
+    """A real number (any numbers.Real, not a bool) in [lo, hi], an end marked open left out;
+    NaN fails."""
+    return (isinstance(x, numbers.Real) and not isinstance(x, bool)
+            and (lo < x if lo_open else lo <= x) and (x < hi if hi_open else x <= hi))
+
+
 _NO_EPSILON = object()
 
 
@@ -227,7 +239,7 @@ def check_schedule_args(moves, late_temperature=0.0):
     or (moves, late_temperature)."""
     if moves is None:
         return None
-    if isinstance(moves, bool) or not isinstance(moves, numbers.Integral) or moves < 0:
+    if not is_int(moves) or moves < 0:
         raise RvzError(f"temperature schedule: moves must be None or an int >= 0, not {moves!r}")
     if int(moves) > 2 ** 31 - 5:
         raise RvzError(f"temperature schedule: moves = {moves!r} is out of range")

@@ -11,13 +11,12 @@ gradients in float64; ``full_policy_loss`` makes it a differentiable torch funct
 from __future__ import annotations
 
 import math
-import numbers
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib
-from ._lib import RvzError, check, ptr
+from ._lib import RvzError, check, is_number, ptr
 
 OUT_LOSS = ("loss", "policy_loss", "value_loss", "target_entropy", "weight_sum", "agreement",
             "malformed")        # out_loss[0 .. 7); out_loss[7] is 0
@@ -57,8 +56,7 @@ def check_loss_args(logits, value, policy_targets, value_targets, weights, polic
     if n * npol >= 2 ** 31:
         raise RvzError("policy_value_loss: n * (S*S + 1) does not fit int32")
     for name, x in (("policy_weight", policy_weight), ("value_weight", value_weight)):
-        if isinstance(x, bool) or not isinstance(x, numbers.Real) or \
-                not 0.0 <= float(x) < math.inf:
+        if not is_number(x, 0.0, math.inf, hi_open=True):
             raise RvzError(f"policy_value_loss: {name} must be a finite number >= 0, not {x!r}")
     return n
 

@@ -20,19 +20,147 @@ The reference's evaluation tournament and checkpointing (:128-140) are out of sc
 """
 from __future__ import annotations
 
-import numbers
 import time
 from typing import Dict, Optional
 
 import torch
 import torch.distributed as dist
 
+from ._lib import is_int, is_number
 from .engine import SOLVE_MAX_EMPTIES, Engine
 from .network import LeafEvaluator, leaf_evaluator
 from .records import records_games
-from .replay import ReplayBuffer
+from .replay import ReplayBuffer, check_recency_decay
 from .selfplay import SelfPlayRunner
-from .trainer import DDPTrainer, adjudicate, games_to_training, records_to_training
+from .trainer import (DDPTrainer, adjudicate, check_ownership_coef, check_policy_target,
+                      games_to_training, records_to_training)
+
+
+def _check_options(board_size: int, *, fused, exact_policy, adjudicate_empties, symmetries,
+                   merge_positions, replay_iterations, policy_target, count_weights,
+                   replay_sampling, replay_recency_decay, replay_priority_alpha,
+                   replay_priority_beta, continuous_plies, openings, reanalyse_rows,
+                   reanalyse_age, ownership_coef) -> tuple:
+    """SelfPlayTrainer's option rules (its docstring has what each option means): ValueError for
+    every refused value or combination, before a model, a device or the library is touched.
+    Returns the options it converts, normalised: (ownership_coef, reanalyse_rows, reanalyse_age,
+    replay_priority_beta, replay_recency_decay, continuous_plies, exact_policy,
+    replay_iterations, adjudicate_empties)."""
+    def unit(x):
+        return is_number(x, 0.0, 1.0)
+    ownership_coef = check_ownership_coef(ownership_coef)
+    if ownership_coef > 0.0:
+        if not replay_iterations or replay_iterations < 1:
+            raise ValueError("ownership_coef > 0 needs replay_iterations >= 1: the ownership "
+                             "targets are held by the replay buffer")
+        if merge_positions:
+            raise ValueError("ownership_coef > 0 keeps one final position per row: "
+                             "merge_positions must be False")
+        if adjudicate_empties:
+            raise ValueError("ownership_coef > 0 needs every game played to its end: "
+                             "adjudicate_empties must be 0")
+    for name, x in (("reanalyse_rows", reanalyse_rows), ("reanalyse_age", reanalyse_age)):
+        if not is_int(x) or x < 0:
+            raise ValueError(f"{name} must be an int >= 0, not {x!r}")
+    if reanalyse_rows and not replay_iterations:
+        raise ValueError("reanalyse_rows needs replay_iterations > 0: it refreshes the "
+                         "replay buffer's rows")
+    if reanalyse_age and not reanalyse_rows:
+        raise ValueError("reanalyse_age needs reanalyse_rows > 0")
+    if reanalyse_rows and replay_iterations < reanalyse_age + 2:
+        raise ValueError("reanalyse_rows needs replay_iterations >= reanalyse_age + 2: a row "
+                         "aged reanalyse_age iterations must stay in the window for the next "
+                         "iteration's training steps")
+    check_policy_target(policy_target, count_weights)
+    if count_weights and not merge_positions:
+        raise ValueError("count_weights=True needs merge_positions=True (the counts are "
+                         "the merged rows' position_counts)")
+    if count_weights and replay_iterations:
+        raise ValueError("count_weights=True needs replay_iterations=0: the replay ring "
+                         "stores no position counts")
+    if replay_sampling not in ("uniform", "counts", "priority"):
+        raise ValueError("replay_sampling must be 'uniform', 'counts' or 'priority', not "
+                         f"{replay_sampling!r}")
+    if replay_sampling == "priority" and not replay_iterations:
+        raise ValueError("replay_sampling='priority' needs replay_iterations > 0: it is the "
+                         "replay buffer's draw")
+    if replay_sampling == "priority" and policy_target != "full":
+        raise ValueError("replay_sampling='priority' needs policy_target='full': the "
+                         "importance weights and the per-row losses are that loss's")
+    if replay_sampling != "priority" and (replay_priority_alpha != 0.6 or
+                                          replay_priority_beta != 0.4):
+        raise ValueError("replay_priority_alpha and replay_priority_beta need "
+                         "replay_sampling='priority'")
+    if not unit(replay_priority_alpha):
+        raise ValueError("replay_priority_alpha must be in [0, 1], not "
+                         f"{replay_priority_alpha!r}")
+    beta = replay_priority_beta
+    if isinstance(beta, (tuple, list)):
+        if len(beta) != 3 or not unit(beta[0]) or not unit(beta[1]) or not is_int(beta[2]) or \
+                beta[2] < 1:
+            raise ValueError("replay_priority_beta must be a float in [0, 1] or (start, end, "
+                             f"iterations >= 1) with both ends in [0, 1], not {beta!r}")
+        beta = (float(beta[0]), float(beta[1]), int(beta[2]))
+    elif not unit(beta):
+        raise ValueError("replay_priority_beta must be a float in [0, 1] or (start, end, "
+                         f"iterations), not {beta!r}")
+    if replay_sampling == "counts" and not replay_iterations:
+        raise ValueError("replay_sampling='counts' needs replay_iterations > 0: it is the "
+                         "replay buffer's draw")
+    if replay_sampling == "counts" and not merge_positions:
+        raise ValueError("replay_sampling='counts' needs merge_positions=True (the weights "
+                         "are the merged rows' position_counts)")
+    check_recency_decay(replay_recency_decay, "replay_recency_decay")
+    if replay_recency_decay != 1.0 and not replay_iterations:
+        raise ValueError("replay_recency_decay != 1 needs replay_iterations > 0: it ages "
+                         "the replay buffer's rows")
+    if continuous_plies is not None:
+        if not is_int(continuous_plies) or continuous_plies < 1:
+            raise ValueError("continuous_plies must be None or an int >= 1, not "
+                             f"{continuous_plies!r}")
+        if not replay_iterations:
+            raise ValueError("continuous_plies needs replay_iterations > 0: its rows are the "
+                             "replay buffer's compact records")
+        if not fused:
+            raise ValueError("continuous_plies needs fused=True: it is one rvz_play launch "
+                             "with autoreset")
+        if adjudicate_empties:
+            raise ValueError("continuous_plies plays every game to its end: "
+                             "adjudicate_empties must be 0")
+        if symmetries is not None:
+            raise ValueError("continuous_plies leaves the symmetry to the replay buffer's "
+                             f"draw: symmetries must be None, not {symmetries!r}")
+        continuous_plies = int(continuous_plies)
+    if openings is not None and adjudicate_empties:
+        raise ValueError("openings start games with more than 4 discs, and adjudication's "
+                         "stopping ply assumes 4: adjudicate_empties must be 0")
+    if openings is not None and not 3 <= len(openings) <= 4:
+        raise ValueError("openings is None or (black, white, side[, salt])")
+    exact_policy = int(exact_policy)
+    if not 0 <= exact_policy <= SOLVE_MAX_EMPTIES:
+        raise ValueError(f"exact_policy must be in [0, {SOLVE_MAX_EMPTIES}]")
+    if symmetries not in (None, "all", "random"):
+        raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
+    replay_iterations = int(replay_iterations)
+    if replay_iterations < 0:
+        raise ValueError("replay_iterations must be >= 0")
+    if replay_iterations and symmetries is not None:
+        raise ValueError("replay_iterations > 0 draws a symmetry with every sampled row "
+                         f"(replay_symmetries): symmetries must be None, not {symmetries!r}")
+    adjudicate_empties, max_plies = int(adjudicate_empties), board_size * board_size - 4
+    if adjudicate_empties and not (1 <= adjudicate_empties <= SOLVE_MAX_EMPTIES and
+                                   adjudicate_empties < max_plies):
+        raise ValueError(f"adjudicate_empties must be 0 or in [1, {SOLVE_MAX_EMPTIES}] and "
+                         f"below {max_plies}")
+    return (ownership_coef, int(reanalyse_rows), int(reanalyse_age), beta,
+            float(replay_recency_decay), continuous_plies, exact_policy, replay_iterations,
+            adjudicate_empties)
+
+
+# the 0-d counters of generate()'s data that run_iteration reports (0 where an option is off)
+_COUNTERS = ("exact_rows", "exact_unsolved", "exact_policy_rows", "exact_policy_unsolved",
+             "adjudicated", "adjudicate_unsolved", "already_over", "symmetry_rows",
+             "symmetry_quirk_rows", "merge_rows", "merge_input_rows")
 
 
 class SelfPlayTrainer:
@@ -80,7 +208,8 @@ class SelfPlayTrainer:
         left out of the selection: no training step would read them again. Every refreshed row
         is therefore trained on for at least one more iteration, which needs
         replay_iterations >= reanalyse_age + 2 for any row to qualify (ValueError otherwise).
-        The re-search's engine is checked (Engine.check) after every pass. It needs replay_iterations > 0, and reanalyse_age needs
+        The re-search's engine is checked (Engine.check) after every pass. It needs
+        replay_iterations > 0, and reanalyse_age needs
         reanalyse_rows > 0, ValueError otherwise. train() then also reports reanalyse/rows (the
         rows rewritten), reanalyse/skipped (selected rows that were not: none is expected),
         reanalyse/policy_kl (the mean over the rewritten rows of KL(new target || old target), the
@@ -207,112 +336,19 @@ class SelfPlayTrainer:
         None: the next power of two >= 32 x games, within [2^12, 2^22]: 2^20 for C4's 32,768
         games per rank). Each slot is 576 B of granules + a 4-B claim word on 8x8 (48 granules
         on 6x6): 2^20 slots = 608 MB, 2^12 = 2.4 MB."""
-        if isinstance(ownership_coef, bool) or not isinstance(ownership_coef, numbers.Real) or \
-                not 0.0 <= float(ownership_coef) < float("inf"):
-            raise ValueError(f"ownership_coef must be a finite number >= 0, not "
-                             f"{ownership_coef!r}")
-        self.ownership_coef = float(ownership_coef)
-        if self.ownership_coef > 0.0:
-            if not replay_iterations or replay_iterations < 1:
-                raise ValueError("ownership_coef > 0 needs replay_iterations >= 1: the ownership "
-                                 "targets are held by the replay buffer")
-            if merge_positions:
-                raise ValueError("ownership_coef > 0 keeps one final position per row: "
-                                 "merge_positions must be False")
-            if adjudicate_empties:
-                raise ValueError("ownership_coef > 0 needs every game played to its end: "
-                                 "adjudicate_empties must be 0")
-        for name, x in (("reanalyse_rows", reanalyse_rows), ("reanalyse_age", reanalyse_age)):
-            if isinstance(x, bool) or not isinstance(x, numbers.Integral) or x < 0:
-                raise ValueError(f"{name} must be an int >= 0, not {x!r}")
-        if reanalyse_rows and not replay_iterations:
-            raise ValueError("reanalyse_rows needs replay_iterations > 0: it refreshes the "
-                             "replay buffer's rows")
-        if reanalyse_age and not reanalyse_rows:
-            raise ValueError("reanalyse_age needs reanalyse_rows > 0")
-        if reanalyse_rows and replay_iterations < reanalyse_age + 2:
-            raise ValueError("reanalyse_rows needs replay_iterations >= reanalyse_age + 2: a row "
-                             "aged reanalyse_age iterations must stay in the window for the next "
-                             "iteration's training steps")
-        self.reanalyse_rows, self.reanalyse_age = int(reanalyse_rows), int(reanalyse_age)
-        if policy_target not in ("argmax", "full"):
-            raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
-        if count_weights and policy_target != "full":
-            raise ValueError("count_weights=True weights the rows of the full policy loss: "
-                             "policy_target must be 'full'")
-        if count_weights and not merge_positions:
-            raise ValueError("count_weights=True needs merge_positions=True (the counts are "
-                             "the merged rows' position_counts)")
-        if count_weights and replay_iterations:
-            raise ValueError("count_weights=True needs replay_iterations=0: the replay ring "
-                             "stores no position counts")
-        if replay_sampling not in ("uniform", "counts", "priority"):
-            raise ValueError("replay_sampling must be 'uniform', 'counts' or 'priority', not "
-                             f"{replay_sampling!r}")
-        if replay_sampling == "priority" and not replay_iterations:
-            raise ValueError("replay_sampling='priority' needs replay_iterations > 0: it is the "
-                             "replay buffer's draw")
-        if replay_sampling == "priority" and policy_target != "full":
-            raise ValueError("replay_sampling='priority' needs policy_target='full': the "
-                             "importance weights and the per-row losses are that loss's")
-        if replay_sampling != "priority" and (replay_priority_alpha != 0.6 or
-                                              replay_priority_beta != 0.4):
-            raise ValueError("replay_priority_alpha and replay_priority_beta need "
-                             "replay_sampling='priority'")
-        def _unit(x):
-            return not isinstance(x, bool) and isinstance(x, numbers.Real) and 0.0 <= x <= 1.0
-        if not _unit(replay_priority_alpha):
-            raise ValueError("replay_priority_alpha must be in [0, 1], not "
-                             f"{replay_priority_alpha!r}")
-        beta = replay_priority_beta
-        if isinstance(beta, (tuple, list)):
-            if len(beta) != 3 or not _unit(beta[0]) or not _unit(beta[1]) or \
-                    isinstance(beta[2], bool) or not isinstance(beta[2], numbers.Integral) or \
-                    beta[2] < 1:
-                raise ValueError("replay_priority_beta must be a float in [0, 1] or (start, end, "
-                                 f"iterations >= 1) with both ends in [0, 1], not {beta!r}")
-            beta = (float(beta[0]), float(beta[1]), int(beta[2]))
-        elif not _unit(beta):
-            raise ValueError("replay_priority_beta must be a float in [0, 1] or (start, end, "
-                             f"iterations), not {beta!r}")
-        self.replay_priority_beta = beta
-        if replay_sampling == "counts" and not replay_iterations:
-            raise ValueError("replay_sampling='counts' needs replay_iterations > 0: it is the "
-                             "replay buffer's draw")
-        if replay_sampling == "counts" and not merge_positions:
-            raise ValueError("replay_sampling='counts' needs merge_positions=True (the weights "
-                             "are the merged rows' position_counts)")
-        if isinstance(replay_recency_decay, bool) or \
-                not isinstance(replay_recency_decay, numbers.Real) or \
-                not 0.0 < replay_recency_decay <= 1.0:
-            raise ValueError("replay_recency_decay must be in (0, 1], not "
-                             f"{replay_recency_decay!r}")
-        if replay_recency_decay != 1.0 and not replay_iterations:
-            raise ValueError("replay_recency_decay != 1 needs replay_iterations > 0: it ages "
-                             "the replay buffer's rows")
-        if continuous_plies is not None:
-            if isinstance(continuous_plies, bool) or \
-                    not isinstance(continuous_plies, numbers.Integral) or continuous_plies < 1:
-                raise ValueError("continuous_plies must be None or an int >= 1, not "
-                                 f"{continuous_plies!r}")
-            if not replay_iterations:
-                raise ValueError("continuous_plies needs replay_iterations > 0: its rows are the "
-                                 "replay buffer's compact records")
-            if not fused:
-                raise ValueError("continuous_plies needs fused=True: it is one rvz_play launch "
-                                 "with autoreset")
-            if adjudicate_empties:
-                raise ValueError("continuous_plies plays every game to its end: "
-                                 "adjudicate_empties must be 0")
-            if symmetries is not None:
-                raise ValueError("continuous_plies leaves the symmetry to the replay buffer's "
-                                 f"draw: symmetries must be None, not {symmetries!r}")
-        if openings is not None and adjudicate_empties:
-            raise ValueError("openings start games with more than 4 discs, and adjudication's "
-                             "stopping ply assumes 4: adjudicate_empties must be 0")
-        if openings is not None and not 3 <= len(openings) <= 4:
-            raise ValueError("openings is None or (black, white, side[, salt])")
-        self.continuous_plies = None if continuous_plies is None else int(continuous_plies)
+        bs = int(getattr(model, "board_size", 8))
+        (self.ownership_coef, self.reanalyse_rows, self.reanalyse_age, self.replay_priority_beta,
+         self.replay_recency_decay, self.continuous_plies, self.exact_policy,
+         self.replay_iterations, self.adjudicate_empties) = _check_options(
+            bs, fused=fused, exact_policy=exact_policy, adjudicate_empties=adjudicate_empties,
+            symmetries=symmetries, merge_positions=merge_positions,
+            replay_iterations=replay_iterations, policy_target=policy_target,
+            count_weights=count_weights, replay_sampling=replay_sampling,
+            replay_recency_decay=replay_recency_decay,
+            replay_priority_alpha=replay_priority_alpha,
+            replay_priority_beta=replay_priority_beta, continuous_plies=continuous_plies,
+            openings=openings, reanalyse_rows=reanalyse_rows, reanalyse_age=reanalyse_age,
+            ownership_coef=ownership_coef)
         self.model = model.eval()
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -320,26 +356,11 @@ class SelfPlayTrainer:
                                  else (0, 1))
         self.games, self.seed = int(games), int(seed)
         self.exact_endgame, self.exact_node_limit = int(exact_endgame), int(exact_node_limit)
-        self.exact_wld = bool(exact_wld)
-        self.exact_policy = int(exact_policy)
-        if not 0 <= self.exact_policy <= SOLVE_MAX_EMPTIES:
-            raise ValueError(f"exact_policy must be in [0, {SOLVE_MAX_EMPTIES}]")
-        if symmetries not in (None, "all", "random"):
-            raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
-        self.symmetries = symmetries
+        self.exact_wld, self.merge_positions = bool(exact_wld), bool(merge_positions)
+        self.symmetries, self.replay_sampling = symmetries, replay_sampling
         self.symmetry_seed = None if symmetry_seed is None else int(symmetry_seed)
-        self.merge_positions = bool(merge_positions)
-        self.replay_iterations = int(replay_iterations)
-        if self.replay_iterations < 0:
-            raise ValueError("replay_iterations must be >= 0")
-        if self.replay_iterations and symmetries is not None:
-            raise ValueError("replay_iterations > 0 draws a symmetry with every sampled row "
-                             f"(replay_symmetries): symmetries must be None, not {symmetries!r}")
         self.replay_steps = None if replay_steps is None else int(replay_steps)
         self.replay_symmetries = bool(replay_symmetries)
-        self.replay_sampling = replay_sampling
-        self.replay_recency_decay = float(replay_recency_decay)
-        self.adjudicate_empties = int(adjudicate_empties)
         self.adjudicate_node_limit = int(adjudicate_node_limit)
         self.train_steps = train_steps
         self.trainer = DDPTrainer(model, lr=lr, weight_decay=weight_decay,
@@ -353,7 +374,6 @@ class SelfPlayTrainer:
         # drops the memo)
         self.evaluator = leaf_evaluator(model, device=self.device)
         h2 = isinstance(self.evaluator, LeafEvaluator)
-        bs = int(getattr(model, "board_size", 8))
         self.eng = Engine(games, num_simulations, batch_size, c_puct, board_size=bs,
                           device=self.device, compact_leaves=compact_leaves, memo=memo)
         if root_noise is not None:
@@ -363,10 +383,6 @@ class SelfPlayTrainer:
         if openings is not None:
             self.eng.openings(*openings)
         self.max_plies = bs * bs - 4
-        if self.adjudicate_empties and not (1 <= self.adjudicate_empties <= SOLVE_MAX_EMPTIES and
-                                            self.adjudicate_empties < self.max_plies):
-            raise ValueError(f"adjudicate_empties must be 0 or in [1, {SOLVE_MAX_EMPTIES}] and "
-                             f"below {self.max_plies}")
         # fused: every game of the iteration in ONE rvz_play launch with device records, the
         # memo's deferred last batch and the cross-game table (a new generation per refresh());
         # else the pull-style ply graph (per-batch launches, records copied per ply)
@@ -394,19 +410,17 @@ class SelfPlayTrainer:
             if replay_capacity is None:
                 replay_capacity = self.replay_iterations * self.games * (
                     self.max_plies + (self.continuous_plies or 0))
-            weighted = self.replay_sampling == "counts" or self.replay_recency_decay != 1.0
-            priority = ({"prioritized": True, "priority_alpha": float(replay_priority_alpha),
-                         "recency_decay": self.replay_recency_decay}
-                        if self.replay_sampling == "priority" else {})
+            draw = {}
+            if self.replay_sampling == "priority":
+                draw = {"prioritized": True, "priority_alpha": float(replay_priority_alpha)}
+            elif self.replay_sampling == "counts" or self.replay_recency_decay != 1.0:
+                draw = {"weighted": True}
+            if draw:
+                draw["recency_decay"] = self.replay_recency_decay
             self.buffer = ReplayBuffer(int(replay_capacity), bs, self.device,
-                                       window_iterations=self.replay_iterations,
-                                       **(priority or
-                                          ({"weighted": True,
-                                            "recency_decay": self.replay_recency_decay}
-                                           if weighted else {})),
-                                       **({"stamps": True} if self.reanalyse_rows else {}),
-                                       **({"ownership": True} if self.ownership_coef > 0.0
-                                          else {}))
+                                       window_iterations=self.replay_iterations, **draw,
+                                       stamps=bool(self.reanalyse_rows),
+                                       ownership=self.ownership_coef > 0.0)
         if self.reanalyse_rows:
             # the re-search's own engine: the plain search, whatever self-play's engine has set
             self.reanalyse_eng = Engine(games, num_simulations, batch_size, c_puct, board_size=bs,
@@ -424,12 +438,13 @@ class SelfPlayTrainer:
             seed = (self.seed + self.iteration) * self.world + self.rank
         return {"symmetries": self.symmetries, "symmetry_seed": seed}
 
-    def _merge_args(self) -> dict:
-        return {"merge_positions": True} if self.merge_positions else {}
-
-    def _compact_args(self) -> dict:
-        own = {"ownership": True} if self.ownership_coef > 0.0 else {}
-        return {"compact": True, **own} if self.replay_iterations else {}
+    def _record_args(self) -> dict:
+        """This iteration's options as records_to_training and games_to_training take them; the
+        rows are compact exactly when there is a replay buffer to hold them."""
+        return {"exact_endgame": self.exact_endgame, "exact_node_limit": self.exact_node_limit,
+                "exact_wld": self.exact_wld, "exact_policy": self.exact_policy,
+                **self._symmetry_args(), "merge_positions": self.merge_positions,
+                "compact": bool(self.replay_iterations), "ownership": self.ownership_coef > 0.0}
 
     def generate(self) -> Dict[str, torch.Tensor]:
         """One iteration's self-play: every game of this rank from the start to its end.
@@ -454,11 +469,7 @@ class SelfPlayTrainer:
             raise RuntimeError(f"a game is not over after {self.max_plies} plies")
         return records_to_training(run.rec_black, run.rec_white, run.rec_side, run.rec_idx,
                                    run.rec_p, run.post_status, self.eng.board_size,
-                                   exact_endgame=self.exact_endgame,
-                                   exact_node_limit=self.exact_node_limit,
-                                   exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                   **self._symmetry_args(), **self._merge_args(),
-                                   **self._compact_args())
+                                   **self._record_args())
 
     def _continuous(self) -> Dict[str, torch.Tensor]:
         """generate() with continuous_plies on: one launch of K plies with autoreset behind the
@@ -471,14 +482,8 @@ class SelfPlayTrainer:
         run.check()
         rows = records_games(run.rec_black, run.rec_white, run.rec_side, run.rec_idx, run.rec_p,
                              self.eng.board_size, emit_from=C)
-        out = games_to_training(rows, self.eng.board_size, exact_endgame=self.exact_endgame,
-                                exact_node_limit=self.exact_node_limit,
-                                exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                **self._merge_args(), compact=True,
-                                **({"ownership": True,
-                                    "window": (run.rec_black, run.rec_white, run.rec_side,
-                                               run.rec_idx)}
-                                   if self.ownership_coef > 0.0 else {}))
+        out = games_to_training(rows, self.eng.board_size, **self._record_args(),
+                                window=(run.rec_black, run.rec_white, run.rec_side, run.rec_idx))
         run.roll()
         out["records_stats"] = rows["stats"]
         return out
@@ -499,11 +504,7 @@ class SelfPlayTrainer:
                               torch.full_like(run.rec_idx[:plies], -2))
         out = records_to_training(run.rec_black[:plies], run.rec_white[:plies],
                                   run.rec_side[:plies], rec_idx, run.rec_p[:plies], final,
-                                  eng.board_size, exact_endgame=self.exact_endgame,
-                                  exact_node_limit=self.exact_node_limit,
-                                  exact_wld=self.exact_wld, exact_policy=self.exact_policy,
-                                  **self._symmetry_args(), **self._merge_args(),
-                                  **self._compact_args())
+                                  eng.board_size, **self._record_args())
         out.update(stats)
         return out
 
@@ -540,7 +541,7 @@ class SelfPlayTrainer:
                 steps = min(steps, self.train_steps)
             if self.continuous_plies and len(self.buffer) == 0:
                 steps = 0               # no game has finished yet: nothing to draw from
-            beta =({"priority_beta": self.priority_beta()}
+            beta = ({"priority_beta": self.priority_beta()}
                     if self.replay_sampling == "priority" else {})
             out = self.trainer.train_replay(self.buffer, steps, seed=self.seed + self.iteration,
                                             symmetries=self.replay_symmetries, **beta)
@@ -606,17 +607,7 @@ class SelfPlayTrainer:
         out.update({"selfplay_s": t1 - t0, "train_s": t2 - t1 - out.get("reanalyse_s", 0.0),
                     "board_steps": plies,
                     "samples": int(data["policy_targets"].shape[0]),
-                    "exact_rows": int(data.get("exact_rows", 0)),
-                    "exact_unsolved": int(data.get("exact_unsolved", 0)),
-                    "exact_policy_rows": int(data.get("exact_policy_rows", 0)),
-                    "exact_policy_unsolved": int(data.get("exact_policy_unsolved", 0)),
-                    "adjudicated": int(data.get("adjudicated", 0)),
-                    "adjudicate_unsolved": int(data.get("adjudicate_unsolved", 0)),
-                    "already_over": int(data.get("already_over", 0)),
-                    "symmetry_rows": int(data.get("symmetry_rows", 0)),
-                    "symmetry_quirk_rows": int(data.get("symmetry_quirk_rows", 0)),
-                    "merge_rows": int(data.get("merge_rows", 0)),
-                    "merge_input_rows": int(data.get("merge_input_rows", 0)),
+                    **{k: int(data.get(k, 0)) for k in _COUNTERS},
                     "replay_rows": len(self.buffer) if self.buffer is not None else 0,
                     "replay_iterations_held": (len(self.buffer.rows_by_iteration())
                                                if self.buffer is not None else 0)})

@@ -2,7 +2,8 @@
 (include/rvz.h): board symmetries, merge_positions, the replay ring's draws and the cut of autoreset
 self-play records into finished games. Every argument rule
 is one private helper that raises ``RvzError``, its message beginning with the caller's name,
-before any device call."""
+before any device call; what counts as an int or as a number in a range is ``_lib.is_int`` and
+``_lib.is_number``, for the whole package."""
 from __future__ import annotations
 
 import numbers
@@ -11,7 +12,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import RvzError, check, check_board_size, ptr
+from ._lib import RvzError, check, check_board_size, is_int, is_number, ptr
 
 _U64 = 2 ** 64 - 1
 
@@ -19,7 +20,7 @@ _U64 = 2 ** 64 - 1
 # ------------------------------------------------------------------ the argument rules
 def _ints(who: str, **named) -> None:
     for name, x in named.items():
-        if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+        if not is_int(x):
             raise RvzError(f"{who}: {name} is an int, not {x!r}")
 
 
@@ -96,7 +97,7 @@ _SYM_PERMS = [tuple(3 * a + b for a, b in (_sym_src(k, i, j, 3) for i in range(3
 
 
 def _sym_index(k, what: str) -> int:
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or not 0 <= k < 8:
+    if not is_int(k) or not 0 <= k < 8:
         raise RvzError(f"{what}: a symmetry is an int in [0, 8), not {k!r}")
     return int(k)
 
@@ -631,8 +632,7 @@ PRIORITY_MIN_FLOOR, PRIORITY_MAX_CAP = 2.0 ** -16, 65536.0
 
 def _number(who: str, name: str, x, lo: float, hi: float, closed_hi: bool = True) -> float:
     """A real number (not a bool) in [lo, hi] (or [lo, hi)); NaN fails."""
-    if isinstance(x, bool) or not isinstance(x, numbers.Real) or \
-            not (lo <= float(x) <= hi if closed_hi else lo <= float(x) < hi):
+    if not is_number(x, lo, hi, hi_open=not closed_hi):
         raise RvzError(f"{who}: {name} must be a number in [{lo}, {hi}{']' if closed_hi else ')'}"
                        f", not {x!r}")
     return float(x)

@@ -26,16 +26,22 @@ their policy targets overwritten in place (MuZero's Reanalyse in an AlphaZero lo
 """
 from __future__ import annotations
 
-import numbers
-from typing import List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
 from . import _lib
-from ._lib import RvzError
+from ._lib import RvzError, is_int, is_number
 from .records import (check_priority_args, replay_batch, replay_batch_weighted, replay_cdf,
                       replay_is_weight, replay_ownership, replay_priority, replay_refresh,
                       replay_roots, replay_stale)
+
+
+def check_recency_decay(recency_decay, name: str = "ReplayBuffer: recency_decay") -> None:
+    """ReplayBuffer's rule for recency_decay (SelfPlayTrainer checks its replay_recency_decay by
+    it too, under that name)."""
+    if not is_number(recency_decay, 0.0, 1.0, lo_open=True):
+        raise ValueError(f"{name} must be in (0, 1], not {recency_decay!r}")
 
 
 class ReplayBuffer:
@@ -102,7 +108,7 @@ class ReplayBuffer:
         the draw's own slot and sym. reanalyse leaves the two columns alone. Without it the buffer
         allocates nothing more and behaves exactly as before."""
         for name, x in (("capacity", capacity), ("window_iterations", window_iterations)):
-            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            if not is_int(x):
                 raise ValueError(f"ReplayBuffer: {name} is an int, not {x!r}")
         if board_size not in (8, 6):
             raise ValueError("board_size must be 8 or 6")
@@ -126,36 +132,30 @@ class ReplayBuffer:
                                   cdf_builder is not None):
             raise ValueError("ReplayBuffer: recency_decay, weighted_batcher and cdf_builder need "
                              "weighted=True")
-        if isinstance(recency_decay, bool) or not isinstance(recency_decay, numbers.Real) or \
-                not 0.0 < recency_decay <= 1.0:
-            raise ValueError(f"ReplayBuffer: recency_decay must be in (0, 1], not "
-                             f"{recency_decay!r}")
-        npol = self.board_size ** 2 + 1
-        self.mover = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-        self.opponent = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-        self.policy = torch.zeros(self.capacity, npol, dtype=torch.float32, device=self.device)
-        self.value = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+        check_recency_decay(recency_decay)
+        if ownership_batcher is not None and not ownership:
+            raise ValueError("ReplayBuffer: ownership_batcher needs ownership=True")
+        self.mover, self.opponent = self._zeros(torch.int64), self._zeros(torch.int64)
+        self.policy = self._zeros(torch.float32, self.board_size ** 2 + 1)
+        self.value = self._zeros(torch.float32)
         self.start = 0                  # the slot of the oldest row
         self._live = 0
         self._ledger: List[List[int]] = []      # [iteration, rows], oldest first
         self.stamps = bool(stamps)
         if self.stamps:
-            self.stamp = torch.zeros(self.capacity, dtype=torch.int32, device=self.device)
-        if ownership_batcher is not None and not ownership:
-            raise ValueError("ReplayBuffer: ownership_batcher needs ownership=True")
+            self.stamp = self._zeros(torch.int32)
         if ownership:
             self.ownership = True
             self.ownership_batcher = (replay_ownership if ownership_batcher is None
                                       else ownership_batcher)
-            self.final_mover = torch.zeros(self.capacity, dtype=torch.int64, device=self.device)
-            self.final_opponent = torch.zeros(self.capacity, dtype=torch.int64,
-                                              device=self.device)
+            self.final_mover, self.final_opponent = (self._zeros(torch.int64),
+                                                     self._zeros(torch.int64))
         if self.weighted:
             self.recency_decay = float(recency_decay)
             self.weighted_batcher = (replay_batch_weighted if weighted_batcher is None
                                      else weighted_batcher)
             self.cdf_builder = replay_cdf if cdf_builder is None else cdf_builder
-            self.weight = torch.zeros(self.capacity, dtype=torch.float32, device=self.device)
+            self.weight = self._zeros(torch.float32)
             # the table at this capacity: 4 words of header, one per row, the scan's upper levels
             words = _lib.load().rvz_replay_cdf_size(self.capacity, 0) // 8
             self._cdf = torch.zeros(words, dtype=torch.int64, device=self.device)
@@ -175,6 +175,24 @@ class ReplayBuffer:
                 else priority_updater
             self.is_weighter = replay_is_weight if is_weighter is None else is_weighter
             self._max_priority = torch.ones(1, dtype=torch.float32, device=self.device)
+
+    def _zeros(self, dtype, *row_shape) -> torch.Tensor:
+        return torch.zeros(self.capacity, *row_shape, dtype=dtype, device=self.device)
+
+    def _columns(self) -> Dict[str, torch.Tensor]:
+        """The ring's per-row columns, name -> tensor [capacity, ...], in append's write order.
+        Each is the attribute of its name, there only with the option it belongs to."""
+        return {k: vars(self)[k] for k in ("mover", "opponent", "policy", "value", "final_mover",
+                                           "final_opponent", "weight", "stamp") if k in vars(self)}
+
+    def _write(self, ring: torch.Tensor, head: int, n: int, rows) -> None:
+        """rows (a tensor of n rows, or one scalar for all n) into the n slots from `head` on,
+        wrapping at the ring's end: at most two slice writes."""
+        first = min(n, self.capacity - head)
+        tensor = isinstance(rows, torch.Tensor)
+        ring[head:head + first] = rows[:first] if tensor else rows
+        if first < n:
+            ring[:n - first] = rows[first:] if tensor else rows
 
     def __len__(self) -> int:
         return self._live
@@ -206,7 +224,7 @@ class ReplayBuffer:
         (stamps=True only): the iteration whose net produced the rows' policy targets, an int in
         [0, 2^31); None: `iteration`. final_mover / final_opponent (ownership=True only, and
         required then): int64 [n], the rows' final positions."""
-        if isinstance(iteration, bool) or not isinstance(iteration, numbers.Integral):
+        if not is_int(iteration):
             raise ValueError(f"ReplayBuffer.append: iteration is an int, not {iteration!r}")
         n = mover.numel()
         npol = self.board_size ** 2 + 1
@@ -235,8 +253,7 @@ class ReplayBuffer:
             raise ValueError("ReplayBuffer.append: stamp needs ReplayBuffer(stamps=True)")
         if self.stamps:
             stamp = iteration if stamp is None else stamp
-            if isinstance(stamp, bool) or not isinstance(stamp, numbers.Integral) or \
-                    not 0 <= stamp < 2 ** 31:
+            if not is_int(stamp) or not 0 <= stamp < 2 ** 31:
                 raise ValueError(f"ReplayBuffer.append: stamp is an int in [0, 2^31), not "
                                  f"{stamp!r}")
         if n > self.capacity:
@@ -246,11 +263,9 @@ class ReplayBuffer:
                              f"{self._ledger[-1][0]}")
         if n:
             head = (self.start + self._live) % self.capacity
-            first = min(n, self.capacity - head)
-            fields = [(self.mover, mover), (self.opponent, opponent), (self.policy, policy),
-                      (self.value, value.reshape(n))]
-            if self.ownership:
-                fields += [(self.final_mover, final_mover), (self.final_opponent, final_opponent)]
+            rows = {"mover": mover, "opponent": opponent, "policy": policy,
+                    "value": value.reshape(n), "final_mover": final_mover,
+                    "final_opponent": final_opponent}
             if self.weighted:
                 if self._ledger and iteration > self._ledger[-1][0] and self.recency_decay != 1.0:
                     # the held rows age by the iterations that passed (slots that hold no row too:
@@ -261,16 +276,12 @@ class ReplayBuffer:
                     weight = self._max_priority.expand(n)       # read on the device
                 elif weight is None:
                     weight = torch.ones(n, dtype=torch.float32, device=self.device)
-                fields.append((self.weight, weight))
+                rows["weight"] = weight
                 self._dirty = True
-            for ring, rows in fields:
-                ring[head:head + first].copy_(rows[:first])
-                if first < n:
-                    ring[:n - first].copy_(rows[first:])
             if self.stamps:
-                self.stamp[head:head + first] = int(stamp)
-                if first < n:
-                    self.stamp[:n - first] = int(stamp)
+                rows["stamp"] = int(stamp)
+            for name, ring in self._columns().items():
+                self._write(ring, head, n, rows[name])
             if self._ledger and self._ledger[-1][0] == iteration:
                 self._ledger[-1][1] += n
             else:
@@ -427,10 +438,9 @@ class ReplayBuffer:
             raise ValueError(f"{who}: the engine plays {engine.board_size}x{engine.board_size}, "
                              f"the ring holds {self.board_size}x{self.board_size}")
         for name, x in (("rows", rows), ("lo", lo), ("below", below), ("new_stamp", new_stamp)):
-            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+            if not is_int(x):
                 raise ValueError(f"{who}: {name} is an int, not {x!r}")
-        if isinstance(first, bool) or not isinstance(first, numbers.Integral) or \
-                not 0 <= first <= self._live:
+        if not is_int(first) or not 0 <= first <= self._live:
             raise ValueError(f"{who}: first = {first!r} must be an int in [0, {self._live}]")
         rows, G, first = int(rows), engine.n_games, int(first)
         out = {"slot": torch.full((max(rows, 0),), -1, dtype=torch.int32, device=self.device),

@@ -15,7 +15,6 @@ lockstep instead of one after another.
 """
 from __future__ import annotations
 
-import numbers
 import os
 import time
 from datetime import datetime
@@ -24,6 +23,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from ._lib import is_int
 from .engine import Engine, board_canonical
 
 
@@ -47,8 +47,7 @@ class SelfPlayRunner:
         # each window into the games that finished in its new part (C >= S*S - 4, the longest
         # game, keeps every such game whole). 0: the records hold max_plies plies of whole
         # lockstep games
-        if isinstance(carry_plies, bool) or not isinstance(carry_plies, numbers.Integral) or \
-                carry_plies < 0:
+        if not is_int(carry_plies) or carry_plies < 0:
             raise ValueError(f"carry_plies must be an int >= 0, not {carry_plies!r}")
         self.carry_plies = int(carry_plies)
         if self.carry_plies and not (fused and record):

@@ -17,14 +17,15 @@ optimizer step. Differences by design:
 """
 from __future__ import annotations
 
-import numbers
-from typing import Dict, Optional
+from dataclasses import dataclass
+from typing import Callable, Dict, Optional
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._lib import is_number
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
                      solve_moves, solve_moves_wld, solve_wld)
 from .loss import full_ownership_loss, full_policy_loss
@@ -63,8 +64,9 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     squares whose every move the per-move solver decides (rvz.best_moves' `complete`) gets the
     policy target mask / mask.sum(), float32: uniform over the proven-optimal moves (the pass
     index for a root that can only pass), so its argmax, which DDPTrainer trains on by default, is
-    the lowest-index optimal move (DDPTrainer(policy_target="full") trains on the whole row). Rows above N, and rows with an abandoned move, keep their MCTS
-    target bit for bit; states and value targets are untouched. Two more keys then, 0-d int64
+    the lowest-index optimal move (DDPTrainer(policy_target="full") trains on the whole row).
+    Rows above N, and rows with an abandoned move, keep their MCTS target bit for bit; states
+    and value targets are untouched. Two more keys then, 0-d int64
     (no host synchronisation): "exact_policy_rows", the rows replaced, and
     "exact_policy_unsolved", the rows within N with an abandoned move. N = 0 (the default) is
     off: the keys and bytes of before.
@@ -124,126 +126,160 @@ def records_to_training(rec_black: torch.Tensor, rec_white: torch.Tensor, rec_si
     "final_mover", "final_opponent", "ok": default rvz.records_final (the rvz_records_final HIP
     kernel).
     """
-    if symmetries not in (None, "all", "random"):
-        raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
-    if compact and symmetries is not None:
-        raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
-                         f"symmetries must be None, not {symmetries!r}")
-    _check_ownership(ownership, merge_positions, compact)
-    if canonical is None:
-        canonical = board_canonical
+    o = _record_options(
+        board_size=board_size, canonical=canonical, exact_endgame=exact_endgame, solver=solver,
+        exact_node_limit=exact_node_limit, exact_wld=exact_wld, exact_policy=exact_policy,
+        moves_solver=moves_solver, symmetries=symmetries, symmetry_seed=symmetry_seed,
+        augment=augment, merge_positions=merge_positions, merger=merger, compact=compact,
+        ownership=ownership, finaler=finaler)
     P, G = rec_idx.shape
     live = (rec_idx >= 0).t().reshape(-1)                    # game-major order
-    fin = None
+    fin = {}
     if ownership:
         # record (p, g) is window index p * G + g; the kept rows are game-major
         src = torch.arange(P * G, device=rec_idx.device).reshape(P, G).t().reshape(-1)[live]
-        fin = (records_final if finaler is None else finaler)(
-            rec_black, rec_white, rec_side, rec_idx, src.to(torch.int32), None, board_size)
-        ok = fin["ok"].to(live.device) != 0
+        ok, fin = o.final_rows((rec_black, rec_white, rec_side, rec_idx), src.to(torch.int32))
         live = live.clone()
         live[live.nonzero().reshape(-1)[~ok]] = False
-        fin = {"final_mover": fin["final_mover"][ok], "final_opponent": fin["final_opponent"][ok],
-               "ownership_dropped": (~ok).sum()}
     black = rec_black.t().reshape(-1)[live].contiguous()
     white = rec_white.t().reshape(-1)[live].contiguous()
     side = rec_side.t().reshape(-1)[live]
-    st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
-                      torch.zeros_like(side)], dim=1).to(torch.int32).contiguous()
-    states = (canonical(black, white, st, board_size)
-              if symmetries is None and not merge_positions and not compact else None)
+    st = _status_rows(side)
+    states = o.planes_now(black, white, st)
     policy = rec_p.permute(1, 0, 2).reshape(P * G, -1)[live].to(torch.float32)
     winner = final_status[:, 2].to(torch.int32).unsqueeze(0).expand(P, G).t().reshape(-1)[live]
     over = final_status[:, 1].unsqueeze(0).expand(P, G).t().reshape(-1)[live]
     v = torch.where(winner == side.to(torch.int32), 1.0, -1.0)
     v = torch.where(winner == 0, torch.zeros_like(v), v)
     v = torch.where(over != 0, v, -torch.ones_like(v))      # winner None -> -1 (self_play.py:121-126)
-    out = _training_tail(black, white, st, states, policy, v, board_size, canonical,
-                         exact_endgame, solver, exact_node_limit, exact_wld, exact_policy,
-                         moves_solver, symmetries, symmetry_seed, augment, merge_positions,
-                         merger, compact)
-    if fin is not None:
-        out.update(fin)
-    return out
+    return {**_training_tail(black, white, st, states, policy, v, o), **fin}
 
 
-def _check_ownership(ownership, merge_positions, compact) -> None:
-    if ownership and merge_positions:
+@dataclass(frozen=True)
+class _RecordOptions:
+    """The options records_to_training and games_to_training share, as their arguments of the
+    same names (canonical and finaler with their defaults filled in)."""
+    board_size: int
+    canonical: Callable
+    exact_endgame: int
+    solver: Optional[Callable]
+    exact_node_limit: int
+    exact_wld: bool
+    exact_policy: int
+    moves_solver: Optional[Callable]
+    symmetries: Optional[str]
+    symmetry_seed: int
+    augment: Optional[Callable]
+    merge_positions: bool
+    merger: Optional[Callable]
+    compact: bool
+    ownership: bool
+    finaler: Callable
+
+    def planes_now(self, black, white, st):
+        """The canonical planes of the kept records, or None where a later step writes the states
+        (merging, symmetries) or the rows carry none (compact)."""
+        if self.symmetries is None and not self.merge_positions and not self.compact:
+            return self.canonical(black, white, st, self.board_size)
+        return None
+
+    def final_rows(self, window, src):
+        """ownership: the final positions of the records src of `window` (rec_black, rec_white,
+        rec_side, rec_idx). Returns (ok, keys): ok bool [n], the records whose walk reaches the
+        end of their game, and those records' "final_mover" / "final_opponent" with
+        "ownership_dropped"."""
+        fin = self.finaler(*window, src, None, self.board_size)
+        ok = fin["ok"].to(src.device) != 0
+        return ok, {"final_mover": fin["final_mover"][ok],
+                    "final_opponent": fin["final_opponent"][ok], "ownership_dropped": (~ok).sum()}
+
+
+def _record_options(canonical, finaler, **options) -> _RecordOptions:
+    """The record options checked: the combinations both functions refuse."""
+    o = _RecordOptions(canonical=board_canonical if canonical is None else canonical,
+                       finaler=records_final if finaler is None else finaler, **options)
+    if o.symmetries not in (None, "all", "random"):
+        raise ValueError(f"symmetries must be None, 'all' or 'random', not {o.symmetries!r}")
+    if o.compact and o.symmetries is not None:
+        raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
+                         f"symmetries must be None, not {o.symmetries!r}")
+    if o.ownership and o.merge_positions:
         raise ValueError("ownership=True keeps one final position per row: merge_positions must "
                          "be False (a merged row would need the mean ownership of its records)")
-    if ownership and not compact:
+    if o.ownership and not o.compact:
         raise ValueError("ownership=True adds the final bitboards to the compact rows a replay "
                          "buffer holds: compact must be True")
+    return o
 
 
-def _training_tail(black, white, st, states, policy, v, board_size, canonical, exact_endgame,
-                   solver, exact_node_limit, exact_wld, exact_policy, moves_solver, symmetries,
-                   symmetry_seed, augment, merge_positions, merger, compact):
+def _status_rows(side: torch.Tensor) -> torch.Tensor:
+    """The status {side, 0, -1, 0} of a position mid-game, int32 [n, 4]."""
+    return torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
+                        torch.zeros_like(side)], dim=1).to(torch.int32).contiguous()
+
+
+def _training_tail(black, white, st, states, policy, v, o: _RecordOptions):
     """What records_to_training and games_to_training share: the kept records (black, white, st
     [n, 4], policy float32 [n, S*S+1], v [n] from the games' outcomes; states the canonical planes
     or None where a later step writes them) through exact_endgame, exact_policy, merge_positions,
     compact and symmetries, in records_to_training's order and with its keys. Every target it
     computes is relative to the player to move."""
+    board_size, exact_wld, limit = o.board_size, o.exact_wld, o.exact_node_limit
     # compact: the two bitboards are filled in below, once merging has chosen the rows
-    out = {"mover": None, "opponent": None} if compact else {"states": states}
+    out = {"mover": None, "opponent": None} if o.compact else {"states": states}
     out.update({"policy_targets": policy, "value_targets": v.reshape(-1, 1).float()})
-    if exact_endgame:
-        if solver is None:
-            def solver(b, w, s, bs, me):
-                return (solve_wld if exact_wld else solve)(b, w, s, bs, me, exact_node_limit)
-        score, move = solver(black, white, st, board_size, int(exact_endgame))[:2]
+    if o.exact_endgame:
+        solver = o.solver if o.solver is not None else lambda b, w, s, bs, me: (
+            solve_wld if exact_wld else solve)(b, w, s, bs, me, limit)
+        score, move = solver(black, white, st, board_size, int(o.exact_endgame))[:2]
         solved = move >= 0                                   # -3: above N; -4: abandoned
         exact = torch.sign(score).to(torch.float32).reshape(-1, 1)
         out["value_targets"] = torch.where(solved.reshape(-1, 1), exact, out["value_targets"])
         out["exact_rows"] = solved.sum()
         out["exact_unsolved"] = (move == -4).sum()
-    if exact_policy:
-        if moves_solver is None:
-            def moves_solver(b, w, s, bs, me):
-                return (solve_moves_wld if exact_wld else solve_moves)(b, w, s, bs, me,
-                                                                      exact_node_limit)
-        scores, count = moves_solver(black, white, st, board_size, int(exact_policy))[:2]
+    if o.exact_policy:
+        moves_solver = o.moves_solver if o.moves_solver is not None else lambda b, w, s, bs, me: (
+            solve_moves_wld if exact_wld else solve_moves)(b, w, s, bs, me, limit)
+        scores, count = moves_solver(black, white, st, board_size, int(o.exact_policy))[:2]
         scores, count = scores.to(policy.device), count.to(policy.device)
         mask, complete = best_moves(scores, count, *((-1, 1) if exact_wld else (-64, 64)))[1:]
         exact = mask.to(torch.float32) / mask.sum(dim=1, keepdim=True).clamp(min=1)
         out["policy_targets"] = torch.where(complete.unsqueeze(1), exact, policy)
         out["exact_policy_rows"] = complete.sum()
         out["exact_policy_unsolved"] = ((count >= 1) & (scores == SOLVE_ABANDONED).any(dim=1)).sum()
-    if merge_positions:
-        if merger is None:
-            merger = _merge_positions
+    if o.merge_positions:
         rows_in = black.numel()
-        merged = merger(black, white, st, out["policy_targets"].contiguous(),
-                        out["value_targets"].reshape(-1).contiguous(), board_size)
+        merged = (_merge_positions if o.merger is None else o.merger)(
+            black, white, st, out["policy_targets"].contiguous(),
+            out["value_targets"].reshape(-1).contiguous(), board_size)
         m = int(merged["m"])
         first = merged["first"][:m].to(black.device, torch.int64)
         black, white, st = (t[first].contiguous() for t in (black, white, st))
-        if symmetries is None and not compact:
-            out["states"] = canonical(black, white, st, board_size)
+        if o.symmetries is None and not o.compact:
+            out["states"] = o.canonical(black, white, st, board_size)
         out["policy_targets"] = merged["policy"][:m]
         out["value_targets"] = merged["value"][:m].reshape(-1, 1)
         out["position_counts"] = merged["count"][:m]
         out["merge_rows"] = torch.tensor(m, dtype=torch.int64, device=black.device)
         out["merge_input_rows"] = torch.tensor(rows_in, dtype=torch.int64, device=black.device)
-    if compact:
+    if o.compact:
         mine = st[:, 0] == 1
         out["mover"] = torch.where(mine, black, white)
         out["opponent"] = torch.where(mine, white, black)
-    if symmetries is not None:
-        if augment is None:
-            def augment(b, w, s, p, sym, bs, all_images):
-                return training_rows(b, w, s, p, sym, bs, all_images, quirk=True)
-        every = symmetries == "all"
+    if o.symmetries is not None:
+        augment = o.augment if o.augment is not None else lambda b, w, s, p, sym, bs, every: (
+            training_rows(b, w, s, p, sym, bs, every, quirk=True))
+        every = o.symmetries == "all"
         sym = None
         if not every:
-            g = torch.Generator().manual_seed(int(symmetry_seed))
+            g = torch.Generator().manual_seed(int(o.symmetry_seed))
             sym = torch.randint(0, 8, (black.numel(),), generator=g,
                                 dtype=torch.int32).to(black.device)
         out["states"], out["policy_targets"], quirk = augment(
             black, white, st, out["policy_targets"].contiguous(), sym, board_size, every)
         if every:
             out["value_targets"] = out["value_targets"].repeat_interleave(8, dim=0)
-            if merge_positions:
+            if o.merge_positions:
                 out["position_counts"] = out["position_counts"].repeat_interleave(8)
         out["symmetry_rows"] = torch.tensor(out["states"].shape[0], dtype=torch.int64,
                                             device=out["states"].device)
@@ -275,40 +311,25 @@ def games_to_training(rows: Dict[str, torch.Tensor], board_size: int = 8, canoni
     rec_white, rec_side, rec_idx), the window records_games cut (rows["src"] indexes it):
     "final_mover" / "final_opponent" per row and "ownership_dropped". Every emitted row belongs
     to a game that ended inside the window, so nothing is dropped unless the window changed."""
-    if symmetries not in (None, "all", "random"):
-        raise ValueError(f"symmetries must be None, 'all' or 'random', not {symmetries!r}")
-    if compact and symmetries is not None:
-        raise ValueError("compact=True leaves the symmetry to the replay buffer's draw: "
-                         f"symmetries must be None, not {symmetries!r}")
-    _check_ownership(ownership, merge_positions, compact)
+    o = _record_options(
+        board_size=board_size, canonical=canonical, exact_endgame=exact_endgame, solver=solver,
+        exact_node_limit=exact_node_limit, exact_wld=exact_wld, exact_policy=exact_policy,
+        moves_solver=moves_solver, symmetries=symmetries, symmetry_seed=symmetry_seed,
+        augment=augment, merge_positions=merge_positions, merger=merger, compact=compact,
+        ownership=ownership, finaler=finaler)
     if ownership and (window is None or len(window) != 4):
         raise ValueError("ownership=True needs window=(rec_black, rec_white, rec_side, rec_idx), "
                          "the records rows was cut from")
-    if canonical is None:
-        canonical = board_canonical
     m = int(rows["m"])
-    fin = None
+    fin = {}
     if ownership:
-        fin = (records_final if finaler is None else finaler)(*window, rows["src"][:m], None,
-                                                              board_size)
-        ok = fin["ok"] != 0
-        fin = {"final_mover": fin["final_mover"][ok], "final_opponent": fin["final_opponent"][ok],
-               "ownership_dropped": (~ok).sum()}
+        ok, fin = o.final_rows(window, rows["src"][:m])
         rows = {k: rows[k][:m][ok] for k in ("mover", "opponent", "policy", "value")}
         m = rows["mover"].numel()
     black, white = rows["mover"][:m].contiguous(), rows["opponent"][:m].contiguous()
-    side = torch.ones(m, dtype=torch.int32, device=black.device)
-    st = torch.stack([side, torch.zeros_like(side), torch.full_like(side, -1),
-                      torch.zeros_like(side)], dim=1).contiguous()
-    states = (canonical(black, white, st, board_size)
-              if symmetries is None and not merge_positions and not compact else None)
-    out = _training_tail(black, white, st, states, rows["policy"][:m],
-                         rows["value"][:m].reshape(-1), board_size, canonical, exact_endgame,
-                         solver, exact_node_limit, exact_wld, exact_policy, moves_solver,
-                         symmetries, symmetry_seed, augment, merge_positions, merger, compact)
-    if fin is not None:
-        out.update(fin)
-    return out
+    st = _status_rows(torch.ones(m, dtype=torch.int32, device=black.device))
+    return {**_training_tail(black, white, st, o.planes_now(black, white, st),
+                             rows["policy"][:m], rows["value"][:m].reshape(-1), o), **fin}
 
 
 def adjudicate(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, board_size: int,
@@ -353,6 +374,31 @@ def adjudicate(black: torch.Tensor, white: torch.Tensor, status: torch.Tensor, b
     return final, over | solved, stats
 
 
+def check_ownership_coef(ownership_coef) -> float:
+    """DDPTrainer's rule for ownership_coef (SelfPlayTrainer checks it too)."""
+    if not is_number(ownership_coef, 0.0, float("inf"), hi_open=True):
+        raise ValueError(f"ownership_coef must be a finite number >= 0, not "
+                         f"{ownership_coef!r}")
+    return float(ownership_coef)
+
+
+def check_policy_target(policy_target, count_weights) -> None:
+    """DDPTrainer's rule for policy_target and count_weights (SelfPlayTrainer checks it too)."""
+    if policy_target not in ("argmax", "full"):
+        raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
+    if count_weights and policy_target != "full":
+        raise ValueError("count_weights=True weights the rows of the full policy loss: "
+                         "policy_target must be 'full'")
+
+
+def _drawn(batch, with_prob: bool, ownership: bool) -> dict:
+    """The outputs of ReplayBuffer.sample by name: prob is there with with_prob=True, ownership
+    and margin with a ReplayBuffer(ownership=True)."""
+    names = ("states", "policy", "value", "slot", "sym") + (("prob",) if with_prob else ()) + \
+        (("ownership", "margin") if ownership else ())
+    return dict(zip(names, batch))
+
+
 class DDPTrainer:
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 1e-4,
                  gradient_clip: float = 1.0, policy_loss_weight: float = 1.0,
@@ -385,26 +431,23 @@ class DDPTrainer:
         loss reads leaves DistributedDataParallel's reducer waiting for its gradient.
         ownership_loss_fn(logits, targets, weights, board_size) -> (loss, stats): default
         rvz.full_ownership_loss."""
-        if isinstance(ownership_coef, bool) or not isinstance(ownership_coef, numbers.Real) or \
-                not 0.0 <= float(ownership_coef) < float("inf"):
-            raise ValueError(f"ownership_coef must be a finite number >= 0, not "
-                             f"{ownership_coef!r}")
-        if (float(ownership_coef) > 0.0) != bool(getattr(model, "ownership_head", False)):
+        self.ownership_coef = check_ownership_coef(ownership_coef)
+        if (self.ownership_coef > 0.0) != bool(getattr(model, "ownership_head", False)):
             raise ValueError("ownership_coef > 0 goes with a model that has the ownership head "
                              "(AlphaZeroNetwork(ownership_head=True)) and 0 with one that has "
                              "none: an unused head breaks DistributedDataParallel's reducer")
-        self.ownership_coef = float(ownership_coef)
         self.ownership_loss_fn = (full_ownership_loss if ownership_loss_fn is None
                                   else ownership_loss_fn)
         self.last_ownership = None  # the (loss, stats) of the last step's ownership term
-        if policy_target not in ("argmax", "full"):
-            raise ValueError(f"policy_target must be 'argmax' or 'full', not {policy_target!r}")
-        if count_weights and policy_target != "full":
-            raise ValueError("count_weights=True weights the rows of the full policy loss: "
-                             "policy_target must be 'full'")
+        check_policy_target(policy_target, count_weights)
         self.policy_target, self.count_weights = policy_target, bool(count_weights)
         self.loss_fn = full_policy_loss if loss_fn is None else loss_fn
         self.last_stats = None      # "full": the stats of the last train_step (0-d tensors)
+        # the loss dict's keys, in the order _step_totals fills its vector
+        self._loss_keys = ("train/loss", "train/policy_loss", "train/value_loss") + \
+            (("train/policy_kl", "train/policy_agreement") if policy_target == "full" else ()) + \
+            (("train/ownership_loss", "train/ownership_agreement")
+             if self.ownership_coef > 0.0 else ())
         self.model = model
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -481,9 +524,10 @@ class DDPTrainer:
         self.opt.step()
         return loss.detach(), policy_loss.detach(), value_loss.detach()
 
-    def _step_totals(self, losses):
-        """The per-step summands of the loss dict: the three losses, and in "full" mode the
-        policy KL and the agreement."""
+    def _step_totals(self, losses, priority=None):
+        """The per-step summands of the loss dict, in the order of its keys: the three losses, in
+        "full" mode the policy KL and the agreement, with ownership_coef > 0 the ownership term's
+        loss and agreement, and `priority`, train_replay's two of a prioritized step."""
         vals = [x.double() for x in losses]
         if self.policy_target == "full":
             st = self.last_stats
@@ -492,23 +536,32 @@ class DDPTrainer:
         if self.ownership_coef > 0.0:
             own_loss, own_stats = self.last_ownership
             vals += [own_loss.double(), own_stats["agreement"].double().to(own_loss.device)]
-        return torch.stack(vals)
+        vals = torch.stack(vals)
+        return vals if priority is None else torch.cat([vals, priority.to(vals.device)])
 
-    def _n_totals(self) -> int:
-        return (5 if self.policy_target == "full" else 3) + 2 * (self.ownership_coef > 0.0)
+    def _loss_dict(self, keys, tot, steps):
+        """The loss dict of `steps` steps: tot holds the mean of each of `keys`."""
+        pairs = [(k, float(x)) for k, x in zip(keys, tot)]
+        return dict(pairs[:3] + [("train/lr", self.opt.param_groups[0]["lr"]), ("steps", steps)] +
+                    pairs[3:])
 
-    def _loss_dict(self, tot, steps):
-        out = {"train/loss": float(tot[0]), "train/policy_loss": float(tot[1]),
-               "train/value_loss": float(tot[2]), "train/lr": self.opt.param_groups[0]["lr"],
-               "steps": steps}
-        if self.policy_target == "full":
-            out["train/policy_kl"] = float(tot[3])
-            out["train/policy_agreement"] = float(tot[4])
-        if self.ownership_coef > 0.0:
-            at = 5 if self.policy_target == "full" else 3
-            out["train/ownership_loss"] = float(tot[at])
-            out["train/ownership_agreement"] = float(tot[at + 1])
-        return out
+    def _min_steps(self, steps: int) -> int:
+        """Every rank must run the same number of DDP steps: the minimum over ranks."""
+        if self.distributed:
+            t = torch.tensor([steps], dtype=torch.int64,
+                             device=self.device if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MIN)
+            steps = int(t.item())
+        return steps
+
+    def _rank_mean(self, tot: torch.Tensor) -> torch.Tensor:
+        """The job's loss: the mean over ranks."""
+        ranks = self.rank_world()[1]
+        if self.distributed and ranks > 1:
+            t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(t)
+            tot = t / ranks
+        return tot
 
     def train_epoch(self, data: Dict[str, torch.Tensor], seed: int = 0,
                     max_steps: Optional[int] = None, local_data: bool = False
@@ -532,7 +585,6 @@ class DDPTrainer:
             raise ValueError("train_epoch: count_weights=True needs data['position_counts'] "
                              "(records_to_training(merge_positions=True))")
         rank, world = self.rank_world()
-        ranks = world
         n = data["states"].shape[0]
         # local data: one stream per (seed, rank) pair, seed * world + rank, so rank r at seed s
         # never repeats rank r + 1's shuffle at seed s - 1 (the pipeline passes seed + iteration)
@@ -548,29 +600,17 @@ class DDPTrainer:
         steps = -(-n // per_step) if partial else n // per_step
         if max_steps is not None:
             steps = min(steps, max_steps)
-        if self.distributed:          # every rank must run the same number of DDP steps
-            t = torch.tensor([steps], dtype=torch.int64,
-                             device=self.device if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            steps = int(t.item())
-        tot = torch.zeros(self._n_totals(), dtype=torch.float64, device=self.device)
+        steps = self._min_steps(steps)
+        tot = torch.zeros(len(self._loss_keys), dtype=torch.float64, device=self.device)
         for s in range(steps):
             idx = order[s * per_step + rank * self.batch_size:
                         s * per_step + (rank + 1) * self.batch_size].to(self.device)
-            if self.count_weights:
-                losses = self.train_step(data["states"][idx], data["policy_targets"][idx],
-                                         data["value_targets"][idx],
-                                         data["position_counts"][idx].to(torch.float32))
-            else:
-                losses = self.train_step(data["states"][idx], data["policy_targets"][idx],
-                                         data["value_targets"][idx])
-            tot += self._step_totals(losses)
+            tot += self._step_totals(self.train_step(
+                data["states"][idx], data["policy_targets"][idx], data["value_targets"][idx],
+                *((data["position_counts"][idx].to(torch.float32),) if self.count_weights
+                  else ())))
         tot /= max(1, steps)
-        if self.distributed and ranks > 1:   # the job's loss: the mean over ranks
-            t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(t)
-            tot = t / ranks
-        return self._loss_dict(tot, steps)
+        return self._loss_dict(self._loss_keys, self._rank_mean(tot), steps)
 
     def train_replay(self, buffer, steps: int, seed: int = 0, symmetries: bool = True,
                      priority_beta: float = 0.4) -> Dict[str, float]:
@@ -608,40 +648,26 @@ class DDPTrainer:
                              "policy_target='full' (the importance weights and the loss rows "
                              "are the full policy loss's)")
         rank, world = self.rank_world()
-        steps = int(steps)
-        if self.distributed:          # every rank must run the same number of DDP steps
-            t = torch.tensor([steps], dtype=torch.int64,
-                             device=self.device if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            steps = int(t.item())
-        tot = torch.zeros(self._n_totals() + 2 * prioritized, dtype=torch.float64,
-                          device=self.device)
+        steps = self._min_steps(int(steps))
+        keys = self._loss_keys + (("train/is_weight_mean", "train/priority_mean") if prioritized
+                                  else ())
+        tot = torch.zeros(len(keys), dtype=torch.float64, device=self.device)
+        with_prob = {"with_prob": True} if prioritized else {}
         for s in range(steps):
+            b = _drawn(buffer.sample(self.batch_size, seed * world + rank, s, symmetries,
+                                     **with_prob), prioritized, own)
+            weights, extras = (), ({"ownership": b["ownership"]} if own else {})
             if prioritized:
-                drawn = buffer.sample(self.batch_size, seed * world + rank, s, symmetries,
-                                      with_prob=True)
-                states, policy, value, slot, _, prob = drawn[:6]
-                weights = buffer.is_weights(prob, slot, priority_beta)
-                losses = self.train_step(states, policy, value, weights, rows=True,
-                                         **({"ownership": drawn[6]} if own else {}))
-                priority, state = buffer.update_priorities(slot, self.last_stats["rows"],
-                                                           self.wp, self.wv)
+                weights = (buffer.is_weights(b["prob"], b["slot"], priority_beta),)
+                extras["rows"] = True
+            losses = self.train_step(b["states"], b["policy"], b["value"], *weights, **extras)
+            priority = None
+            if prioritized:     # the step's loss rows are the drawn rows' new priorities
+                written, state = buffer.update_priorities(b["slot"], self.last_stats["rows"],
+                                                          self.wp, self.wv)
                 valid = (state >= 0).sum().clamp(min=1)
-                extra = torch.stack([weights.double().mean(), priority.double().sum() / valid])
-                tot += torch.cat([self._step_totals(losses), extra.to(tot.device)])
-                continue
-            drawn = buffer.sample(self.batch_size, seed * world + rank, s, symmetries)
-            states, policy, value = drawn[:3]
-            losses = self.train_step(states, policy, value,
-                                     **({"ownership": drawn[5]} if own else {}))
-            tot += self._step_totals(losses)
+                priority = torch.stack([weights[0].double().mean(),
+                                        written.double().sum() / valid])
+            tot += self._step_totals(losses, priority)
         tot /= max(1, steps)
-        if self.distributed and world > 1:   # the job's loss: the mean over ranks
-            t = tot.to(self.device if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(t)
-            tot = t / world
-        out = self._loss_dict(tot, steps)
-        if prioritized:
-            out["train/is_weight_mean"] = float(tot[-2])
-            out["train/priority_mean"] = float(tot[-1])
-        return out
+        return self._loss_dict(keys, self._rank_mean(tot), steps)

@@ -13,6 +13,7 @@ import socket
 import sys
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -100,6 +101,58 @@ def test_records_to_training_equals_selfplay_dicts():
     assert np.array_equal(t["states"].numpy(), st)
     assert np.array_equal(t["policy_targets"].numpy(), pr)
     assert np.array_equal(t["value_targets"].numpy(), va)
+
+
+def test_selfplay_trainer_checks_its_options_before_it_builds_anything(monkeypatch):
+    """Every refused option value or combination is a ValueError raised before SelfPlayTrainer
+    constructs its engine or its evaluator (the rule that needs the evaluator, continuous_plies
+    on a net the h2 kernels do not cover, is the one exception and is not listed)."""
+    _paths()
+    from rvz import pipeline
+    from rvz.network import AlphaZeroNetwork
+
+    def built(*args, **kw):
+        raise AssertionError("constructed before the options were checked")
+    monkeypatch.setattr(pipeline, "Engine", built)
+    monkeypatch.setattr(pipeline, "leaf_evaluator", built)
+    net = AlphaZeroNetwork(8, 1, 16)
+    replay = dict(replay_iterations=2)
+    priority = dict(replay, replay_sampling="priority", policy_target="full")
+    continuous = dict(replay, continuous_plies=8)
+    refused = [dict(ownership_coef=c) for c in (True, -1.0, float("inf"), float("nan"), "1")]
+    refused += [dict(ownership_coef=0.5), dict(replay, ownership_coef=0.5, merge_positions=True),
+                dict(replay, ownership_coef=0.5, adjudicate_empties=4),
+                dict(replay, ownership_coef=0.5)]                # the net has no ownership head
+    refused += [dict(replay_iterations=4, reanalyse_rows=x) for x in (-1, True, 1.5)]
+    refused += [dict(reanalyse_rows=4), dict(replay_iterations=4, reanalyse_age=1),
+                dict(replay_iterations=4, reanalyse_rows=4, reanalyse_age=-1),
+                dict(replay_iterations=2, reanalyse_rows=4, reanalyse_age=1)]
+    refused += [dict(policy_target="soft"), dict(count_weights=True),
+                dict(policy_target="full", count_weights=True),
+                dict(replay, policy_target="full", count_weights=True, merge_positions=True)]
+    refused += [dict(replay_sampling="loss"), dict(replay_sampling="priority", policy_target="full"),
+                dict(replay, replay_sampling="priority"), dict(replay, replay_priority_alpha=0.5),
+                dict(replay, replay_priority_beta=0.5),
+                dict(replay_sampling="counts", merge_positions=True),
+                dict(replay, replay_sampling="counts")]
+    refused += [dict(priority, replay_priority_alpha=a) for a in (1.5, -0.1, True, "0.5")]
+    refused += [dict(priority, replay_priority_beta=b)
+                for b in (1.5, True, "0.4", (0.4, 1.0), (0.4, 1.0, 0), (0.4, 2.0, 3),
+                          (0.4, 1.0, True), (0.4, 1.0, 2.5))]
+    refused += [dict(replay, replay_recency_decay=d) for d in (0.0, 1.5, True, float("nan"))]
+    refused += [dict(replay_recency_decay=0.5)]
+    refused += [dict(replay, continuous_plies=k) for k in (0, True, 2.5)]
+    refused += [dict(continuous_plies=8), dict(continuous, fused=False),
+                dict(continuous, adjudicate_empties=4)]
+    refused += [dict(openings=(1, 2, 3), adjudicate_empties=4), dict(openings=(1, 2)),
+                dict(openings=(1, 2, 3, 4, 5))]
+    refused += [dict(exact_policy=-1), dict(exact_policy=15), dict(symmetries="half"),
+                dict(replay_iterations=-1), dict(replay, symmetries="all"),
+                dict(replay, symmetries="random")]
+    refused += [dict(adjudicate_empties=n) for n in (-1, 15, 60)]
+    for kw in refused:
+        with pytest.raises(ValueError):
+            pipeline.SelfPlayTrainer(net, 4, **kw)
 
 
 def _worker(rank, world, port, q):
