@@ -48,6 +48,9 @@ struct rvz_engine {
     const void* tab_blob = nullptr;   // the weight blob the current generation's rows came from
     // rvz_play_gate: the per-XCD pass gate of the 10x128 k_play form (fraction < 0: the default)
     double gate_frac = -1.0, gate_us = 0.0, gate_late_us = 0.0;
+    // rvz_play_ahead: ahead rows of the 8x8 / 64-filter k_play form (< 0: the default)
+    int ahead = -1;
+    int64_t* ahead_stats = nullptr;   // rvz_play_ahead_stats: device int64 [2], or null
     // the device's g_noise_err word (rvz_dirichlet_noise's exhaustion flag), read by rvz_check
     int32_t* noise_err = nullptr;
     // rvz_env_openings: the engine's copy of the pool (black, white, side, the validation's word)

@@ -64,6 +64,21 @@ int rvz_play_gate(rvz_engine* e, double fraction, double timeout_us, double late
     return RVZ_OK;
 }
 
+int rvz_play_ahead(rvz_engine* e, int32_t mode) {
+    if (!e || mode > 2) {
+        if (e) e->err = "rvz_play_ahead: mode 0, 1 or 2 (< 0: the default)";
+        return RVZ_EINVAL;
+    }
+    e->ahead = mode;
+    return RVZ_OK;
+}
+
+int rvz_play_ahead_stats(rvz_engine* e, int64_t* stats) {
+    if (!e) return RVZ_EINVAL;
+    e->ahead_stats = stats;
+    return RVZ_OK;
+}
+
 int rvz_play_table(rvz_engine* e, int64_t slots, int32_t max_discs) {
     if (!e) return RVZ_EINVAL;
     if (slots != 0 && (slots < 1024 || (slots & (slots - 1)) != 0 || slots > (1ll << 30) ||
@@ -118,9 +133,13 @@ int rvz_play_walk_read(int32_t n_games, uint64_t* out) {
 // 16-byte aligned. First the queue words, zeroed per launch as one run of `queue` words: q_next
 // (the task counter, padded to 4), q_done (one 64-bit {published | claimed} word per group, at
 // most G), the pass gate's words (PlayArgs::gate: 8 XCDs x 128 bytes); then the leaf planes, need,
-// the head-conv rows, logits and value.
+// the head-conv rows, logits and value. The forms with ahead rows (play_ahead_shape: leaves as
+// bitboards, head-conv rows in LDS) use neither x nor work; with ahead rows on they keep two rows
+// per game there instead of one in logits / value: ah_logits [2 G][NPOL] and ah_value [2 G]
+// inside x, the slots' keys ah_key [G][3] (64-bit) inside work.
 struct PlayScratch {
     int64_t q_next, q_done, gate, queue, x, need, work, logits, value, total;
+    int64_t ah_logits, ah_value, ah_key;
 };
 static PlayScratch play_scratch(int64_t G, int NSQ, int NPOL) {
     const auto al4 = [](int64_t n) { return (n + 3) / 4 * 4; };
@@ -137,6 +156,9 @@ static PlayScratch play_scratch(int64_t G, int NSQ, int NPOL) {
     s.logits = take(G * NPOL);
     s.value = take(G);
     s.total = at;
+    s.ah_logits = s.x;
+    s.ah_value = s.x + al4(2 * G * NPOL);
+    s.ah_key = s.work;
     return s;
 }
 int64_t rvz_play_scratch_size(const rvz_engine* e) {
@@ -150,6 +172,10 @@ int64_t rvz_play_scratch_size(const rvz_engine* e) {
 // the pass gate's default (rvz_play_gate; measured on C3, profiles/r06c_gate_ab_*): a round opens
 // when 0.8 of the XCD's running workgroups arrived or 400 us after a waiter's arrival; a workgroup
 // arriving within 200 us of a round's opening joins it at once
+// ahead rows (rvz_play_ahead): the default of the forms that have them
+#ifndef RVZ_PLAY_AHEAD_DEFAULT
+#define RVZ_PLAY_AHEAD_DEFAULT 1
+#endif
 #ifndef RVZ_PLAY_GATE_FRAC
 #define RVZ_PLAY_GATE_FRAC 0.8
 #endif
@@ -170,6 +196,20 @@ static int play_launch(rvz_engine* e, const View& v, const PlayArgs& pa) {
             hipSuccess || cus <= 0)
         cus = 256;
     PlayArgs a = pa;
+    if constexpr (play_ahead_shape<F, T::NB, BS>()) {
+        // two rows per game: the game's own and its ahead slot (row G + g), in the scratch's x
+        // part, which this form does not use (3 NSQ >= 2 NPOL + 4 words per game)
+        static_assert(3 * Geo<BS>::NSQ >= 2 * Geo<BS>::NPOL + 8, "ahead rows fit");
+        if (a.ahead) {
+            const PlayScratch sc = play_scratch(v.G, e->NSQ, e->NPOL);
+            float* scratch = a.x - sc.x;
+            a.logits = scratch + sc.ah_logits;
+            a.value = scratch + sc.ah_value;
+            a.ah_key = reinterpret_cast<uint64_t*>(scratch + sc.ah_key);
+        }
+    } else {
+        a.ahead = 0;
+    }
     const int slots = cus * T::OCC;
     dim3 grid;
     if (a.q_next) {     // queue: one persistent workgroup per resident slot, groups of gpw games
@@ -195,7 +235,7 @@ static int play_launch(rvz_engine* e, const View& v, const PlayArgs& pa) {
 }  // extern "C++"
 
 #ifdef RVZ_PLAY_TIMING
-// tools/exp_play_phases.py: host copy of g_play_t (n workgroups x PLAY_T_SLOTS = 14) and g_pass_t
+// tools/exp_play_phases.py: host copy of g_play_t (n workgroups x PLAY_T_SLOTS = 16) and g_pass_t
 // (n x 6), then zeroed
 int rvz_play_timing_read(uint64_t* host, int n) {
     if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_play_t), (size_t)n * PLAY_T_SLOTS * 8) != hipSuccess)
@@ -322,6 +362,15 @@ int rvz_play(rvz_engine* e, const rvz_play_args* a) {
     pa.unread = reinterpret_cast<unsigned long long*>(a->rows_unread);
     pa.roots_unread = reinterpret_cast<unsigned long long*>(a->roots_unread);
     pa.tstats = reinterpret_cast<unsigned long long*>(a->table_stats);
+    // ahead rows (on for the 8x8 / 64-filter pair shape, the only form that has them;
+    // rvz_play_ahead sets it, RVZ_PLAY_AHEAD overrides: 0 off, 1 fill the empty board slots,
+    // 2 also in place of holding an odd row; the same games with any setting)
+    pa.ahead = e->ahead < 0 ? RVZ_PLAY_AHEAD_DEFAULT : e->ahead;
+    if (const char* ah = getenv("RVZ_PLAY_AHEAD")) pa.ahead = atoi(ah);
+    if (pa.ahead < 0 || pa.ahead > 2 || !pa.single_pass) pa.ahead = 0;   // (the pair shape
+                                       // everywhere is the launch as it was: no ahead rows either)
+    pa.ah_key = nullptr;
+    pa.ah_stats = reinterpret_cast<unsigned long long*>(e->ahead_stats);
     // self-play records
     pa.rec_black = a->rec_black;
     pa.rec_white = a->rec_white;

@@ -94,6 +94,14 @@ struct PlayArgs {
     // whose root has at least E - 1 legal moves is played whole at its first step (forced_search)
     int skip_forced;
     unsigned long long* roots_unread;   // += the root rows those searches left out, or null
+    // ahead rows (rvz_play_ahead; the 8x8 / 64-filter pair shape only, 0: off): a pass left with
+    // an empty board slot evaluates the next row a game of the group will ask for (ahead_child)
+    // into that game's ahead slot: row G + g of logits / value and the key ah_key[3 g ..] =
+    // (P, O, V), valid while the game's PF_AHEAD is set. 2: such a row also takes the place of
+    // holding an odd row back
+    int ahead;
+    uint64_t* ah_key;               // [G][3]
+    unsigned long long* ah_stats;   // += {ahead rows issued, consumed}, or null
 };
 constexpr int PLAY_GPW_MAX = 64;
 // the 8x8 / 64-filter (C2) geometry keeps its head-conv rows in LDS for the FC heads (no
@@ -104,9 +112,17 @@ template <int F, int BS>
 __host__ __device__ constexpr int play_gpw_max() {
     return play_heads_lds<F, BS>() ? 8 : PLAY_GPW_MAX;
 }
+// the forms with ahead rows (PlayArgs::ahead): the 8x8 / 64-filter pair (C2), which reads its
+// leaves as bitboards and keeps its head-conv rows in LDS, so that the scratch's x and work parts
+// are free for the two rows per game (csrc/rvz_play.hip play_launch)
+template <int F, int NBOARD, int BS>
+__host__ __device__ constexpr bool play_ahead_shape() {
+    return NBOARD == 2 && play_heads_lds<F, BS>();
+}
 // game flags: a row queued for the NN, its output ready for the expand, the game's plies done,
-// its row in this cycle's passes, its row held back last cycle (an odd row waits one cycle)
-enum : int { PF_QUEUED = 1, PF_READY = 2, PF_DONE = 4, PF_EVAL = 8, PF_HELD = 16 };
+// its row in this cycle's passes, its row held back last cycle (an odd row waits one cycle), its
+// ahead slot holds a row
+enum : int { PF_QUEUED = 1, PF_READY = 2, PF_DONE = 4, PF_EVAL = 8, PF_HELD = 16, PF_AHEAD = 32 };
 constexpr int32_t ERR_SCHED = 16;   // a queue wait timed out (device error word)
 
 // ---- the cross-game NN-output table (rvz_play_table) ---------------------------------------
@@ -326,6 +342,26 @@ __device__ __forceinline__ void play_gate(unsigned long long* gate, unsigned fra
     }
 }
 
+// The consumer of game g's ahead slot (valid: PF_AHEAD): true when its key is the queued leaf's
+// (P, O, V) = bits[0..2]. Then the slot's row becomes the game's logits / value row, as the FC
+// heads would have written it: an h2 row's outputs depend only on its position, so it is bit for
+// bit the row the leaf's own pass would compute.
+template <int BS>
+__device__ __forceinline__ bool ahead_take(const PlayArgs& a, int G, int g, const uint64_t* bits,
+                                           int lane) {
+    constexpr int NSQ = Geo<BS>::NSQ, NPOL = Geo<BS>::NPOL;
+    const bool ne = lane < 3 && a.ah_key[3 * (size_t)g + lane] != bits[lane];
+    if (__ballot(ne) != 0ull) return false;
+    const float* src = a.logits + (size_t)(G + g) * NPOL;
+    float* row = a.logits + (size_t)g * NPOL;
+    if (lane < NSQ) row[lane] = src[lane];
+    if (lane == 0) {
+        row[NSQ] = src[NSQ];
+        a.value[g] = a.value[G + g];
+    }
+    return true;
+}
+
 struct PlayCtx {
     View v;
     PlayArgs a;
@@ -355,13 +391,17 @@ __device__ __forceinline__ const PlayCtx& play_ctx() {
 // [7] the workgroup's XCC / CU (HW_ID); [8] cycles drawing tasks (queue: the scans of the group
 // words and the waits when nothing was ready), [9] tasks, [10] the launch clock at the
 // workgroup's end (s_memrealtime, 100 MHz), [11] empty scans (nothing ready, plies left), [12] the
-// trunk passes with fewer live boards than NBOARD and [13] their cycles (part of [5] and [1])
+// trunk passes with fewer live boards than NBOARD and [13] their cycles (part of [5] and [1]),
+// [14] the cycles that left a board slot empty or held a row back (an odd row count) and [15]
+// those of them in which a game of the group had an ahead row to offer (ahead_child)
 #ifdef RVZ_PLAY_TIMING
-constexpr int PLAY_T_SLOTS = 14;
+constexpr bool PLAY_TIMED = true;
+constexpr int PLAY_T_SLOTS = 16;
 __device__ unsigned long long g_play_t[16384][PLAY_T_SLOTS];
 #define PT_NOW(t) const unsigned long long t = __builtin_amdgcn_s_memtime()
 #define PT_ADD(i, v) if (tid == 0 && blockIdx.x < 16384) g_play_t[blockIdx.x][i] += (v)
 #else
+constexpr bool PLAY_TIMED = false;
 #define PT_NOW(t)
 #define PT_ADD(i, v)
 #endif
@@ -382,6 +422,8 @@ void k_play(PlayCtx ctx0) {
     constexpr int GMAX = play_gpw_max<F, BS>();
     // the 8x8 / 64-filter pair (C2): a pass with one live board runs at the one-board tile shape
     constexpr bool PLAY_SINGLE = F == 64 && NBOARD == 2 && BS == 8 && (PTW & 1) == 0 && HLDS;
+    // the same shape's ahead rows (PlayArgs::ahead); the other forms carry none of it
+    constexpr bool PLAY_AHEAD = PLAY_SINGLE && play_ahead_shape<F, NBOARD, BS>();
     constexpr int HROW = heads_in_floats(BS) / 16;
     // LDS: the trunk's activation image; between passes its head holds the search phase's act /
     // reset scratch (per wave) or (not HLDS) the FC heads' input rows
@@ -415,10 +457,11 @@ void k_play(PlayCtx ctx0) {
         task_plies = queue ? 1 : c.a.plies;
     }
     bool ovf = false;
-    // the workgroup's rows, table hits, inserts, unread rows and unread root rows, in LDS (no
-    // registers held across the phases)
-    __shared__ unsigned s_cnt[5];
-    if (tid < 5) s_cnt[tid] = 0u;
+    // the workgroup's rows, table hits, inserts, unread rows, unread root rows, ahead rows issued
+    // and consumed, in LDS (no registers held across the phases)
+    constexpr int NCNT = PLAY_AHEAD ? 7 : 5;
+    __shared__ unsigned s_cnt[NCNT];
+    if (tid < NCNT) s_cnt[tid] = 0u;
     if (tid == 0) {
         const PlayArgs& a = play_ctx().a;
         s_tgen = a.tab ? __hip_atomic_load(a.tgen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
@@ -598,6 +641,17 @@ void k_play(PlayCtx ctx0) {
                         if (copies < 0 && k < E && lane == 0) atomicAdd(&s_cnt[3], 1u);
                         // the last batch's row with skip_last: left unevaluated (rvz_search_skip)
                         if (copies > 0 && !(k == E && a.skip_last)) {
+                            // the row an earlier pass took ahead: no new row and no table lookup
+                            // (a table hit stays one row nobody evaluated for this leaf)
+                            if constexpr (PLAY_AHEAD) {
+                                if ((f & PF_AHEAD) &&
+                                    ahead_take<BS>(a, G, g, st_bits + 3 * j, lane)) {
+                                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                                    f = (f & ~PF_AHEAD) | PF_READY;
+                                    if (lane == 0) atomicAdd(&s_cnt[6], 1u);
+                                    continue;
+                                }
+                            }
                             if (a.tab) {   // an earlier evaluation of this position: no new row
                                 const uint64_t P = st_bits[3 * j], O = st_bits[3 * j + 1],
                                                Vb = st_bits[3 * j + 2];
@@ -636,6 +690,7 @@ void k_play(PlayCtx ctx0) {
                                                  a.logits, 1, a.value, a.temperature, nullptr, 1,
                                                  a.out_idx, outp, &over);
                     f &= ~PF_READY;
+                    if constexpr (PLAY_AHEAD) f &= ~PF_AHEAD;   // the root moved: the slot is void
                     // k_autoreset: count the ply; a finished game restarts with its slot's next
                     // seed
                     int64_t sd = 0;
@@ -671,6 +726,32 @@ void k_play(PlayCtx ctx0) {
             PT_NOW(t_c1);
             PT_ADD(0, t_c1 - t_c0);
             PT_ADD(4, 1);
+            // ahead rows: an odd row count leaves a board slot empty (or holds a row back), and
+            // wave 0 looks for a game of the group, queued and with its slot free, that knows the
+            // row it will ask for next (ahead_child), from the last game down: the game whose row
+            // would stand alone first. Only when the slot will be there: a count that holding
+            // makes even needs none, unless the row is to take the place of holding (ahead 2).
+            bool ah_found = false;
+            int ah_j = 0;
+            uint64_t ah_P = 0, ah_O = 0, ah_V = 0;
+            if constexpr (PLAY_AHEAD) {
+                const PlayCtx& c = play_ctx();
+                if (wave == 0 && (c.a.ahead != 0 || PLAY_TIMED)) {
+                    const int lane = opaque_tid() & 63;
+                    const int fj = lane < ng ? st_f[lane] : 0;
+                    const int n = __popcll(__ballot((fj & PF_QUEUED) != 0));
+                    const bool holds = n > NBOARD && __ballot((fj & PF_QUEUED) && !(fj & PF_HELD));
+                    if ((n & 1) && (!holds || c.a.ahead == 2 || PLAY_TIMED)) {
+                        uint64_t cand = __ballot((fj & PF_QUEUED) && !(fj & PF_AHEAD));
+                        while (cand != 0ull && !ah_found) {
+                            ah_j = 63 - __clzll((long long)cand);
+                            cand &= ~(1ull << ah_j);
+                            ah_found = ahead_child<BS>(c.v, g0 + ah_j, st_k[ah_j], E, lane, ah_P,
+                                                       ah_O, ah_V);
+                        }
+                    }
+                }
+            }
             if (tid == 0) {   // the queued rows, in game order
                 int n = 0;
                 for (int j = 0; j < ng; ++j)
@@ -681,6 +762,11 @@ void k_play(PlayCtx ctx0) {
                 // (never holding, now that an odd row's own pass is a one-board pass, measured
                 // 1.0-1.8% behind holding on the 60-ply line: tools/patches/play_no_hold.patch)
                 int hold = n > NBOARD ? n % NBOARD : 0;
+                if constexpr (PLAY_AHEAD) {
+                    PT_ADD(14, n & 1);
+                    PT_ADD(15, (n & 1) && ah_found);
+                    if (ah_found && play_ctx().a.ahead == 2) hold = 0;
+                }
                 for (int j = ng - 1; j >= 0; --j) {
                     const int fj = st_f[j];
                     if (!(fj & PF_QUEUED)) continue;
@@ -699,6 +785,22 @@ void k_play(PlayCtx ctx0) {
                     }
                 for (int i = n; i < n + 16; ++i) q_rows[i] = -1;
                 for (int i = 3 * n; i < 3 * (n + NBOARD); ++i) q_bits[i] = 0;
+                if constexpr (PLAY_AHEAD) {
+                    const PlayArgs& a = play_ctx().a;
+                    if (ah_found && a.ahead != 0 && (n & 1)) {
+                        // the pass's second board: row G + g of logits / value takes its outputs
+                        const int g = g0 + ah_j;
+                        q_bits[3 * n] = ah_P;
+                        q_bits[3 * n + 1] = ah_O;
+                        q_bits[3 * n + 2] = ah_V;
+                        q_rows[n++] = G + g;
+                        a.ah_key[3 * (size_t)g] = ah_P;
+                        a.ah_key[3 * (size_t)g + 1] = ah_O;
+                        a.ah_key[3 * (size_t)g + 2] = ah_V;
+                        st_f[ah_j] |= PF_AHEAD;
+                        s_cnt[5] += 1u;
+                    }
+                }
                 s_nq = n;
             }
             __syncthreads();
@@ -863,6 +965,13 @@ void k_play(PlayCtx ctx0) {
     if (un && tid == 0 && s_cnt[3]) atomicAdd(un, (unsigned long long)s_cnt[3]);
     unsigned long long* ur = play_ctx().a.roots_unread;
     if (ur && tid == 0 && s_cnt[4]) atomicAdd(ur, (unsigned long long)s_cnt[4]);
+    if constexpr (PLAY_AHEAD) {
+        unsigned long long* as = play_ctx().a.ah_stats;
+        if (as && tid == 0 && s_cnt[5]) {
+            atomicAdd(as, (unsigned long long)s_cnt[5]);
+            atomicAdd(as + 1, (unsigned long long)s_cnt[6]);
+        }
+    }
 }
 
 }  // namespace

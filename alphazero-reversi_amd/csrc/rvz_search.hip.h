@@ -763,6 +763,51 @@ __device__ __forceinline__ int select_phase(const View& v, int g, int lane, int 
     return copies;   // the queued copies of the batch's NN row (0: no row; -1: a row left unread)
 }
 
+// k_play's ahead rows: the next NN row game g's search will ask for after the one
+// it has queued, when that is known now. The game has selected batches 0 .. k - 1 of E. With an
+// expanded root of fewer than E - 1 children, batch b = 1 .. nchild goes whole to child b - 1
+// (N == 0 scores inf and select_phase's argmax takes the first, mcts.py:96-97), whatever the
+// earlier children's values were; a child the memo links needs no row (memo_expand_backup) and a
+// terminal one none either, and both take their batch whole. So the row is that of the first
+// child at index >= k - 1 that is unvisited, unlinked and has legal moves: the children's rows are
+// read as select_phase's level reads them, the move and the legal mask are select_phase's leaf
+// code on the root's game. Returns false when there is no such child; else the child's canonical
+// (P, O, V), the key of its row. Nothing is written: a wrong answer costs a row, never a result.
+template <int BS>
+__device__ __forceinline__ bool ahead_child(const View& v, int g, int k, int E, int lane,
+                                            uint64_t& P, uint64_t& O, uint64_t& V) {
+    constexpr int NSQ = Geo<BS>::NSQ;
+    const Node* nodes = v.nodes + (size_t)g * v.M;
+    const uint32_t* meta = v.meta + (size_t)g * v.M;
+    const uint32_t m0 = meta[0];
+    const int nch = m_nchild(m0);
+    if (m_term(m0) || nch == 0 || nch >= E - 1 || k < 1 || k > nch) return false;
+    const int base = 1 + m_block(m0) * NSQ;
+    Node c;
+    uint32_t cm = 0;
+    c.n = 1; c.c = 0.0f;
+    if (lane < nch) {
+        c = nodes[base + lane];
+        cm = meta[base + lane];
+    }
+    const bool fresh = lane < nch && lane >= k - 1 && c.n == 0 &&
+                       !(v.memo && link_ok(__float_as_uint(c.c)));
+    const GameS root = load_game(v, g);
+    if (root.over) return false;
+    for (uint64_t rest = __ballot(fresh); rest != 0ull; rest &= rest - 1ull) {
+        const int ci = __ffsll((unsigned long long)rest) - 1;
+        GameS sim = root;
+        make_move_wave<BS>(sim, m_sq((uint32_t)lane_bcast((int)cm, ci)), lane);
+        V = legal_wave<BS>(mine(sim), theirs(sim), lane);
+        if (V != 0ull) {
+            P = mine(sim);
+            O = theirs(sim);
+            return true;
+        }
+    }
+    return false;
+}
+
 // Dense visit count of square `lane` at the root: the root's children are the set bits of the
 // search root's legal mask in ascending order (expand inserts them row-major).
 template <int BS>

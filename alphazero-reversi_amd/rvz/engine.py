@@ -300,6 +300,10 @@ class Engine:
         if getattr(self, "play_roots_unread", None) is None:
             # root rows play() left out (skip_forced_roots: the forced searches' own roots)
             self.play_roots_unread = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if getattr(self, "play_ahead", None) is None:
+            # {ahead rows evaluated, ahead rows taken} of play() calls (rvz_play_ahead)
+            self.play_ahead = torch.zeros(2, dtype=torch.int64, device=self.device)
+            self._call("rvz_play_ahead_stats", self.play_ahead.data_ptr())
         n = self.lib.rvz_play_scratch_size(self._h)
         sc = getattr(self, "_play_scratch", None)
         if sc is None or sc.numel() < n:
@@ -360,6 +364,7 @@ class Engine:
         n = self.lib.rvz_play_scratch_size(self._h)
         ready = (getattr(self, "play_rows", None) is not None and
                  getattr(self, "play_roots_unread", None) is not None and
+                 getattr(self, "play_ahead", None) is not None and
                  getattr(self, "_play_scratch", None) is not None and
                  self._play_scratch.numel() >= n and getattr(evaluator, "_ovf", None) is not None)
         if not ready:
@@ -382,6 +387,12 @@ class Engine:
                           int(bool(skip_forced_roots)), self.play_roots_unread.data_ptr())
         self._stream()
         self._call("rvz_play", C.byref(a))
+
+    def ahead(self, mode: int = -1):
+        """rvz_play_ahead: ahead rows of play()'s 8x8 / 64-filter form (0: off, 1: fill a pass's
+        empty board slot, 2: also instead of holding an odd row, < 0: the default). The same
+        games with any setting; play_ahead counts {rows evaluated ahead, rows taken}."""
+        self._call("rvz_play_ahead", int(mode))
 
     def _bind(self, evaluator):
         """Remember the evaluator (check() reads its overflow word) and register this engine with

@@ -1187,6 +1187,22 @@ int rvz_play_table(rvz_engine *e, int64_t slots, int32_t max_discs);
  * +10%). The environment
  * variable RVZ_PLAY_GATE="fraction,us[,late_us]" overrides the setting (experiments). */
 int rvz_play_gate(rvz_engine *e, double fraction, double timeout_us, double late_us);
+/* Ahead rows of rvz_play's 8x8 / 64-filter form (two boards per trunk pass). A pass left with one
+ * live board evaluates, in its empty board slot, the row some game of the group will ask for next:
+ * the position of the next unvisited child of an expanded root with fewer legal moves than the
+ * search has batches after the first, to which the next batch goes whole (mcts.py:96-97). The
+ * outputs wait in that game's slot under the position's (mover, opponent, legal-move) bitboards;
+ * the search takes them when it queues a leaf with the same key, instead of a row of its own, and
+ * the slot is dropped when the game moves. A row's outputs depend only on its position, so games,
+ * moves, p and counters are identical with any setting (tests/test_gpu_play_ahead.py); only the
+ * passes change. mode 1 (the default): fill empty board slots; 2: also in place of holding an odd
+ * row back a cycle; 0: off; < 0: the default. The other forms have no ahead rows. The environment
+ * variable RVZ_PLAY_AHEAD overrides the setting (experiments). */
+int rvz_play_ahead(rvz_engine *e, int32_t mode);
+/* The ahead rows' counters: every later rvz_play adds {ahead rows evaluated, ahead rows a search
+ * took} to stats (device int64 [2], kept by the caller; null: not counted, the default).
+ * rows_evaluated counts the former among its rows. */
+int rvz_play_ahead_stats(rvz_engine *e, int64_t *stats);
 
 /* ---- introspection (tests / bench) -------------------------------------------------------- */
 /* Stream-ordered HIP event timer, events without system fence (the engine's own launch timing

@@ -43,12 +43,13 @@ if int(os.environ.get("STAGGER", 1)):      # bench.py's phase stagger (--stagger
 lib = rvz.load()
 lib.rvz_play_timing_read.argtypes = [C.c_void_p, C.c_int]
 n_wg = 16384
-NS = 14                                       # PLAY_T_SLOTS (csrc/rvz_play.hip.h)
+NS = 16                                       # PLAY_T_SLOTS (csrc/rvz_play.hip.h)
 buf = np.zeros((n_wg, NS + 6), dtype=np.uint64)   # [n][NS] phases, then [n][6] pass / heads parts
 for _ in range(WARM):
     run.ply()
 torch.cuda.synchronize()
 lib.rvz_play_timing_read(buf.ctypes.data, n_wg)
+ahead0 = eng.play_ahead.clone()
 t0 = torch.cuda.Event(enable_timing=True)
 t1 = torch.cuda.Event(enable_timing=True)
 t0.record()
@@ -81,6 +82,14 @@ out = {"workgroups": int(used.sum()), "launch_ms": round(ms, 3), "plies": PLIES,
        "rows_per_pass": round(float(b[:, 6].sum() / b[:, 5].sum()), 4),
        "trunk_kcycles_per_pass": round(float(b[:, 1].sum() / b[:, 5].sum()) / 1e3, 2),
        "single_pass": os.environ.get("RVZ_PLAY_SINGLE_PASS", "1") != "0",
+       "ahead": int(os.environ.get("RVZ_PLAY_AHEAD", -1)),
+       # cycles with an odd row count (a one-board pass or a held row) and those of them in which
+       # a game of the group had an ahead row to offer; the ahead rows of the timed launch
+       "odd_cycles": int(b[:, 14].sum()),
+       "odd_cycles_with_an_ahead_row": int(b[:, 15].sum()),
+       "fillable_frac": round(float(b[:, 15].sum() / max(b[:, 14].sum(), 1.0)), 4),
+       "held_rows_per_cycle": round(float((b[:, 14].sum() - n_part) / b[:, 4].sum()), 4),
+       "ahead_rows_issued_taken": (eng.play_ahead - ahead0).tolist(),
        "partial_pass_frac": round(float(n_part / b[:, 5].sum()), 4),
        "partial_pass_cycle_frac_of_trunk": round(float(c_part / b[:, 1].sum()), 4),
        "partial_pass_kcycles": round(float(c_part / max(n_part, 1.0)) / 1e3, 2),
