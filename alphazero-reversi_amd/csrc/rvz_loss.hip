@@ -20,7 +20,7 @@
 //                  lse, then the two gradients, scaled by w / W.
 // No floating-point atomics anywhere; every output element is written by exactly one lane.
 // rvz_ownership_loss (the auxiliary ownership head's loss) runs its own two row kernels around the
-// same k_loss_reduce, on the same scratch.
+// same k_loss_reduce, on the same scratch, and so does rvz_score_loss (the final-score head's loss).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -317,7 +317,202 @@ __global__ __launch_bounds__(LOSS_THREADS) void k_own_grads(
         (float)((w / W) * (2.0 / (double)NSQ) * (th - (double)target[at]) * (1.0 - th * th));
 }
 
+// ---------------------------------------------------------------- the score loss
+// rvz_score_loss: the same three kinds of launch on the same scratch. A row is K = 2 S*S + 1
+// classes, class k the final margin k - S*S. A lane holds CPL consecutive classes (lane l the
+// classes l * CPL .. l * CPL + CPL - 1: 3 a lane on 8x8, 2 on 6x6), so the cumulative distribution
+// is a lane-local running sum on top of one wave scan of the lanes' totals; the strided layout of
+// k_loss_rows would need a scan per slot. The row kernel saves {lse, Qr} in the scratch's aux
+// pair; the gradient kernel recomputes p, C and e from lse by the same device function, so the
+// two agree bit for bit. The terms go into the six arrays of the tree as w, w Lpdf, w Lcdf,
+// w abserr, w agree, malformed, which k_loss_reduce sums and finishes as it is.
+template <int BS>
+struct SG {
+    static constexpr int NSQ = BS * BS;
+    static constexpr int K = 2 * NSQ + 1;
+    static constexpr int CPL = (K + 63) / 64;            // classes a lane holds
+};
+
+// p[i] = exp(z[i] - lse), C[i] = the cumulative sum up to the lane's class i, e[i] = C[i] - T[i]
+// for the thresholds j <= K - 2 and 0 beyond; c: the target class
+template <int BS>
+__device__ __forceinline__ void score_cdf(const float* z, double lse, int c, int lane,
+                                          double* p, double* C, double* e) {
+    constexpr int K = SG<BS>::K, CPL = SG<BS>::CPL;
+    double run = 0.0;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        p[i] = lane * CPL + i < K ? exp((double)z[i] - lse) : 0.0;
+        run = i == 0 ? p[0] : run + p[i];
+        C[i] = run;                                      // the lane's own running sum so far
+    }
+    const double incl = wave_prefix_sum(run, lane);
+    const double below = __shfl_up(incl, 1, 64);
+    const double before = lane == 0 ? 0.0 : below;       // the lanes below this one
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int k = lane * CPL + i;
+        C[i] = before + C[i];
+        e[i] = k <= K - 2 ? C[i] - (k >= c ? 1.0 : 0.0) : 0.0;
+    }
+}
+
+template <int BS>
+__global__ __launch_bounds__(LOSS_THREADS) void k_score_rows(
+    int n, const float* __restrict__ logits, const float* __restrict__ margin,
+    const float* __restrict__ weight, double* __restrict__ aux, double* __restrict__ term,
+    double* __restrict__ out_row) {
+    constexpr int NSQ = SG<BS>::NSQ, K = SG<BS>::K, CPL = SG<BS>::CPL;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int r = blockIdx.x * LOSS_WAVES + wave;        // n * K fits int32
+    if (r >= n) return;                                  // wave-uniform
+    const float* zrow = logits + (size_t)r * K;
+    float z[CPL];
+    bool bad = false;
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int k = lane * CPL + i;
+        const bool in = k < K;
+        z[i] = in ? zrow[k] : -INFINITY;                 // an empty slot: never a maximum, exp 0
+        bad |= in && !finite32(z[i]);
+    }
+    const float mf = margin[r], wf = weight ? weight[r] : 1.0f;
+    bad |= !(mf >= -(float)NSQ && mf <= (float)NSQ) || mf != truncf(mf) ||
+           !(wf >= 0.0f && wf <= FLT_MAX);               // NaN fails the range tests
+    const bool ok = __ballot(bad) == 0;
+
+    double lse = 0.0, Qr = 0.0, Lpdf = 0.0, Lcdf = 0.0, mean = 0.0, abserr = 0.0, w = 0.0,
+           agree = 0.0;
+    if (ok) {                                            // wave-uniform
+        const int c = (int)mf + NSQ;
+        float zm = z[0];
+        int zi = lane * CPL;
+#pragma unroll
+        for (int i = 1; i < CPL; ++i)
+            if (z[i] > zm) { zm = z[i]; zi = lane * CPL + i; }
+        const float mx = wave_reduce(zm, [](float a, float b) { return fmaxf(a, b); });
+        const int zarg = wave_argmax(zm, zi);            // an empty lane holds -inf: never wins
+        const double m = (double)mx;
+        double se = 0.0;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+            if (lane * CPL + i < K) se += exp((double)z[i] - m);
+        lse = m + log(wave_sum(se));
+        double p[CPL], C[CPL], e[CPL];
+        score_cdf<BS>(z, lse, c, lane, p, C, e);
+        double sq = 0.0, q = 0.0, mu = 0.0;
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            sq += e[i] * e[i];
+            q += e[i] * C[i];
+            mu += p[i] * (double)(lane * CPL + i - NSQ);
+        }
+        Lcdf = wave_sum(sq) / (double)(K - 1);
+        Qr = wave_sum(q);
+        mean = wave_sum(mu);
+        Lpdf = lse - (double)zrow[c];                    // 0 <= c < K: the margin is in range
+        abserr = fabs(mean - (double)mf);
+        agree = zarg == c ? 1.0 : 0.0;
+        w = (double)wf;
+    }
+    if (lane == 0) {
+        aux[2 * (size_t)r] = lse;
+        aux[2 * (size_t)r + 1] = Qr;
+        term[r] = w;
+        term[(size_t)n + r] = w * Lpdf;
+        term[2 * (size_t)n + r] = w * Lcdf;
+        term[3 * (size_t)n + r] = w * abserr;
+        term[4 * (size_t)n + r] = w * agree;
+        term[5 * (size_t)n + r] = ok ? 0.0 : 1.0;
+        if (out_row) {
+            out_row[4 * (size_t)r] = Lpdf;
+            out_row[4 * (size_t)r + 1] = Lcdf;
+            out_row[4 * (size_t)r + 2] = mean;
+            out_row[4 * (size_t)r + 3] = agree;
+        }
+    }
+}
+
+template <int BS>
+__global__ __launch_bounds__(LOSS_THREADS) void k_score_grads(
+    int n, const float* __restrict__ logits, const float* __restrict__ margin,
+    const double* __restrict__ aux, const double* __restrict__ term,
+    const double* __restrict__ hdr, double pdf_weight, double cdf_weight,
+    float* __restrict__ grad_logits) {
+    constexpr int NSQ = SG<BS>::NSQ, K = SG<BS>::K, CPL = SG<BS>::CPL;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int r = blockIdx.x * LOSS_WAVES + wave;
+    if (r >= n) return;                                  // wave-uniform
+    const double W = hdr[0], w = term[r];                // w: 0 for a malformed row
+    float* grow = grad_logits + (size_t)r * K;
+    if (!(W > 0.0) || !(w > 0.0)) {                      // wave-uniform: nothing of the row is read
+#pragma unroll
+        for (int i = 0; i < CPL; ++i)
+            if (lane * CPL + i < K) grow[lane * CPL + i] = 0.0f;
+        return;
+    }
+    const double lse = aux[2 * (size_t)r], Qr = aux[2 * (size_t)r + 1];
+    const int c = (int)margin[r] + NSQ;                  // w > 0: the row is well-formed
+    const float* zrow = logits + (size_t)r * K;
+    float z[CPL];
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) z[i] = lane * CPL + i < K ? zrow[lane * CPL + i] : -INFINITY;
+    double p[CPL], C[CPL], e[CPL], R[CPL];
+    score_cdf<BS>(z, lse, c, lane, p, C, e);
+    double run = 0.0;                                    // R: the suffix sums of e, from the top
+#pragma unroll
+    for (int i = CPL - 1; i >= 0; --i) {
+        run = i == CPL - 1 ? e[i] : run + e[i];
+        R[i] = run;
+    }
+    const double incl = wave_suffix_sum(run, lane);
+    const double above = __shfl_down(incl, 1, 64);
+    const double after = lane == 63 ? 0.0 : above;       // the lanes above this one
+    const double cw = cdf_weight * (2.0 / (double)(K - 1));
+#pragma unroll
+    for (int i = 0; i < CPL; ++i) {
+        const int k = lane * CPL + i;
+        if (k < K)
+            grow[k] = (float)((w / W) * (pdf_weight * (p[i] - (k == c ? 1.0 : 0.0)) +
+                                         cw * p[i] * ((after + R[i]) - Qr)));
+    }
+}
+
 }  // namespace
+
+extern "C" int64_t rvz_score_loss_scratch_size(int32_t bs, int32_t n) {
+    if (!board_ok(bs) || n < 0 || (int64_t)n * (2 * bs * bs + 1) > INT32_MAX) return -1;
+    return Layout(bs, n, nullptr).total;                 // the policy loss's scratch, as it is
+}
+
+extern "C" int rvz_score_loss(int32_t bs, int32_t n, const float* logits, const float* margin,
+                              const float* weight, double pdf_weight, double cdf_weight,
+                              void* scratch, double* out_loss, double* out_row,
+                              float* grad_logits, void* stream) {
+    if (rvz_score_loss_scratch_size(bs, n) < 0) return RVZ_EINVAL;
+    if (!(pdf_weight >= 0.0 && pdf_weight <= DBL_MAX) ||
+        !(cdf_weight >= 0.0 && cdf_weight <= DBL_MAX))
+        return RVZ_EINVAL;
+    if (n > 0 && (!logits || !margin || !scratch_ok(scratch) || !out_loss)) return RVZ_EINVAL;
+    if (n == 0) return RVZ_OK;
+    const Layout L(bs, n, scratch);
+    hipStream_t s = (hipStream_t)stream;
+    const Geometry rows = wave_per_row(n, LOSS_WAVES);
+    launch_bs_unchecked(bs, k_score_rows<8>, k_score_rows<6>, rows.grid, rows.block, s, n, logits,
+                        margin, weight, L.aux, L.level[0], out_row);
+    for (int k = 0; k < L.levels; ++k) {
+        double* dst = k + 1 < L.levels ? L.level[k + 1] : nullptr;
+        hipLaunchKernelGGL(k_loss_reduce, dim3(L.count[k + 1]), dim3(RED_THREADS), 0, s,
+                           L.count[k], (const double*)L.level[k], dst, pdf_weight, cdf_weight,
+                           L.hdr, out_loss);
+    }
+    if (!grad_logits) return last_launch();
+    return launch_bs(bs, k_score_grads<8>, k_score_grads<6>, rows.grid, rows.block, s, n, logits,
+                     margin, (const double*)L.aux, (const double*)L.level[0],
+                     (const double*)L.hdr, pdf_weight, cdf_weight, grad_logits);
+}
 
 extern "C" int64_t rvz_ownership_loss_scratch_size(int32_t bs, int32_t n) {
     return Layout(bs, n, nullptr).total;                 // the policy loss's scratch, as it is

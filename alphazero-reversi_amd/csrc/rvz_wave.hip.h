@@ -18,6 +18,29 @@ __device__ __forceinline__ T wave_inclusive_scan(T v, int lane) {
     return v;
 }
 
+// The float64 scans of rvz_score_loss's cumulative distribution. The order is part of the
+// contract, as wave_reduce's is: the steps d = 1, 2, 4, ... 32 in that order, and in each step
+// every lane l >= d (prefix) or l + d < 64 (suffix) computes v = v + (the value lane l - d, or
+// l + d, held before the step); the other lanes keep theirs. wave_prefix_sum: lane l ends with the
+// sum of lanes 0 .. l; wave_suffix_sum: with the sum of lanes l .. 63. The same inputs give the
+// same bits on every call.
+__device__ __forceinline__ double wave_prefix_sum(double v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double up = __shfl_up(v, d, 64);
+        if (lane >= d) v = v + up;
+    }
+    return v;
+}
+__device__ __forceinline__ double wave_suffix_sum(double v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const double down = __shfl_down(v, d, 64);
+        if (lane + d < 64) v = v + down;
+    }
+    return v;
+}
+
 // The xor butterfly: every lane ends with op over the wave's 64 values. The order is part of the
 // contract: d = 32, 16, ... 1, each step x = op(x, lane ^ d's x). rvz_loss.hip's float64 outputs
 // are defined by it and tests/loss_ref.py restates it; op being commutative, the two lanes of a

@@ -45,6 +45,10 @@ Batched core:
                             own symmetries (rvz_replay_ownership; ReplayBuffer(ownership=True)),
                             and the deterministic float64 loss of an ownership head
                             (rvz_ownership_loss); AlphaZeroNetwork(ownership_head=True)
+    score_loss, full_score_loss, differentiable_score   the auxiliary final-score target: the
+                            deterministic float64 loss of a score-distribution head on the final
+                            disc margin a ReplayBuffer(ownership=True) returns with every batch
+                            (rvz_score_loss); AlphaZeroNetwork(score_head=True)
     openings, opening_suite, opening_index   the distinct positions after d plies under the
                             engine's own rules (rvz_openings), the balanced ones among them, and
                             the pool row a seed picks (rvz_opening_index); Engine.openings starts
@@ -59,8 +63,8 @@ from .engine import (AB_HEUR_MAX, AB_MAX_DEPTH, AB_WIN, SOLVE_ABANDONED,  # noqa
                      best_moves, board_apply, board_canonical, board_legal, dirichlet_noise,
                      policy_softmax, solve, solve_moves, solve_moves_wld, solve_window, solve_wld)
 from .game import Board, ReversiGame  # noqa: F401
-from .loss import (full_ownership_loss, full_policy_loss, ownership_loss,  # noqa: F401
-                   policy_value_loss)
+from .loss import (differentiable_score, full_ownership_loss, full_policy_loss,  # noqa: F401
+                   full_score_loss, ownership_loss, policy_value_loss, score_loss)
 from .mcts import MCTS  # noqa: F401
 from .network import (AlphaZeroNetwork, LeafEvaluator, ModuleEvaluator,  # noqa: F401
                       load_reference_state_dict)

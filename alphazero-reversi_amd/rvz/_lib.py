@@ -140,6 +140,9 @@ SIGNATURES = {
                                         C.c_double, _P, _P, _P, _P, _P, _P]),
     "rvz_ownership_loss_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
     "rvz_ownership_loss": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rvz_score_loss_scratch_size": (C.c_int64, [C.c_int32, C.c_int32]),
+    "rvz_score_loss": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_double, C.c_double, _P, _P,
+                                 _P, _P, _P]),
     "rvz_play_scratch_size": (C.c_int64, [_P]),
     "rvz_play": (C.c_int, [_P, _P]),
     "rvz_play_table": (C.c_int, [_P, C.c_int64, C.c_int32]),

@@ -271,3 +271,107 @@ def full_ownership_loss(logits: torch.Tensor, targets: torch.Tensor,
     with respect to logits; stats the 0-d float64 device tensors "agreement", "weight_sum" and
     "malformed". Nothing synchronises with the host."""
     return _full_own(logits, targets, weights, board_size)
+
+
+# ------------------------------------------------------------------ the score loss
+SCORE_LOSS = ("loss", "pdf_loss", "cdf_loss", "abs_error", "weight_sum", "agreement",
+              "malformed")      # out_loss[0 .. 7); out_loss[7] is 0
+
+
+def check_score_loss_args(logits, margin, weights, pdf_weight, cdf_weight, board_size) -> int:
+    """The shape, dtype and weight rules of score_loss, checked before any device call; returns
+    n."""
+    _lib.check_board_size(board_size)
+    k = 2 * board_size * board_size + 1
+    for name, t in (("logits", logits), ("margin", margin)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise RvzError(f"score_loss: {name} must be a float32 tensor")
+    if logits.dim() != 2 or logits.shape[1] != k:
+        raise RvzError(f"score_loss: logits must be [n, {k}]")
+    n = logits.shape[0]
+    if margin.shape != (n,):
+        raise RvzError("score_loss: margin must be [n]")
+    if weights is not None and (not isinstance(weights, torch.Tensor) or
+                                weights.dtype != torch.float32 or weights.shape != (n,)):
+        raise RvzError("score_loss: weights must be None or float32 [n]")
+    if n * k >= 2 ** 31:
+        raise RvzError("score_loss: n * (2*S*S + 1) does not fit int32")
+    for name, x in (("pdf_weight", pdf_weight), ("cdf_weight", cdf_weight)):
+        if not is_number(x, 0.0, math.inf, hi_open=True):
+            raise RvzError(f"score_loss: {name} must be a finite number >= 0, not {x!r}")
+    return n
+
+
+def score_loss(logits: torch.Tensor, margin: torch.Tensor,
+               weights: Optional[torch.Tensor] = None, pdf_weight: float = 1.0,
+               cdf_weight: float = 1.0, board_size: int = 8, rows: bool = False,
+               grads: bool = True) -> Dict[str, torch.Tensor]:
+    """rvz_score_loss: the weighted loss of a final-score head on a batch's final disc margins,
+    with its gradient, in float64 (include/rvz.h has the definition). logits float32
+    [n, 2*S*S+1], class k the margin k - S*S from the mover's side; margin float32 [n]
+    (replay_ownership's, ReplayBuffer(ownership=True).sample's: an integer in [-S*S, S*S]);
+    weights None (every row 1) or float32 [n]; device tensors. Returns a dict of device tensors:
+    "out_loss" float64 [8] and 0-d views of its entries "loss" (pdf_weight * P + cdf_weight * Q),
+    "pdf_loss" P (the cross-entropy of the margin's class), "cdf_loss" Q (the mean squared
+    distance of the cumulative distributions), "abs_error" (the weighted mean of |the
+    distribution's mean - margin|, in discs), "weight_sum" W, "agreement" (the weighted share of
+    rows whose first largest logit is the margin's class) and "malformed" (the rows dropped with
+    weight 0: a non-finite logit, a margin that is no integer in range, a negative or non-finite
+    weight); with rows=True "rows" float64 [n, 4], each row's {Lpdf, Lcdf, mean, agree}; with
+    grads=True "grad_logits" float32 [n, 2*S*S+1], the derivative of "loss". The call runs on the
+    current stream, allocates its scratch and outputs, and never synchronises with the host;
+    n = 0 launches nothing and returns zeros."""
+    n = check_score_loss_args(logits, margin, weights, pdf_weight, cdf_weight, board_size)
+    lib = _lib.load()
+    dev = logits.device
+    z = logits.detach().contiguous()
+    t = margin.detach().to(dev).contiguous()
+    w = None if weights is None else weights.detach().to(dev).contiguous()
+    f64 = {"dtype": torch.float64, "device": dev}
+    out_loss = torch.empty(8, **f64) if n else torch.zeros(8, **f64)
+    out = {"out_loss": out_loss}
+    out.update({name: out_loss[i] for i, name in enumerate(SCORE_LOSS)})
+    if rows:
+        out["rows"] = torch.empty(n, 4, **f64)
+    if grads:
+        out["grad_logits"] = torch.empty(n, logits.shape[1], dtype=torch.float32, device=dev)
+    if n:
+        size = lib.rvz_score_loss_scratch_size(board_size, n)
+        if size < 0:
+            raise RvzError(f"score_loss: no scratch for n = {n}")
+        scratch = torch.empty(size, dtype=torch.uint8, device=dev)
+        check(lib.rvz_score_loss(board_size, n, _addr(z), _addr(t), _addr(w), float(pdf_weight),
+                                 float(cdf_weight), ptr(scratch), _addr(out_loss),
+                                 _addr(out.get("rows")), _addr(out.get("grad_logits")),
+                                 _lib.stream_handle(dev)), None, "rvz_score_loss")
+    return out
+
+
+def differentiable_score(kernel):
+    """A function of full_score_loss's signature around any `kernel` of score_loss's signature
+    and results (tests on a host without a GPU wrap the NumPy reference)."""
+    def loss_fn(logits, margin, weights=None, pdf_weight=1.0, cdf_weight=1.0, board_size=8):
+        holder = {}
+
+        def call(*a, **k):
+            holder["out"] = kernel(*a, **k)
+            return holder["out"]
+        loss = _OwnLoss.apply(logits, call, (margin, weights, pdf_weight, cdf_weight, board_size))
+        out = holder["out"]
+        return loss, {k: out[k] for k in ("pdf_loss", "cdf_loss", "abs_error", "agreement",
+                                          "weight_sum", "malformed")}
+    return loss_fn
+
+
+_full_score = differentiable_score(score_loss)
+
+
+def full_score_loss(logits: torch.Tensor, margin: torch.Tensor,
+                    weights: Optional[torch.Tensor] = None, pdf_weight: float = 1.0,
+                    cdf_weight: float = 1.0, board_size: int = 8):
+    """score_loss as a differentiable torch function (one rvz_score_loss call in the forward,
+    which also computes the gradient; the backward multiplies the saved gradient by the upstream
+    factor). Returns (loss, stats): loss a 0-d tensor of logits' dtype, differentiable with
+    respect to logits; stats the 0-d float64 device tensors "pdf_loss", "cdf_loss", "abs_error",
+    "agreement", "weight_sum" and "malformed". Nothing synchronises with the host."""
+    return _full_score(logits, margin, weights, pdf_weight, cdf_weight, board_size)

@@ -43,10 +43,16 @@ class AlphaZeroNetwork(nn.Module):
     final ownership of the square from the mover's side). forward, the packed parameters and the
     evaluators do not read it: self-play with and without the head is the same computation. It
     is created last, so the other parameters' initial values do not depend on it, and with
-    the head off the state_dict keys are those of before."""
+    the head off the state_dict keys are those of before.
+    score_head=True adds a second training-only head in the same way: score_conv, a 1x1
+    convolution from the trunk output to two planes, ReLU, and score_fc, a linear layer to
+    2*S*S + 1 logits, one per final disc margin -S*S .. S*S from the mover's side (what
+    rvz.score_loss trains); score_fc starts at zero, so a fresh head predicts the uniform
+    distribution. It is created after own_conv, so every other initial value, own_conv's
+    included, is that of a net without it."""
 
     def __init__(self, board_size: int = 8, num_res_blocks: int = 5, num_filters: int = 128,
-                 ownership_head: bool = False):
+                 ownership_head: bool = False, score_head: bool = False):
         super().__init__()
         self.board_size = board_size
         self.num_filters = num_filters
@@ -67,6 +73,16 @@ class AlphaZeroNetwork(nn.Module):
             self.own_conv = nn.Conv2d(num_filters, 1, 1)
             nn.init.kaiming_normal_(self.own_conv.weight, mode="fan_out", nonlinearity="relu")
             nn.init.zeros_(self.own_conv.bias)
+        self.score_head = bool(score_head)
+        if self.score_head:                         # after own_conv: its values do not move either
+            self.score_conv = nn.Conv2d(num_filters, 2, 1)
+            self.score_fc = nn.Linear(2 * cells, 2 * cells + 1)
+            nn.init.kaiming_normal_(self.score_conv.weight, mode="fan_out", nonlinearity="relu")
+            nn.init.zeros_(self.score_conv.bias)
+            # the output layer starts at 0: a fresh head predicts the uniform distribution (loss
+            # log K), whatever the scale of the trunk's activations, and not a confident wrong one
+            nn.init.zeros_(self.score_fc.weight)
+            nn.init.zeros_(self.score_fc.bias)
 
     def reset_parameters(self):
         """Kaiming-normal fan-out for conv/linear weights, BN affine = (1, 0) (network.py:71-78)."""
@@ -91,17 +107,25 @@ class AlphaZeroNetwork(nn.Module):
         return self.policy_fc(pol), val.squeeze(1)
 
     def forward(self, x, aux: bool = False):
-        """(policy logits, value); with aux=True forward_aux's three outputs (the form a
+        """(policy logits, value); with aux=True forward_aux's outputs (the form a
         DistributedDataParallel wrapper, which only forwards `forward`, is called in)."""
         h = self.trunk(x)
         if not aux:
             return self._heads(h)
-        if not self.ownership_head:
-            raise ValueError("forward_aux needs AlphaZeroNetwork(ownership_head=True)")
-        return (*self._heads(h), self.own_conv(h).reshape(h.shape[0], -1))
+        if not (self.ownership_head or self.score_head):
+            raise ValueError("forward_aux needs AlphaZeroNetwork(ownership_head=True) or "
+                             "AlphaZeroNetwork(score_head=True)")
+        n = h.shape[0]
+        out = self._heads(h)
+        if self.ownership_head:
+            out = (*out, self.own_conv(h).reshape(n, -1))
+        if self.score_head:
+            out = (*out, self.score_fc(F.relu(self.score_conv(h)).reshape(n, -1)))
+        return out
 
-    def forward_aux(self, x) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        """(policy logits, value, ownership logits [n, S*S]); needs ownership_head=True."""
+    def forward_aux(self, x) -> Tuple[torch.Tensor, ...]:
+        """(policy logits, value), then the ownership logits [n, S*S] with ownership_head=True,
+        then the score logits [n, 2*S*S+1] with score_head=True; needs one of the two heads."""
         return self.forward(x, aux=True)
 
     def predict(self, board_state, valid_moves=None):

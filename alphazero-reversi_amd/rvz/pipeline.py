@@ -33,19 +33,19 @@ from .records import records_games
 from .replay import ReplayBuffer, check_recency_decay
 from .selfplay import SelfPlayRunner
 from .trainer import (DDPTrainer, adjudicate, check_ownership_coef, check_policy_target,
-                      games_to_training, records_to_training)
+                      check_score_coef, games_to_training, records_to_training)
 
 
 def _check_options(board_size: int, *, fused, exact_policy, adjudicate_empties, symmetries,
                    merge_positions, replay_iterations, policy_target, count_weights,
                    replay_sampling, replay_recency_decay, replay_priority_alpha,
                    replay_priority_beta, continuous_plies, openings, reanalyse_rows,
-                   reanalyse_age, ownership_coef) -> tuple:
+                   reanalyse_age, ownership_coef, score_coef) -> tuple:
     """SelfPlayTrainer's option rules (its docstring has what each option means): ValueError for
     every refused value or combination, before a model, a device or the library is touched.
     Returns the options it converts, normalised: (ownership_coef, reanalyse_rows, reanalyse_age,
     replay_priority_beta, replay_recency_decay, continuous_plies, exact_policy,
-    replay_iterations, adjudicate_empties)."""
+    replay_iterations, adjudicate_empties, score_coef)."""
     def unit(x):
         return is_number(x, 0.0, 1.0)
     ownership_coef = check_ownership_coef(ownership_coef)
@@ -58,6 +58,17 @@ def _check_options(board_size: int, *, fused, exact_policy, adjudicate_empties, 
                              "merge_positions must be False")
         if adjudicate_empties:
             raise ValueError("ownership_coef > 0 needs every game played to its end: "
+                             "adjudicate_empties must be 0")
+    score_coef = check_score_coef(score_coef)
+    if score_coef > 0.0:                        # the margin comes with the final position
+        if not replay_iterations or replay_iterations < 1:
+            raise ValueError("score_coef > 0 needs replay_iterations >= 1: the final positions "
+                             "are held by the replay buffer")
+        if merge_positions:
+            raise ValueError("score_coef > 0 keeps one final position per row: "
+                             "merge_positions must be False")
+        if adjudicate_empties:
+            raise ValueError("score_coef > 0 needs every game played to its end: "
                              "adjudicate_empties must be 0")
     for name, x in (("reanalyse_rows", reanalyse_rows), ("reanalyse_age", reanalyse_age)):
         if not is_int(x) or x < 0:
@@ -154,7 +165,7 @@ def _check_options(board_size: int, *, fused, exact_policy, adjudicate_empties, 
                          f"below {max_plies}")
     return (ownership_coef, int(reanalyse_rows), int(reanalyse_age), beta,
             float(replay_recency_decay), continuous_plies, exact_policy, replay_iterations,
-            adjudicate_empties)
+            adjudicate_empties, score_coef)
 
 
 # the 0-d counters of generate()'s data that run_iteration reports (0 where an option is off)
@@ -182,8 +193,19 @@ class SelfPlayTrainer:
                  replay_sampling: str = "uniform", replay_recency_decay: float = 1.0,
                  replay_priority_alpha: float = 0.6, replay_priority_beta=0.4,
                  continuous_plies: Optional[int] = None, openings=None,
-                 reanalyse_rows: int = 0, reanalyse_age: int = 0, ownership_coef: float = 0.0):
-        """ownership_coef: 0 (off: the code and the keys of before) or c > 0: the auxiliary
+                 reanalyse_rows: int = 0, reanalyse_age: int = 0, ownership_coef: float = 0.0,
+                 score_coef: float = 0.0):
+        """score_coef: 0 (off: the code and the keys of before) or c > 0: the auxiliary
+        final-score target, independent of ownership_coef and under its rules. The model has the
+        score head (AlphaZeroNetwork(score_head=True); ValueError otherwise, as DDPTrainer's);
+        the data path carries the final positions as it does for ownership_coef > 0 (either
+        coefficient asks for them), and every training step adds c times the head's loss on the
+        drawn rows' final disc margins (DDPTrainer(score_coef=c), rvz.full_score_loss); the loss
+        dict gains "train/score_loss", "train/score_pdf", "train/score_cdf",
+        "train/score_abs_error" and "train/score_agreement", and run_iteration
+        "ownership_dropped". Self-play does not read the head. ValueError without
+        replay_iterations >= 1, with merge_positions or with adjudicate_empties > 0.
+        ownership_coef: 0 (off: the code and the keys of before) or c > 0: the auxiliary
         final-ownership target. The model has the ownership head
         (AlphaZeroNetwork(ownership_head=True); ValueError otherwise, as DDPTrainer's); every
         compact row carries the final position of its game from its mover's side
@@ -339,7 +361,7 @@ class SelfPlayTrainer:
         bs = int(getattr(model, "board_size", 8))
         (self.ownership_coef, self.reanalyse_rows, self.reanalyse_age, self.replay_priority_beta,
          self.replay_recency_decay, self.continuous_plies, self.exact_policy,
-         self.replay_iterations, self.adjudicate_empties) = _check_options(
+         self.replay_iterations, self.adjudicate_empties, self.score_coef) = _check_options(
             bs, fused=fused, exact_policy=exact_policy, adjudicate_empties=adjudicate_empties,
             symmetries=symmetries, merge_positions=merge_positions,
             replay_iterations=replay_iterations, policy_target=policy_target,
@@ -348,7 +370,9 @@ class SelfPlayTrainer:
             replay_priority_alpha=replay_priority_alpha,
             replay_priority_beta=replay_priority_beta, continuous_plies=continuous_plies,
             openings=openings, reanalyse_rows=reanalyse_rows, reanalyse_age=reanalyse_age,
-            ownership_coef=ownership_coef)
+            ownership_coef=ownership_coef, score_coef=score_coef)
+        # the rows carry their games' final positions when either auxiliary target is on
+        self.final_positions = self.ownership_coef > 0.0 or self.score_coef > 0.0
         self.model = model.eval()
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -368,7 +392,8 @@ class SelfPlayTrainer:
                                   lr_milestones=lr_milestones, lr_gamma=lr_gamma,
                                   policy_target=policy_target,
                                   count_weights=bool(count_weights),
-                                  ownership_coef=self.ownership_coef)
+                                  ownership_coef=self.ownership_coef,
+                                  score_coef=self.score_coef)
         # the h2 kernels when they cover the net, else the module itself on the GPU
         # (ModuleEvaluator: pull-style, eager plies; it reads the live module, so refresh() only
         # drops the memo)
@@ -420,7 +445,7 @@ class SelfPlayTrainer:
             self.buffer = ReplayBuffer(int(replay_capacity), bs, self.device,
                                        window_iterations=self.replay_iterations, **draw,
                                        stamps=bool(self.reanalyse_rows),
-                                       ownership=self.ownership_coef > 0.0)
+                                       ownership=self.final_positions)
         if self.reanalyse_rows:
             # the re-search's own engine: the plain search, whatever self-play's engine has set
             self.reanalyse_eng = Engine(games, num_simulations, batch_size, c_puct, board_size=bs,
@@ -444,7 +469,7 @@ class SelfPlayTrainer:
         return {"exact_endgame": self.exact_endgame, "exact_node_limit": self.exact_node_limit,
                 "exact_wld": self.exact_wld, "exact_policy": self.exact_policy,
                 **self._symmetry_args(), "merge_positions": self.merge_positions,
-                "compact": bool(self.replay_iterations), "ownership": self.ownership_coef > 0.0}
+                "compact": bool(self.replay_iterations), "ownership": self.final_positions}
 
     def generate(self) -> Dict[str, torch.Tensor]:
         """One iteration's self-play: every game of this rank from the start to its end.
@@ -524,7 +549,7 @@ class SelfPlayTrainer:
         counts = ({"weight": data["position_counts"].to(torch.float32)}
                   if self.replay_sampling == "counts" else {})
         own = ({"final_mover": data["final_mover"], "final_opponent": data["final_opponent"]}
-               if "final_mover" in data else {})       # ownership_coef > 0
+               if "final_mover" in data else {})       # ownership_coef or score_coef > 0
         self.buffer.append(data["mover"], data["opponent"], data["policy_targets"],
                            data["value_targets"], self.iteration, **counts, **own)
 
@@ -611,7 +636,7 @@ class SelfPlayTrainer:
                     "replay_rows": len(self.buffer) if self.buffer is not None else 0,
                     "replay_iterations_held": (len(self.buffer.rows_by_iteration())
                                                if self.buffer is not None else 0)})
-        if self.ownership_coef > 0.0:
+        if self.final_positions:
             out["ownership_dropped"] = int(data["ownership_dropped"])
         if self.replay_sampling == "priority":
             out["replay_priority_max"] = self.buffer.max_priority()

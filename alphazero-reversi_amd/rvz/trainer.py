@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from ._lib import is_number
 from .engine import (SOLVE_ABANDONED, SOLVE_MAX_EMPTIES, best_moves, board_canonical, solve,
                      solve_moves, solve_moves_wld, solve_wld)
-from .loss import full_ownership_loss, full_policy_loss
+from .loss import full_ownership_loss, full_policy_loss, full_score_loss
 from .records import merge_positions as _merge_positions, records_final, training_rows
 
 
@@ -382,6 +382,13 @@ def check_ownership_coef(ownership_coef) -> float:
     return float(ownership_coef)
 
 
+def check_score_coef(score_coef) -> float:
+    """DDPTrainer's rule for score_coef (SelfPlayTrainer checks it too)."""
+    if not is_number(score_coef, 0.0, float("inf"), hi_open=True):
+        raise ValueError(f"score_coef must be a finite number >= 0, not {score_coef!r}")
+    return float(score_coef)
+
+
 def check_policy_target(policy_target, count_weights) -> None:
     """DDPTrainer's rule for policy_target and count_weights (SelfPlayTrainer checks it too)."""
     if policy_target not in ("argmax", "full"):
@@ -405,7 +412,8 @@ class DDPTrainer:
                  value_loss_weight: float = 1.0, batch_size: int = 64, bucket_cap_mb: int = 25,
                  lr_milestones=(), lr_gamma: float = 0.1, policy_target: str = "argmax",
                  count_weights: bool = False, loss_fn=None, ownership_coef: float = 0.0,
-                 ownership_loss_fn=None):
+                 ownership_loss_fn=None, score_coef: float = 0.0,
+                 score_weights=(1.0, 1.0), score_loss_fn=None):
         """Defaults = the reference's TrainingConfig (config.py:46-60): AdamW(lr 1e-3, weight decay
         1e-4), clip 1.0, loss weights 1, batch 64, MultiStepLR(milestones [], gamma 0.1)
         (pipeline.py:91-105), stepped once per iteration (scheduler_step, pipeline.py:131).
@@ -430,7 +438,32 @@ class DDPTrainer:
         the head (AlphaZeroNetwork(ownership_head=True)), ValueError otherwise: a head that no
         loss reads leaves DistributedDataParallel's reducer waiting for its gradient.
         ownership_loss_fn(logits, targets, weights, board_size) -> (loss, stats): default
-        rvz.full_ownership_loss."""
+        rvz.full_ownership_loss.
+        score_coef = c > 0 (0, the default, is off: the steps and the loss dict of before):
+        train_replay, on a ReplayBuffer(ownership=True), adds c * L_score to every step's loss,
+        L_score = score_weights[0] * P + score_weights[1] * Q the score head's loss on the drawn
+        rows' final disc margins: P the cross-entropy of the margin's class, Q the squared
+        distance of the cumulative distributions (rvz.full_score_loss; the rvz_score_loss HIP
+        kernels, float64, deterministic), with the rows' weights of the policy term. The loss
+        dict then gains "train/score_loss", "train/score_pdf", "train/score_cdf",
+        "train/score_abs_error" (the mean distance, in discs, of the predicted mean margin from
+        the game's) and "train/score_agreement". c > 0 exactly when the model has the head
+        (AlphaZeroNetwork(score_head=True)), ValueError otherwise, for ownership_coef's reason.
+        The two coefficients are independent of each other.
+        score_loss_fn(logits, margin, weights, pdf_weight, cdf_weight, board_size) ->
+        (loss, stats): default rvz.full_score_loss."""
+        self.score_coef = check_score_coef(score_coef)
+        if (self.score_coef > 0.0) != bool(getattr(model, "score_head", False)):
+            raise ValueError("score_coef > 0 goes with a model that has the score head "
+                             "(AlphaZeroNetwork(score_head=True)) and 0 with one that has "
+                             "none: an unused head breaks DistributedDataParallel's reducer")
+        if (not isinstance(score_weights, (tuple, list)) or len(score_weights) != 2 or
+                not all(is_number(x, 0.0, float("inf"), hi_open=True) for x in score_weights)):
+            raise ValueError("score_weights must be two finite numbers >= 0 (pdf, cdf), not "
+                             f"{score_weights!r}")
+        self.score_weights = (float(score_weights[0]), float(score_weights[1]))
+        self.score_loss_fn = full_score_loss if score_loss_fn is None else score_loss_fn
+        self.last_score = None      # the (loss, stats) of the last step's score term
         self.ownership_coef = check_ownership_coef(ownership_coef)
         if (self.ownership_coef > 0.0) != bool(getattr(model, "ownership_head", False)):
             raise ValueError("ownership_coef > 0 goes with a model that has the ownership head "
@@ -447,7 +480,9 @@ class DDPTrainer:
         self._loss_keys = ("train/loss", "train/policy_loss", "train/value_loss") + \
             (("train/policy_kl", "train/policy_agreement") if policy_target == "full" else ()) + \
             (("train/ownership_loss", "train/ownership_agreement")
-             if self.ownership_coef > 0.0 else ())
+             if self.ownership_coef > 0.0 else ()) + \
+            (("train/score_loss", "train/score_pdf", "train/score_cdf", "train/score_abs_error",
+              "train/score_agreement") if self.score_coef > 0.0 else ())
         self.model = model
         self.device = next(model.parameters()).device
         self.distributed = dist.is_available() and dist.is_initialized()
@@ -483,23 +518,31 @@ class DDPTrainer:
         return (dist.get_rank(), dist.get_world_size()) if self.distributed else (0, 1)
 
     def train_step(self, states, policy_targets, value_targets, weights=None, rows=False,
-                   ownership=None):
+                   ownership=None, margin=None):
         """One optimizer step (pipeline.py:297-340); returns (loss, policy_loss, value_loss).
         weights (policy_target="full" only): float32 [n], each row's weight in the batch's mean;
         None weights every row 1. In "full" mode last_stats holds the step's loss_fn stats; with
         rows=True ("full" only) loss_fn is asked for its per-row losses, last_stats["rows"].
         ownership (ownership_coef > 0 only, and required then): float32 [n, S*S], the rows'
         final-ownership targets; ownership_coef times the head's loss on them, under the same
-        weights, is added to the loss, and last_ownership holds that term's (loss, stats)."""
+        weights, is added to the loss, and last_ownership holds that term's (loss, stats).
+        margin (score_coef > 0 only, and required then): float32 [n], the rows' final disc
+        margins; score_coef times the score head's loss on them, under the same weights, is
+        added to the loss, and last_score holds that term's (loss, stats)."""
         if (weights is not None or rows) and self.policy_target != "full":
             raise ValueError("train_step: weights and rows need policy_target='full'")
         if (ownership is not None) != (self.ownership_coef > 0.0):
             raise ValueError("train_step: ownership targets go with ownership_coef > 0 (they "
                              "come from train_replay on a ReplayBuffer(ownership=True))")
+        if (margin is not None) != (self.score_coef > 0.0):
+            raise ValueError("train_step: margin goes with score_coef > 0 (it comes from "
+                             "train_replay on a ReplayBuffer(ownership=True))")
         self.net.train()
         self.opt.zero_grad()
-        if ownership is not None:
-            logits, value, own_logits = self.net(states, aux=True)
+        if ownership is not None or margin is not None:
+            logits, value, *aux = self.net(states, aux=True)     # ownership, then score
+            own_logits = aux[0] if ownership is not None else None
+            score_logits = aux[-1] if margin is not None else None
         else:
             logits, value = self.net(states)
         if self.policy_target == "full":
@@ -518,6 +561,12 @@ class DDPTrainer:
             own_loss, own_stats = self.ownership_loss_fn(own_logits, ownership, weights, board)
             self.last_ownership = (own_loss.detach(), own_stats)
             loss = loss + self.ownership_coef * own_loss
+        if margin is not None:
+            board = int(getattr(self.model, "board_size", 8))
+            score_loss, score_stats = self.score_loss_fn(
+                score_logits, margin, weights, *self.score_weights, board)
+            self.last_score = (score_loss.detach(), score_stats)
+            loss = loss + self.score_coef * score_loss
         loss.backward()                      # DDP: bucketed RCCL all-reduce during backward
         if self.clip > 0:
             torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
@@ -527,7 +576,8 @@ class DDPTrainer:
     def _step_totals(self, losses, priority=None):
         """The per-step summands of the loss dict, in the order of its keys: the three losses, in
         "full" mode the policy KL and the agreement, with ownership_coef > 0 the ownership term's
-        loss and agreement, and `priority`, train_replay's two of a prioritized step."""
+        loss and agreement, with score_coef > 0 the score term's five, and `priority`,
+        train_replay's two of a prioritized step."""
         vals = [x.double() for x in losses]
         if self.policy_target == "full":
             st = self.last_stats
@@ -536,6 +586,10 @@ class DDPTrainer:
         if self.ownership_coef > 0.0:
             own_loss, own_stats = self.last_ownership
             vals += [own_loss.double(), own_stats["agreement"].double().to(own_loss.device)]
+        if self.score_coef > 0.0:
+            score_loss, st = self.last_score
+            vals += [score_loss.double()] + [st[k].double().to(score_loss.device) for k in
+                                             ("pdf_loss", "cdf_loss", "abs_error", "agreement")]
         vals = torch.stack(vals)
         return vals if priority is None else torch.cat([vals, priority.to(vals.device)])
 
@@ -581,6 +635,9 @@ class DDPTrainer:
         if self.ownership_coef > 0.0:
             raise ValueError("train_epoch: ownership_coef > 0 trains through train_replay (the "
                              "ownership targets are a ReplayBuffer(ownership=True)'s)")
+        if self.score_coef > 0.0:
+            raise ValueError("train_epoch: score_coef > 0 trains through train_replay (the "
+                             "margins are a ReplayBuffer(ownership=True)'s)")
         if self.count_weights and "position_counts" not in data:
             raise ValueError("train_epoch: count_weights=True needs data['position_counts'] "
                              "(records_to_training(merge_positions=True))")
@@ -637,12 +694,16 @@ class DDPTrainer:
         With ownership_coef > 0 the buffer is a ReplayBuffer(ownership=True) (ValueError
         otherwise, and for such a buffer with ownership_coef = 0, whose sample has two outputs
         more): every step also draws the rows' ownership targets and adds the head's loss on them
-        (train_step's `ownership`), under the importance weights where there are any."""
+        (train_step's `ownership`), under the importance weights where there are any.
+        score_coef > 0 needs the same buffer, the ring that holds the final positions (the two
+        coefficients are independent: the buffer goes with either being positive), and every
+        step adds the score head's loss on the drawn rows' margins (train_step's `margin`)."""
         prioritized = bool(getattr(buffer, "prioritized", False))
-        own = self.ownership_coef > 0.0
-        if own != bool(getattr(buffer, "ownership", False)):
-            raise ValueError("train_replay: ownership_coef > 0 goes with a "
-                             "ReplayBuffer(ownership=True), and 0 with one without")
+        own, score = self.ownership_coef > 0.0, self.score_coef > 0.0
+        final = own or score                             # the draw has ownership and margin
+        if final != bool(getattr(buffer, "ownership", False)):
+            raise ValueError("train_replay: ownership_coef > 0 or score_coef > 0 goes with a "
+                             "ReplayBuffer(ownership=True), and both 0 with one without")
         if prioritized and self.policy_target != "full":
             raise ValueError("train_replay: a ReplayBuffer(prioritized=True) needs "
                              "policy_target='full' (the importance weights and the loss rows "
@@ -655,8 +716,10 @@ class DDPTrainer:
         with_prob = {"with_prob": True} if prioritized else {}
         for s in range(steps):
             b = _drawn(buffer.sample(self.batch_size, seed * world + rank, s, symmetries,
-                                     **with_prob), prioritized, own)
+                                     **with_prob), prioritized, final)
             weights, extras = (), ({"ownership": b["ownership"]} if own else {})
+            if score:
+                extras["margin"] = b["margin"]
             if prioritized:
                 weights = (buffer.is_weights(b["prob"], b["slot"], priority_beta),)
                 extras["rows"] = True

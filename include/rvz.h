@@ -1086,6 +1086,62 @@ int rvz_ownership_loss(int32_t board_size, int32_t n, const float *logits /* [n]
                        double *out_row /* [n][2], nullable */,
                        float *grad_logits /* [n][S*S], nullable */, void *hip_stream);
 
+/* rvz_score_loss (csrc/rvz_loss.hip): the loss of an auxiliary final-score head against
+ * rvz_replay_ownership's out_margin, on rvz_policy_value_loss's cross-row tree and scratch, with
+ * its weighting, normalisation, determinism and float64 arithmetic (IEEE, no contraction, on the
+ * float32 inputs). The head gives one logit per final disc margin: K = 2 S*S + 1 classes, class k
+ * the margin k - S*S from the mover's side. With z = logits and c = (int) margin + S*S, per row r:
+ *   m = max_k z[k]                     lse = m + log sum_k exp(z[k] - m)
+ *   p[k] = exp(z[k] - lse)
+ *   Lpdf = lse - z[c]                  (the difference, not -log p[c]: finite where p[c] underflows)
+ *   C[j] = sum_{i <= j} p[i]           T[j] = 1 if j >= c else 0
+ *   e[j] = C[j] - T[j]                 for the thresholds j = 0 .. K-2 (e[K-1] is identically 0
+ *                                      and is left out)
+ *   Lcdf = (1 / (K-1)) * sum_{j <= K-2} e[j]^2
+ *   mean = sum_k p[k] * (k - S*S)      abserr = |mean - margin|
+ *   agree = 1 if the first maximum of z is c, else 0
+ *   w = weight[r], or 1 with a null weight
+ * Lpdf is the cross-entropy of the score distribution; Lcdf, the squared distance of the two
+ * cumulative distributions, is what tells a miss by 2 discs from a miss by 40.
+ * A row is malformed if a logit is not finite, margin is not an integer in [-S*S, S*S], or its
+ * weight is negative or not finite (NaN fails each test): it gets w = 0, a zero out_row, a zero
+ * gradient, and is counted. Rows are checked in the kernel, no host synchronisation.
+ *   W = sum_r w        P = sum_r w Lpdf / W        Q = sum_r w Lcdf / W
+ *   out_loss = { pdf_weight * P + cdf_weight * Q, P, Q, sum_r w abserr / W, W,
+ *                sum_r w agree / W, malformed rows, 0 }
+ *   out_row[r] = { Lpdf, Lcdf, mean, agree }
+ *   grad_logits[r][k] = (float) ((w / W) * (pdf_weight * (p[k] - [k == c])
+ *                                           + cdf_weight * (2 / (K-1)) * p[k] * (R[k] - Qr)))
+ *   R[k] = sum_{j = k}^{K-2} e[j]  (R[K-1] = 0)        Qr = sum_{j <= K-2} e[j] * C[j]
+ * the derivative of out_loss[0] with respect to z: dLpdf/dz[k] = p[k] - [k == c] as for any
+ * softmax cross-entropy, and with dp[i]/dz[k] = p[i] ([i == k] - p[k]),
+ *   dC[j]/dz[k] = sum_{i <= j} p[i] ([i == k] - p[k]) = p[k] ([k <= j] - C[j])
+ *   dLcdf/dz[k] = (2 / (K-1)) sum_j e[j] p[k] ([k <= j] - C[j]) = (2 / (K-1)) p[k] (R[k] - Qr).
+ * With W == 0 every mean and every gradient is 0; no NaN is written anywhere.
+ * Sums: one wavefront holds a row, lane l the CPL = ceil(K / 64) consecutive classes l * CPL ..
+ * l * CPL + CPL - 1 (3 a lane on 8x8, 2 on 6x6). C is the lane's own running sum, lowest class
+ * first, added to the sum of the lanes below it, which a fixed float64 scan over the lanes' totals
+ * gives (steps d = 1, 2, ... 32, lane l adding lane l - d's value); R is the mirror image from the
+ * top. A row's scalar sums are the lane's terms added lowest class first, then the float64
+ * butterfly of rvz_policy_value_loss. So out_row[r] and grad_logits[r] depend on row r alone
+ * (and W), and the cross-row sums are rvz_policy_value_loss's tree. No floating-point atomics: the
+ * same inputs give the same bytes on every call. Every output element is written exactly once;
+ * out_row and grad_logits may each be null and are then not computed.
+ * rvz_score_loss_scratch_size: rvz_loss_scratch_size's bytes, non-decreasing in n; negative for
+ * bad arguments (n * K >= 2^31 among them).
+ * RVZ_EINVAL (before any HIP call): board size not 6 | 8, n < 0, n * K >= 2^31, a loss weight that
+ * is negative or not finite, and with n > 0 a null logits / margin / scratch / out_loss or a
+ * scratch that is not 16-byte aligned. n = 0 returns RVZ_OK without a launch, and then nothing is
+ * written. */
+int64_t rvz_score_loss_scratch_size(int32_t board_size, int32_t n);
+int rvz_score_loss(int32_t board_size, int32_t n, const float *logits /* [n][K] */,
+                   const float *margin /* [n] */,
+                   const float *weight /* [n], nullable: every row 1 */,
+                   double pdf_weight, double cdf_weight,
+                   void *scratch /* 16-byte aligned */, double *out_loss /* [8] */,
+                   double *out_row /* [n][4], nullable */,
+                   float *grad_logits /* [n][K], nullable */, void *hip_stream);
+
 /* ---- fused self-play ---------------------------------------------------------------------
  * Replaces SelfPlay.generate_games' ply loop (self_play.py:80-101: MCTS.search + get_action_probs
  * + make_move, mcts.py:322-407 and :642-694) together with its leaf evaluator
